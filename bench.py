@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py - BASELINE.json's headline metric on MI355X: query-points/sec of one dense 257^3
-("256^3") occupancy-lattice evaluation for the icon-filter configuration, plus the second half of
-the metric (mesh Chamfer vs the reference's schedule) and a live parity sample against the checker.
+("256^3") occupancy-lattice evaluation for the icon-filter configuration, plus (--full) the second half
+of the metric (mesh Chamfer vs the reference's schedule) and a live parity sample against the checker.
 
 A "step" is one full reconEngine forward for one image: lattice generation, nearest-triangle /
 inside queries against the SMPL-size body (V=6,890 / F=13,776), barycentric attributes, outlier
@@ -13,13 +13,17 @@ BASELINE.json configs[4] with --res 513).  Per-image constants (feature planes, 
 HBM before the timed region; their one-off preparation time is reported in config.prep_ms.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--res 257] [--prior icon|pamir]
-                    [--precision f16x3|f32] [--replicas] [--no-cpu-baseline] [--no-extras]
+                    [--precision f16x3|f32] [--replicas] [--dump-outputs DIR]
+                    [--full [--no-cpu-baseline] [--no-extras]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0 (contract in the task statement; roofline + cpu_baseline objects and
-the extra config entries are described in DESIGN.md "Measurement").  --no-extras skips everything
-after the timed region (use it under rocprofv3 so the trace holds only the dense step).
+Prints ONE JSON line on rank 0 (roofline object and config entries are described in DESIGN.md
+"Measurement").  A plain run sets up, warms up, times the K steps and prints the line; --full adds
+what takes runs of its own: the CPU baseline, the library GEMM ceiling, the zero-data MLP time and the
+post-timing legs (reference schedule, mesh Chamfer, parity sample, cold image, reserve_cus cost, tie
+sensitivity).  Under --full, --no-cpu-baseline / --no-extras drop the CPU baseline / everything after
+the timed region.  --dump-outputs DIR writes the last timed step's result as DIR/*.npy.
 """
 import argparse
 import json
@@ -308,6 +312,30 @@ def library_gemm_ceiling(dev, m=2_097_152, iters=8):
     return out
 
 
+DUMP_BYTES = 48 * 2 ** 20             # --dump-outputs: a volume larger than this is written as a fixed sample of it
+DUMP_SEED = 1993
+
+
+def dump_outputs(path, result):
+    """Write what the timed step returned as float32 / float64 .npy files under `path`: the [res,res,res] occupancy volume
+    (`occupancy.npy`), or above DUMP_BYTES the values at a fixed seeded sample of its flat indices, sorted
+    (`occupancy_sample.npy`, the same indices for the same --res in every run); the mesh of --mesh-exchange as
+    `mesh_verts.npy` / `mesh_faces.npy` (face indices as float64, exact)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    if isinstance(result, (tuple, list)):
+        verts, faces = result
+        np.save(os.path.join(path, "mesh_verts.npy"), verts.detach().cpu().numpy().astype(np.float32))
+        np.save(os.path.join(path, "mesh_faces.npy"), faces.detach().cpu().numpy().astype(np.float64))
+        return
+    vol = result.detach().float().cpu().numpy()
+    if vol.nbytes <= DUMP_BYTES:
+        np.save(os.path.join(path, "occupancy.npy"), vol)
+        return
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(vol.size, DUMP_BYTES // 4, replace=False))
+    np.save(os.path.join(path, "occupancy_sample.npy"), vol.reshape(-1)[idx])
+
+
 def self_launch(n: int) -> int:
     """Run this very command line as n ranks of one node (torch.distributed.run, 127.0.0.1 rendezvous on a free
     port); the ranks' stdout / stderr pass through, so rank 0's JSON line is this process's JSON line."""
@@ -352,13 +380,22 @@ def main():
                          "assembly copies); 'contiguous' = the round-5 layout (one cost-weighted slab per rank, gathered in two halves)")
     ap.add_argument("--gather-to", type=int, default=-1,
                     help="sharded, 'ab' layout: only this rank receives the volume (gather instead of all_gather); -1 = every rank")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: CPU baseline, library GEMM ceiling, zero-data MLP "
+                         "time, and the post-timing legs (reference schedule, mesh Chamfer, parity sample, cold image, reserve_cus "
+                         "cost, tie sensitivity)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / float64, <= 48 MiB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--full-extras", action="store_true",
-                    help="also run the whole-lattice CPU checker legs (parity sample, mesh vs oracle) above 257^3 (513^3: about a minute)")
+                    help="--full: also run the whole-lattice CPU checker legs (parity sample, mesh vs oracle) above 257^3 (513^3: about a minute)")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the post-timing legs (reference schedule, parity sample, mesh Chamfer): "
-                         "use it under rocprofv3 so the trace holds only the dense step")
+                    help="--full: skip the post-timing legs (reference schedule, parity sample, mesh Chamfer)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N`: start the N ranks ourselves - re-exec under torch.distributed.run, one process per
@@ -487,6 +524,9 @@ def main():
         assert occ is None                              # gather_to: only the destination rank holds the volume
     else:
         assert occ is not None and occ.shape == (res, res, res)
+    # the rank that holds the result (gather_to: the destination; otherwise every rank does, rank 0 writes)
+    if args.dump_outputs and occ is not None and rank == (getattr(recon, "gather_to", None) or 0):
+        dump_outputs(args.dump_outputs, occ)
 
     n_points = res ** 3
     # the cut the engine actually used: one Z-slab per rank, or - 'ab' layout - two (DenseReconEngine.ab_pieces)
@@ -555,7 +595,8 @@ def main():
     extras = {}
     sustained = None
     zero_ms = None
-    if not args.no_extras and world == 1 and rank == 0 and args.precision == "f16x3":
+    run_extras = args.full and not args.no_extras
+    if run_extras and world == 1 and rank == 0 and args.precision == "f16x3":
         try:
             sustained = library_gemm_ceiling(dev)
         except Exception as ex:
@@ -564,7 +605,7 @@ def main():
             zero_ms = mlp_zero_data(dev, 257 ** 3)
         except Exception as ex:
             zero_ms = repr(ex)
-    if not args.no_extras and world == 1 and rank == 0 and args.prior == "icon":
+    if run_extras and world == 1 and rank == 0 and args.prior == "icon":
         from icon_amd.recon import AdaptiveReconEngine, export_mesh_device
         from icon_amd import metrics
         # (2) the reference's own coarse-to-fine schedule (Seg3dLossless._forward_faster, ~1 % of the lattice
@@ -792,7 +833,7 @@ def main():
                 out["config"]["pieces"] = [[list(a), list(b)] for a, b in recon.last_stats["pieces"]]
             if mesh_exchange:
                 out["config"]["exchanged_bytes_per_step"] = recon.last_stats.get("exchanged_bytes")
-        if not args.no_cpu_baseline and world == 1 and args.prior == "icon":
+        if args.full and not args.no_cpu_baseline and world == 1 and args.prior == "icon":
             out["cpu_baseline"] = cpu_baseline(a, res)
             out["cpu_baseline"]["gpu_over_cpu"] = value / out["cpu_baseline"]["value"]
         print(json.dumps(out))

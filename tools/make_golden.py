@@ -297,8 +297,76 @@ def section_j_pamir_real_ve():
           "vol occupied", int((vol.abs().sum(1) > 0).sum()))
 
 
+SMPL_FEATS_CASES = [(["sdf", "vis"], 12), (["sdf", "norm", "vis"], 12), (["sdf", "cmap", "vis"], 12), (["vis", "cmap", "norm", "sdf"], 12),
+                    (["sdf"], 6), (["sdf"], 12), (["sdf", "norm", "cmap"], 6), (["cmap"], 6)]
+
+
+def smpl_feats_key(feats, planes):
+    return "smpl_feats_" + "_".join(feats) + f"_{planes}"
+
+
+def smpl_feats_state_dict(a, feats, planes):
+    """regressor of the input width a smpl_feats subset gives: [img | sdf | cmap? | norm?], img = half the planes with 'vis'"""
+    img = planes // 2 if "vis" in feats else planes
+    c0 = img + 1 + (3 if "cmap" in feats else 0) + (3 if "norm" in feats else 0)
+    sd = synth.make_mlp_state_dict(synth.SEED + 5, dims=(c0, 512, 256, 128, 1)) if (c0, planes, len(feats)) != (13, 12, 4) else a.state_dict
+    return c0, sd
+
+
+def reference_outputs(ref, body_net=None):
+    """What tests/test_oracle_vs_reference.py compares the oracle with: the reference's own query_func on fresh ico points,
+    orthogonal() on random calibrations, Seg3dLossless([17, 33]) on the body, query() for each smpl_feats subset.
+    Returns {fixture key: array}; the tests call it themselves where the reference tree exists."""
+    out = {}
+    a = synth.make_assets("ico")
+    netG, cfg = ref_loader.build_netG(a)
+    pts = synth.stratified_points(a.smpl_verts[0], a.smpl_faces[0], 3000, seed=99)
+    with torch.no_grad():
+        out["query_func_ico_3000"] = ref.query_func(cfg, netG, [T(a.features)], T(pts)[None])[0, 0].numpy()
+    del netG
+    A, p = projection_inputs()
+    out["orthogonal_5000"] = ref.orthogonal(T(p.T.copy())[None], T(A)[None])[0].T.numpy()
+    a = synth.make_assets("body")
+    netG, cfg = body_net or ref_loader.build_netG(a)
+    with torch.no_grad():
+        eng = ref.Seg3dLossless(query_func=ref.query_func, b_min=[[-1.0, 1.0, -1.0]], b_max=[[1.0, -1.0, 1.0]],
+                                resolutions=[17, 33], align_corners=True, balance_value=0.5, faster=True)
+        out["seg3d_body_17_33"] = eng(opt=cfg, netG=netG, features=[T(a.features)], proj_matrix=None).numpy()
+    pts = synth.stratified_points(a.smpl_verts[0], a.smpl_faces[0], 2500, seed=31)
+    saved = (netG.smpl_feats, netG.if_regressor)
+    try:
+        for feats, planes in SMPL_FEATS_CASES:
+            c0, sd = smpl_feats_state_dict(a, feats, planes)
+            netG.smpl_feats = feats
+            netG.if_regressor = ref.MLP(filter_channels=[c0, 512, 256, 128, 1], name="if", res_layers=[2, 3, 4], norm="batch", last_op=None).eval()
+            netG.if_regressor.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()}, strict=False)
+            with torch.no_grad():
+                out[smpl_feats_key(feats, planes)] = ref.query_func(cfg, netG, [T(np.ascontiguousarray(a.features[:, :planes]))],
+                                                                    T(pts)[None])[0, 0].numpy()
+    finally:
+        netG.smpl_feats, netG.if_regressor = saved
+    return out
+
+
+def projection_inputs():
+    rng = np.random.RandomState(3)
+    A = np.eye(4, dtype=np.float32)
+    A[:3, :3] += rng.normal(0, 0.1, (3, 3)).astype(np.float32)
+    A[:3, 3] = rng.normal(0, 0.05, 3).astype(np.float32)
+    p = rng.uniform(-1, 1, (5000, 3)).astype(np.float32)
+    return A, p
+
+
+def section_l_oracle_vs_reference():
+    """(l) tests/golden/oracle_vs_reference.npz: the reference's answers tests/test_oracle_vs_reference.py checks the oracle against
+    on machines without the reference tree (where the tree exists the tests recompute them and compare with the fixture too)"""
+    out = reference_outputs(ref_loader.load())
+    np.savez_compressed(os.path.join(OUT, "oracle_vs_reference.npz"), **out)
+    print("oracle_vs_reference:", ", ".join(f"{k} {v.shape}" for k, v in out.items()))
+
+
 if __name__ == "__main__":
-    only = [s for s in ("--display", "--adaptive257", "--adaptive513", "--variants", "--pamir-real") if s in sys.argv]
+    only = [s for s in ("--display", "--adaptive257", "--adaptive513", "--variants", "--pamir-real", "--vs-reference") if s in sys.argv]
     if not only:
         main()
     if not only or "--display" in only:
@@ -311,3 +379,5 @@ if __name__ == "__main__":
         section_i_variants()
     if not only or "--pamir-real" in only:
         section_j_pamir_real_ve()
+    if not only or "--vs-reference" in only:
+        section_l_oracle_vs_reference()
