@@ -216,6 +216,17 @@ struct FusedSigns {
     int world, rank;
 };
 
+// Batched point-mode calls (icon_query_points_batch): the B*N points of a call in subject-major order, point i of subject
+// i / n.  What differs per subject is looked up through this descriptor; the per-call structs (MeshDev, FeatDev, Calib,
+// FusedGeom) keep their layout and the kernels of the unbatched calls never see it.
+struct BatchDev {
+    const MeshDev *meshes;      // [B] device table (icon prior), null otherwise
+    const float *calibs;        // [B][12] device: calibs[b, :3, :4] row-major
+    int64_t n;                  // points per subject
+    int64_t plane_stride;       // floats between two subjects' packed plane sets (FeatDev::planes of subject 0)
+    int B;
+};
+
 }  // namespace icon
 
 // ---- opaque handle bodies -------------------------------------------------------------------
@@ -236,6 +247,20 @@ struct icon_feat {
     float *d_planes = nullptr;
     float *d_vol = nullptr;
     icon::FeatDev dev{};
+    int batch = 1;                    // plane sets held (icon_feat_create_batch), plane_stride floats apart
+    int64_t plane_stride = 0;
+};
+
+// B subject meshes of a batched call (icon_mesh_batch_create): their MeshDev descriptors in one device table
+struct icon_mesh_batch {
+    int B = 0;
+    int64_t V = 0, F = 0;
+    int depth_bound = 0;              // the largest of the subjects' (sizes the cooperative search's LDS)
+    std::vector<const icon_mesh *> subj;
+    icon::MeshDev *d_table = nullptr;
+    icon::MeshDev *h_table = nullptr; // pinned staging of the table upload
+    int *h_status = nullptr;          // host-mapped: ICON_MESH_BATCH_FACES_DIFFER, written by the device face check
+    hipEvent_t done = nullptr;        // recorded behind the face check
 };
 
 struct icon_adaptive;
@@ -305,9 +330,20 @@ int launch_sign(const icon_mesh *mesh, const Calib &cal, int res, int z0, const 
                 const icon_work *work, bool lattice, hipStream_t st);
 // lattice: evaluates the planes [za, zb) of the slab L (global plane numbers; the whole slab = [L.z0, L.z0 + L.nz)),
 // d_occ is the SLAB's output buffer; points: the N points of the call
+// bd: a batched point-mode call (icon_query_points_batch) - mesh, planes and calibration per subject
 int launch_fused_f16x3(const icon_mesh *mesh, const icon_feat *feat, const icon_mlp *mlp, int prior, const Calib &cal,
                        const LatticeMap &L, int za, int zb, const float *d_points, int64_t N, float sdf_clip, int cmap_local,
-                       const icon_work *work, const FusedSigns &fs, float *d_occ, bool lattice, hipStream_t st);
+                       const icon_work *work, const FusedSigns &fs, float *d_occ, bool lattice, hipStream_t st,
+                       const BatchDev *bd = nullptr);
+// sort_points.hip: Morton order of a batched call's B*n points, subject first: subject b's points are the sorted positions
+// [b n, (b + 1) n) (the key carries the subject above the Morton bits)
+int morton_order_batch(icon_work *w, const float *d_points, const float *d_calibs, int64_t n, int B, hipStream_t st, const int32_t **perm);
+// query_kernels.hip: pieces of the point-mode pipeline the batched call shares
+int ensure_work_rows(icon_work *w, int64_t n_points, bool need_x);
+int outlier_list_counted(icon_work *w, int64_t N, hipStream_t st);
+int patch_self_rows(icon_work *w, int64_t N, int cmap_slot, hipStream_t st);
+bool fused_path(int precision, int search);
+void work_mark(icon_work *w, int k, hipStream_t st);
 // per-device launch facts (CU count; one-off kernel attributes): a process may drive several devices
 int device_cu_count(int *n_cu);
 int once_per_device(int kernel_id, const std::function<hipError_t()> &set);   // runs `set` once per (kernel_id, current device), under a mutex

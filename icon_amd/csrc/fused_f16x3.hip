@@ -36,6 +36,7 @@
 #pragma clang fp contract(off)
 
 #include "geom_device.h"
+#include "batch_device.h"
 #include "mlp_f16x3_device.h"
 #include "mlp_plain_device.h"
 
@@ -318,19 +319,19 @@ __device__ __forceinline__ int64_t uniform64(int64_t v)
 // (Requesting the texels of BOTH feature halves up front - their addresses depend on the position only - instead of after
 //  the dependent chain slot -> triangle attributes -> visibility flag was measured: 14.69 vs 14.36 ms; the phase is bound by
 //  the number of loads, not by the length of the chain.)
-__device__ __forceinline__ void icon_row(const FusedGeom &G, f3 p, int64_t i, float *xrow, int64_t K, int64_t rank0)
+__device__ __forceinline__ void icon_row_on(const FusedGeom &G, const MeshDev &m, const FeatDev &f, f3 p, int64_t i, float *xrow, int64_t K, int64_t rank0)
 {
     const uint32_t code = G.code8[i];
     Nearest nr;
     nr.slot = near_slot_of(G.near, i); nr.face = 0;
     nr.d2 = (code & kCodeOutlier) ? 0.0f : near_d2(G.near, i);    // an outlier's sdf is its sign
-    const SdfOut o = sdf_attrs(G.m, p, nr, (code & kCodeInside) != 0);
+    const SdfOut o = sdf_attrs(m, p, nr, (code & kCodeInside) != 0);
     float s = o.sdf;
     f3 cmv = o.cm;
     if (code & kCodeOutlier) {                      // HGPIFuNet.py:298-305
         s = (float)((int)((code >> kCodeSignShift) & 3u) - 1);
         if (G.cmap_local) cmv = mk3(s, s, s);
-        else if (K > 0 && (G.f.smpl_mask & kSmplCmap)) {
+        else if (K > 0 && (f.smpl_mask & kSmplCmap)) {
             // rank among the call's outliers: scan over 256-point blocks + ballots of the 64-point groups
             const int64_t blk = i >> 8;
             const int g = (int)(i >> 6) & 3;
@@ -351,12 +352,17 @@ __device__ __forceinline__ void icon_row(const FusedGeom &G, f3 p, int64_t i, fl
             cmv = mk3(c3[0], c3[1], c3[2]);
         }
     }
-    gather_planes_dyn(G.f, (G.f.n_select == 2 && o.vis == 0.0f) ? 1 : 0, p.x, p.y, xrow);   // feat_select: vis==1 -> front half; no 'vis' in smpl_feats: all channels
-    int hh = G.f.csel;                                  // [img | sdf | cmap (if) | norm (if)], HGPIFuNet.py:301-311
+    gather_planes_dyn(f, (f.n_select == 2 && o.vis == 0.0f) ? 1 : 0, p.x, p.y, xrow);   // feat_select: vis==1 -> front half; no 'vis' in smpl_feats: all channels
+    int hh = f.csel;                                  // [img | sdf | cmap (if) | norm (if)], HGPIFuNet.py:301-311
     xrow[hh++] = s;
-    if (G.f.smpl_mask & kSmplCmap) { xrow[hh] = cmv.x; xrow[hh + 1] = cmv.y; xrow[hh + 2] = cmv.z; hh += 3; }
-    if (G.f.smpl_mask & kSmplNorm) { xrow[hh] = o.nrm.x; xrow[hh + 1] = o.nrm.y; xrow[hh + 2] = o.nrm.z; }
+    if (f.smpl_mask & kSmplCmap) { xrow[hh] = cmv.x; xrow[hh + 1] = cmv.y; xrow[hh + 2] = cmv.z; hh += 3; }
+    if (f.smpl_mask & kSmplNorm) { xrow[hh] = o.nrm.x; xrow[hh + 1] = o.nrm.y; xrow[hh + 2] = o.nrm.z; }
     xrow[kCodeSlot] = __int_as_float((int)(code & kCodeInCube));
+}
+
+__device__ __forceinline__ void icon_row(const FusedGeom &G, f3 p, int64_t i, float *xrow, int64_t K, int64_t rank0)
+{
+    icon_row_on(G, G.m, G.f, p, i, xrow, K, rank0);
 }
 
 // The MLP input row of work item q of the launch (16 floats: reference channel order, zeros, slot kCodeSlot = the in_cube
@@ -388,6 +394,23 @@ __device__ __forceinline__ void build_row(const FusedGeom &G, int64_t q, float *
         } else {
             xrow[hh] = p.z;
         }
+        xrow[kCodeSlot] = __int_as_float((int)in_cube_bit(p));
+    }
+}
+
+// build_row for work item q of a batched point-mode call: subject q / n's calibration, planes and mesh
+template <int PRIOR>
+__device__ __forceinline__ void build_row_batch(const FusedGeom &G, const BatchDev &bd, int64_t q, float *xrow, int64_t K, int64_t rank0)
+{
+    const int64_t b = q / bd.n;
+    const f3 p = project(batch_calib(bd, b), mk3(G.pts[3 * q], G.pts[3 * q + 1], G.pts[3 * q + 2]));
+    const FeatDev f = batch_feat(G.f, bd, b);
+    if (PRIOR == ICON_PRIOR_ICON) {
+        const MeshDev m = bd.meshes[b];
+        icon_row_on(G, m, f, p, q, xrow, K, rank0);
+    } else {                                              // pifu (the pamir prior is refused at B > 1)
+        gather_planes_dyn(f, 0, p.x, p.y, xrow);
+        xrow[f.csel] = p.z;
         xrow[kCodeSlot] = __int_as_float((int)in_cube_bit(p));
     }
 }
@@ -582,6 +605,182 @@ __global__ __launch_bounds__(kF16Block, 2) void k_fused_f16x3(FusedGeom G, float
     }
 }
 
+// The batched point-mode variant (icon_query_points_batch): work item q is point q of the B*n points, subject q / n, whose row
+// build_row_batch assembles from that subject's calibration, planes and mesh.  The body is k_fused_f16x3's point mode line for
+// line; it is a kernel of its own so that the existing instantiations keep their code (routing them through a shared body
+// function was measured to move the SMALL icon variants from 0 to ~220 bytes of scratch per lane).
+template <int PRIOR, bool SMALL>
+__global__ __launch_bounds__(kF16Block, 2) void k_fused_f16x3_batch(FusedGeom G, float *__restrict__ out, MlpF16Dev w, BatchDev bd)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int lane0 = threadIdx.x & 63, wave0 = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    float *Xs = reinterpret_cast<float *>(smem + kXsOff);
+    if (G.clock && threadIdx.x == 0) {
+        if (blockIdx.x == 0) wg_stamp(G.clock);
+        if (blockIdx.x < kMaxProfGrid) wg_stamp(G.clock + 4 + kWgRec * blockIdx.x);
+    }
+
+    // ---- once per workgroup: resident layer-0 operands, side arrays, sign-list geometry ------------------
+    issue_units(w.image, smem + kW0Off, kW0Bytes / 1024, wave0, lane0);
+    float *side = reinterpret_cast<float *>(smem + kSideOff);
+    for (int i = threadIdx.x; i < kSideFloats; i += kF16Block) side[i] = w.side[i];
+    const float *sb0 = side, *sb1 = side + 512, *sb2 = side + 768, *sw3 = side + 896;
+    int64_t K = 0, rank0 = 0;
+    if (PRIOR == ICON_PRIOR_ICON) sign_list_extent(G, K, rank0);
+    // wave-uniform 64-bit values that live across the whole MLP body: keep them in SGPRs, not in the
+    // 250-register vector budget of the MFMA chain
+    K = uniform64(K); rank0 = uniform64(rank0);
+
+    // every workgroup walks a CONTIGUOUS run of tiles: consecutive tiles share the cache lines at their common boundary
+    // (a tile of interior rows does not end on a line) and the triangles / feature texels of neighbouring points, and a
+    // workgroup stays on one XCD - interleaved over the grid, those lines were fetched into two L2s (105 vs 91 MB of HBM
+    // reads per 257^3 launch when the tiles stopped being 1 KiB-aligned runs of the linear order)
+    const int tp = (SMALL && G.N <= (int64_t)(kTilePts / 2) * gridDim.x) ? kTilePts / 2 : kTilePts;       // points per tile (wave-uniform)
+    const int ntiles = (int)((G.N + tp - 1) / tp);                  // N < 2^31 (checked by the launcher)
+    // the workgroup's span of the tiles, and of it the static run it evaluates itself (all of it when the launch is static)
+    const bool stealing = !SMALL && G.steal != nullptr;
+    const int per = ntiles / (int)gridDim.x, rem = ntiles % (int)gridDim.x;
+    int tile = (int)blockIdx.x * per + min((int)blockIdx.x, rem);
+    int tile_end = tile + (stealing ? min(G.steal_static, per) : per + ((int)blockIdx.x < rem ? 1 : 0));
+    tile = __builtin_amdgcn_readfirstlane(tile);
+    tile_end = __builtin_amdgcn_readfirstlane(tile_end);
+    volatile int *pool = reinterpret_cast<volatile int *>(smem + kPoolOff);
+    if (!SMALL) {
+        if (threadIdx.x == 0) {
+            pool[kPoolPer] = per; pool[kPoolRem] = rem; pool[kPoolStatic] = G.steal_static; pool[kPoolGroup] = G.steal_grp;
+            pool[kPoolNGrp] = G.steal_ngrp; pool[kPoolGrid] = (int)gridDim.x; pool[kPoolDone] = 0; pool[kPoolMask] = 0; pool[kPoolNext] = -1;
+            if (stealing && tile >= tile_end) pool_draw(G.steal, pool);      // no static run at all: draw now
+        }
+        __syncthreads();
+        if (stealing && tile >= tile_end) {
+            const int word = __builtin_amdgcn_readfirstlane(pool[kPoolNext]);
+            __syncthreads();                                 // (every wave has read the word before a draw of the loop rewrites it)
+            if (word >= 0) { tile = word & ((1 << kPoolLenShift) - 1); tile_end = tile + (word >> kPoolLenShift); }
+        }
+    }
+    if (tile < tile_end) issue_chunk(w.image, smem, 0, wave0, lane0);
+
+    // `nb`: the group drawn while the LAST tile of the current run is in flight (first tile | tiles << 24; -1: none, or no draw) -
+    // a few returned atomics of wave 4, which has no work item in the feature phase; the barrier that publishes the tile publishes it
+    for (int nb = -1; tile < tile_end;) {
+        // Everything derived from the thread index is re-derived per tile from an opaque copy: hoisted out of
+        // the loop, those ~20 lane-dependent addresses would have to stay live across the 250-register MFMA
+        // body, i.e. be spilled to scratch (measured: 1.5 GB of scratch writes per 257^3 launch).
+        int tid = threadIdx.x;
+        asm volatile("" : "+v"(tid));
+        const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+        const int j = lane & 31, h = lane >> 5;
+        // ---- feature phase: waves 0-3, one work item per thread -> Xs[t][16] -----------------------------
+        const int t = tid;
+        const bool draw = !SMALL && stealing && tile + 1 == tile_end;       // wave-uniform: this is the run's last tile
+        if (!SMALL && draw && t == 256) pool_draw(G.steal, pool);           // (-1: every list is exhausted)
+        const bool worker = t < tp;                             // wave-uniform
+        int64_t q = (int64_t)tile * tp + (worker ? t : 0);
+        if (q >= G.N) q = G.N - 1;                               // padding lanes of the last tile recompute its last item
+        if (worker) build_row_batch<PRIOR>(G, bd, q, Xs + t * kXRow, K, rank0);
+        __syncthreads();          // tile visible; chunk 0 (and, the first time, W0 + side arrays) landed
+
+        nb = (!SMALL && draw) ? __builtin_amdgcn_readfirstlane(pool[kPoolNext]) : -1;
+        if (!SMALL && tid == 0) pool[kPoolDone] = pool[kPoolDone] + 1;
+        const bool more = tile + 1 < tile_end || nb >= 0;       // the first chunks of the next tile ride on the last ones
+        if (SMALL && wave >= (tp >> 5)) {
+            // a wave without points (128-point tiles): its share of the weight stream, the same barriers as the body below
+            for (int c = 0; c < 16; ++c) {
+                issue_chunk(w.image, smem + ((c + 1) & 1) * kBufBytes, c + 1, wave, lane);
+                ICON_CHUNK_BARRIER();
+            }
+            issue_chunk(w.image, smem + kBufBytes, 17, wave, lane);
+            ICON_CHUNK_BARRIER();
+            issue_chunk(w.image, smem, 18, wave, lane);
+            ICON_CHUNK_BARRIER();
+            issue_chunk(w.image, smem + kBufBytes, 19, wave, lane);
+            ICON_CHUNK_BARRIER();
+            if (more) issue_chunk(w.image, smem, 0, wave, lane);
+            ++tile;
+            continue;
+        }
+        // ---- MLP: one wave = 32 points, lane (j,h) holds input slots 8h..8h+7 of point j ------------------
+        const int pt = wave * 32 + j;
+        float xr[8];
+        {
+            const float4 *q = reinterpret_cast<const float4 *>(Xs + pt * kXRow + 8 * h);
+            const float4 a = q[0], b4 = q[1];
+            xr[0] = a.x; xr[1] = a.y; xr[2] = a.z; xr[3] = a.w; xr[4] = b4.x; xr[5] = b4.y; xr[6] = b4.z; xr[7] = b4.w;
+        }
+        const float maskf = (__float_as_int(Xs[pt * kXRow + kCodeSlot]) & (int)kCodeInCube) ? 1.0f : 0.0f;
+#pragma unroll
+        for (int s = 0; s < 8; ++s) xr[s] = (s + 8 * h < w.c0) ? xr[s] : 0.0f;
+        half8 xhi, xlo;
+        split8(xr, xhi, xlo);
+
+        f32x16 acc1[8];
+#pragma unroll
+        for (int m = 0; m < 8; ++m) acc1[m] = ld16(sb1 + (m * 2 + h) * 16);
+        half8 bh[2], bl[2];
+        activate_split(l0_tile(smem + kW0Off, sb0, 0, xhi, xlo, h, lane), LeakyK{w.inv0, w.p0, w.q0}, bh, bl);
+        f32x16 acc2[4];
+        for (int c = 0; c < 16; ++c) {
+            l01_chunk(smem + (c & 1) * kBufBytes, smem + ((c + 1) & 1) * kBufBytes, smem + kW0Off, sb0, w.image, c, acc1, xhi, xlo,
+                      LeakyK{w.inv0, w.p0, w.q0}, h, lane, wave, bh, bl);
+            ICON_CHUNK_BARRIER();
+        }
+#pragma unroll
+        for (int m2 = 0; m2 < 4; ++m2) acc2[m2] = ld16(sb2 + (m2 * 2 + h) * 16);
+        activate_split(acc1[0], LeakyK{w.inv1, w.p1, w.q1}, bh, bl);
+        l2_chunk<0>(smem, smem + kBufBytes, w.image, acc1, acc2, xhi, xlo, LeakyK{w.inv1, w.p1, w.q1}, lane, wave, bh, bl);
+        ICON_CHUNK_BARRIER();
+        l2_chunk<1>(smem + kBufBytes, smem, w.image, acc1, acc2, xhi, xlo, LeakyK{w.inv1, w.p1, w.q1}, lane, wave, bh, bl);
+        ICON_CHUNK_BARRIER();
+        l2_chunk<2>(smem, smem + kBufBytes, w.image, acc1, acc2, xhi, xlo, LeakyK{w.inv1, w.p1, w.q1}, lane, wave, bh, bl);
+        ICON_CHUNK_BARRIER();
+        l2_chunk<3>(smem + kBufBytes, smem, w.image, acc1, acc2, xhi, xlo, LeakyK{w.inv1, w.p1, w.q1}, lane, wave, bh, bl, more ? 0 : -1);
+
+        // ---- layer 3 on the VALU (f32) ---------------------------------------------------------------------
+        const float *w3 = sw3 + h * 72;
+        float part = 0.0f;
+#pragma unroll
+        for (int m2 = 0; m2 < 4; ++m2) {
+            const f32x16 wv = ld16(w3 + m2 * 16);
+#pragma unroll
+            for (int tt = 0; tt < 16; ++tt) {
+                part = fmaf(wv[tt], leaky_scaled(acc2[m2][tt], LeakyK{w.inv2, w.p2, w.q2}), part);
+            }
+        }
+#pragma unroll
+        for (int s = 0; s < 8; ++s) part = fmaf(w3[64 + s], xr[s], part);
+        const float other = __shfl_xor(part, 32);
+        const float y = apply_last_op((part + other) + w.b3, w.last_op);
+        // where this point's occupancy goes is re-derived from the work item (a handful of integer instructions):
+        // nothing lane-dependent lives across the MFMA body
+        const int64_t oq = (int64_t)tile * tp + pt;
+        if (h == 0 && oq < G.N) {
+            out[oq] = masked_result(y, maskf != 0.0f, w.flag);
+        }
+        // the next tile: the one behind this, or the first of the group drawn during this one
+        if (!SMALL && nb >= 0) {
+            tile = nb & ((1 << kPoolLenShift) - 1);
+            tile_end = tile + (nb >> kPoolLenShift);
+        } else ++tile;
+    }
+    if (!SMALL && stealing && threadIdx.x == 0) {
+        // the last workgroup to finish leaves the pair clean for the next launch (every draw of this launch precedes its
+        // workgroup's arrival here in program order; agent-scope atomics on both words)
+        __threadfence();
+        if (atomicAdd(G.steal + 8, 1u) == gridDim.x - 1)
+            for (int k = 0; k < 9; ++k) atomicExch(G.steal + k, 0u);
+    }
+    if (G.clock && threadIdx.x == 0 && blockIdx.x < kMaxProfGrid) {
+        if (blockIdx.x == 0) wg_stamp(G.clock + 2);
+        unsigned long long *rec = G.clock + 4 + kWgRec * blockIdx.x;
+        wg_stamp(rec + 2);
+        unsigned xcc, hw;
+        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
+        rec[4] = ((unsigned long long)xcc << 32) | hw;
+        rec[5] = SMALL ? 0ull : (unsigned long long)pool[kPoolDone];
+    }
+}
+
 // The range safety net (mlp_plain_device.h): when the fused kernel raised the flag, find the work items whose result is not
 // finite, rebuild their input rows exactly as the feature phase did and redo them in plain f32.  One wave per 64 work items.
 template <int PRIOR, bool LATTICE>
@@ -607,6 +806,38 @@ __global__ __launch_bounds__(64) void k_rescue_fused(FusedGeom G, float *__restr
 #pragma unroll
                 for (int k = 0; k < kXRow; ++k) row[k] = 0.0f;
                 build_row<PRIOR, LATTICE>(G, q, row, K, rank0);
+#pragma unroll
+                for (int k = 0; k < kXRow; ++k) s[k] = k < P.c0 ? row[k] : 0.0f;
+            }
+            const float y = mlp_plain_wave(P, s, lane);
+            if (lane == b) out[o] = y;       // only in-cube results are ever non-finite (masked_result): no mask to apply
+            __builtin_amdgcn_wave_barrier();
+        }
+    }
+}
+
+// k_rescue_fused for the batched point-mode variant
+template <int PRIOR>
+__global__ __launch_bounds__(64) void k_rescue_fused_batch(FusedGeom G, float *__restrict__ out, MlpPlain P, const int *flag, int always, BatchDev bd)
+{
+    __shared__ float s[kPlainLds];
+    if (!always && *flag == 0) return;                        // the usual case: one word read per workgroup of a small grid
+    const int lane = threadIdx.x;
+    int64_t K = 0, rank0 = 0;
+    if (PRIOR == ICON_PRIOR_ICON) sign_list_extent(G, K, rank0);
+    for (int64_t base = (int64_t)blockIdx.x * 64; base < G.N; base += (int64_t)gridDim.x * 64) {
+        const int64_t q = base + lane;
+        const int64_t o = q < G.N ? q : 0;
+        const float v = q < G.N ? out[o] : 0.0f;
+        unsigned long long todo = __ballot(not_finite(v));
+        while (todo) {
+            const int b = __ffsll((long long)todo) - 1;
+            todo &= todo - 1;
+            if (lane == b) {
+                float row[kXRow];
+#pragma unroll
+                for (int k = 0; k < kXRow; ++k) row[k] = 0.0f;
+                build_row_batch<PRIOR>(G, bd, q, row, K, rank0);
 #pragma unroll
                 for (int k = 0; k < kXRow; ++k) s[k] = k < P.c0 ? row[k] : 0.0f;
             }
@@ -693,7 +924,7 @@ int once_per_device(int kernel_id, const std::function<hipError_t()> &set)
 
 int launch_fused_f16x3(const icon_mesh *mesh, const icon_feat *feat, const icon_mlp *mlp, int prior, const Calib &cal,
                        const LatticeMap &L, int za, int zb, const float *d_points, int64_t N, float sdf_clip, int cmap_local,
-                       const icon_work *work, const FusedSigns &fs, float *d_occ, bool lattice, hipStream_t st)
+                       const icon_work *work, const FusedSigns &fs, float *d_occ, bool lattice, hipStream_t st, const BatchDev *bd)
 {
     FusedGeom G{};
     if (mesh) G.m = mesh->dev;
@@ -775,11 +1006,27 @@ int launch_fused_f16x3(const icon_mesh *mesh, const icon_feat *feat, const icon_
             debug_sync("k_rescue_fused", st);                                                                              \
         }                                                                                                                  \
     } while (0)
-    if (small) { if (lattice) ICON_FUSED(ICON_PRIOR_ICON, true, 9, true); else ICON_FUSED(ICON_PRIOR_ICON, false, 10, true); }
+#define ICON_FUSED_BATCH(P, ID, ...)                                                                                       \
+    do {                                                                                                                   \
+        if ((rc = once_per_device(ID, [] { return hipFuncSetAttribute(reinterpret_cast<const void *>(k_fused_f16x3_batch<P, ##__VA_ARGS__>), \
+                                                                    hipFuncAttributeMaxDynamicSharedMemorySize, kFusedLds); }))) return rc; \
+        hipLaunchKernelGGL((k_fused_f16x3_batch<P, ##__VA_ARGS__>), dim3(grid), dim3(kF16Block), kFusedLds, st, G, d_occ, w, *bd); \
+        debug_sync("k_fused_f16x3_batch", st);                                                                             \
+        hipLaunchKernelGGL((k_rescue_fused_batch<P>), dim3((unsigned)n_resc), dim3(64), 0, st, G, d_occ, plain, w.flag, rescue_always(), *bd); \
+        debug_sync("k_rescue_fused_batch", st);                                                                            \
+    } while (0)
+    if (bd) {                                    // batched point mode (no lattice, no device-side size, no deferred flag)
+        if (lattice || defer || work->q_n_dev || prior == ICON_PRIOR_PAMIR) return fail(ICON_ERR_UNSUPPORTED, "fused: batched call outside point mode");
+        if (small) ICON_FUSED_BATCH(ICON_PRIOR_ICON, 11, true);
+        else if (prior == ICON_PRIOR_ICON) ICON_FUSED_BATCH(ICON_PRIOR_ICON, 12, false);
+        else ICON_FUSED_BATCH(ICON_PRIOR_PIFU, 13, false);
+    }
+    else if (small) { if (lattice) ICON_FUSED(ICON_PRIOR_ICON, true, 9, true); else ICON_FUSED(ICON_PRIOR_ICON, false, 10, true); }
     else if (prior == ICON_PRIOR_ICON) { if (lattice) ICON_FUSED(ICON_PRIOR_ICON, true, 0); else ICON_FUSED(ICON_PRIOR_ICON, false, 1); }
     else if (prior == ICON_PRIOR_PAMIR) { if (lattice) ICON_FUSED(ICON_PRIOR_PAMIR, true, 2); else ICON_FUSED(ICON_PRIOR_PAMIR, false, 3); }
     else { if (lattice) ICON_FUSED(ICON_PRIOR_PIFU, true, 4); else ICON_FUSED(ICON_PRIOR_PIFU, false, 5); }
 #undef ICON_FUSED
+#undef ICON_FUSED_BATCH
     ICON_HIP(hipGetLastError());
     return ICON_OK;
 }

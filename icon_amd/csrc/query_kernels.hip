@@ -1261,6 +1261,15 @@ FusedSigns self_signs(const icon_work *work)
 
 }  // namespace
 
+namespace icon {
+// the point-mode pipeline's pieces, for the batched call (batch_query.hip)
+int ensure_work_rows(icon_work *w, int64_t n_points, bool need_x) { return ensure_work(w, n_points, need_x); }
+int outlier_list_counted(icon_work *w, int64_t N, hipStream_t st) { return outlier_list(w, N, w->d_signs, true, st); }
+int patch_self_rows(icon_work *w, int64_t N, int cmap_slot, hipStream_t st) { return patch_self(w, N, cmap_slot, st); }
+bool fused_path(int precision, int search) { return want_fused(precision, search); }
+void work_mark(icon_work *w, int k, hipStream_t st) { mark(w, k, st); }
+}  // namespace icon
+
 extern "C" int icon_debug_set_unfused(int on)
 {
     g_unfused = on ? 1 : 0;

@@ -82,6 +82,10 @@ class MeshHandle(_Handle):
     def __init__(self, smpl_verts, smpl_faces, smpl_cmap, smpl_vis, validate: bool = True):
         super().__init__()
         _lib.require_device()
+        for t, what in ((smpl_verts, "smpl_verts"), (smpl_faces, "smpl_faces"), (smpl_cmap, "smpl_cmap"), (smpl_vis, "smpl_vis")):
+            if t.dim() == 3 and t.shape[0] > 1:
+                # one handle is ONE subject: merging a [B,...] batch would give one mesh whose faces index subject 0 only
+                raise IconAmdError(f"{what} has batch size {t.shape[0]}: a MeshHandle holds one subject (MeshBatchHandle for [B,...])")
         v = _dev_f32(smpl_verts, "smpl_verts").reshape(-1, 3)
         f = smpl_faces.detach()
         if not f.is_cuda:
@@ -164,6 +168,57 @@ class MeshHandle(_Handle):
         return out
 
 
+class MeshBatchHandle(_Handle):
+    """B subjects of a batched query() (icon_mesh_batch_create): the tensors of ``smpl_feat_dict`` at batch size B
+    ([B,V,3] / [B,F,3] / [B,V,3] / [B,V,1], lib/net/HGPIFuNet.py:236-240), one device build per subject and a device table of
+    their descriptors.  The reference's check_sign takes subject 0's faces for every subject (lib/dataset/mesh_util.py:393): the
+    batch compares the faces on the device and ``status()`` raises when they differ - as MeshHandle reports bad input, without
+    a synchronisation on the hot path."""
+    _destroy = "icon_mesh_batch_destroy"
+
+    def __init__(self, smpl_verts, smpl_faces, smpl_cmap, smpl_vis):
+        super().__init__()
+        ts = (smpl_verts, smpl_faces, smpl_cmap, smpl_vis)
+        if any(t.dim() != 3 for t in ts):
+            raise IconAmdError("smpl_feat_dict tensors must be [B,V,3] / [B,F,3] / [B,V,3] / [B,V,1] for a batched query")
+        self.B = int(smpl_verts.shape[0])
+        if any(int(t.shape[0]) != self.B for t in ts):
+            raise IconAmdError(f"smpl_feat_dict batch sizes disagree: {[int(t.shape[0]) for t in ts]}")
+        self.subjects = [MeshHandle(smpl_verts[b], smpl_faces[b], smpl_cmap[b], smpl_vis[b], validate=False) for b in range(self.B)]
+        arr = (C.c_void_p * self.B)(*[m.h.value for m in self.subjects])
+        with _on(smpl_verts):
+            check(_lib.lib().icon_mesh_batch_create(arr, C.c_int(self.B), _stream(), C.byref(self.h)), "icon_mesh_batch_create")
+        self.checked = False
+
+    @property
+    def V(self):
+        return self.subjects[0].V
+
+    def status(self, wait: bool = False) -> Optional[int]:
+        """raises IconAmdError for a subject with bad input or faces that differ from subject 0's; None while a check has not run"""
+        if self.checked:
+            return 0
+        pending = False
+        for m in self.subjects:
+            if m.status(wait) is None:
+                pending = True
+        bits = C.c_int(0)
+        try:
+            check(_lib.lib().icon_mesh_batch_status(self.h, C.c_int(int(wait)), C.byref(bits)), "icon_mesh_batch")
+        except IconAmdError:
+            self.reported = True        # said once: replacing this batch does not repeat it
+            raise
+        if pending or bits.value < 0:
+            return None
+        self.checked = True
+        return int(bits.value)
+
+    def close(self):
+        super().close()
+        for m in getattr(self, "subjects", ()):
+            m.close()
+
+
 class FeatHandle(_Handle):
     """Feature planes ``features[-1]`` of HGPIFuNet.filter ([1,C,H,W]) and, for PaMIR, the volume
     encoder output ([1,Cv,D,H,W]); icon_feat_create."""
@@ -198,6 +253,25 @@ class FeatHandle(_Handle):
                   "icon_feat_set_smpl_feats")
         # no synchronisation: the repack kernel is enqueued on the current stream, and the caching allocator
         # recycles the (possibly temporary) source tensors in stream order
+
+
+class FeatBatchHandle(_Handle):
+    """Feature planes ``[B,C,H,W]`` of a batched query(): B plane sets repacked by one launch (icon_feat_create_batch)."""
+    _destroy = "icon_feat_destroy"
+
+    def __init__(self, planes: torch.Tensor, n_select: int, smpl_feats: Sequence[str] = ("sdf", "norm", "vis", "cmap")):
+        super().__init__()
+        p = _dev_f32(planes, "features")
+        if p.dim() != 4:
+            raise IconAmdError("features must be [B,C,H,W]")
+        B, Cc, H, W = (int(x) for x in p.shape)
+        self.B, self.C, self.H, self.W, self.n_select = B, Cc, H, W, n_select
+        with _on(p):
+            check(_lib.lib().icon_feat_create_batch(ptr(p), C.c_int(B), C.c_int(Cc), C.c_int(H), C.c_int(W), C.c_int(n_select), _stream(),
+                                                    C.byref(self.h)), "icon_feat_create_batch")
+        if set(smpl_feats) | {"vis"} != {"sdf", "norm", "vis", "cmap"}:
+            check(_lib.lib().icon_feat_set_smpl_feats(self.h, C.c_int(int("cmap" in smpl_feats)), C.c_int(int("norm" in smpl_feats))),
+                  "icon_feat_set_smpl_feats")
 
 
 def _np32(t) -> np.ndarray:
@@ -539,6 +613,9 @@ class IconQueryEngine:
         m = getattr(self, "_mesh", None)
         if m is not None and not m.checked and m.h:
             m.status(wait)
+        mb = getattr(self, "_mesh_b", None)
+        if mb is not None and not mb.checked and mb.h:
+            mb.status(wait)
 
     def poll_work_status(self) -> None:
         """Raise if a shared-walk search launched on one of this engine's workspaces gave up on a hand-over (icon_work_status:
@@ -764,9 +841,11 @@ class IconQueryEngine:
     # ---- HGPIFuNet.query ---------------------------------------------------------------------------
     @_guarded
     def query(self, features, points, calibs, transforms=None, regressor=None):
-        """features: list of [1,C,H,W]; points [1,3,N]; calibs [1,4,4] (or [1,3,4]) -> list of [1,1,N]"""
-        if points.dim() != 3 or points.shape[0] != 1 or points.shape[1] != 3:
-            raise IconAmdError("points must be [1,3,N] (batch size 1)")
+        """features: list of [B,C,H,W]; points [B,3,N]; calibs [B,4,4] (or [B,3,4]) -> list of [B,1,N]"""
+        if points.dim() != 3 or points.shape[1] != 3 or points.shape[0] < 1:
+            raise IconAmdError("points must be [B,3,N]")
+        if points.shape[0] != 1:
+            return self._query_batch(features, points, calibs, transforms, regressor)
         if not points.is_cuda:
             raise IconAmdError("points are on the CPU; icon_amd has no CPU path")
         n = int(points.shape[2])
@@ -807,6 +886,88 @@ class IconQueryEngine:
                 C.c_int(_lib.SEARCH[self.search]), C.c_int(self._precision()), self._work().h, _stream()),
                 "icon_query_points")
             preds.append(occ.view(1, 1, n))
+        return preds
+
+    def _mesh_batch_handle(self, B: int) -> MeshBatchHandle:
+        d = self.netG.smpl_feat_dict if self.netG is not None else self._smpl_feat_dict
+        if d is None:
+            raise IconAmdError("no SMPL tensors bound: call filter() on the network or set_mesh() first")
+        ts = (d["smpl_verts"], d["smpl_faces"], d["smpl_cmap"], d["smpl_vis"])
+        if any(t.dim() != 3 or int(t.shape[0]) != B for t in ts):
+            raise IconAmdError(f"smpl_feat_dict tensors {[tuple(t.shape) for t in ts]} do not hold the {B} subjects of the points")
+        k = _key(*ts)
+        if k != getattr(self, "_mesh_b_key", None):
+            old = getattr(self, "_mesh_b", None)
+            if old is not None and not old.checked and old.h and not getattr(old, "reported", False):
+                # as _mesh_handle: a batch nobody polled is checked before it is dropped (its work was enqueued a call ago)
+                try:
+                    old.status(wait=True)
+                except IconAmdError as e:
+                    self._mesh_b, self._mesh_b_key, self._mesh_b_src = None, None, None
+                    raise IconAmdError(f"the PREVIOUS SMPL batch bound to this engine was invalid (its results are wrong): {e}") from e
+            self._mesh_b = MeshBatchHandle(*ts)
+            self._mesh_b_key, self._mesh_b_src = k, ts      # strong refs: see _key
+        elif not self._mesh_b.checked:
+            self._mesh_b.status()
+        return self._mesh_b
+
+    def _feat_batch_handle(self, im_feat: torch.Tensor, cache: dict) -> FeatBatchHandle:
+        """one handle per feature stack of the call, kept while the next call passes the same tensors (``cache``: this call's)"""
+        k = _key(im_feat)
+        old = getattr(self, "_featb", {})
+        if k in old:
+            cache[k] = old[k]
+        elif k not in cache:
+            select = 2 if (self.prior_type == "icon" and "vis" in self.smpl_feats) else 1
+            cache[k] = (FeatBatchHandle(im_feat, select, smpl_feats=self.smpl_feats), im_feat)
+        return cache[k][0]
+
+    def _query_batch(self, features, points, calibs, transforms, regressor):
+        """HGPIFuNet.query at batch size B > 1: ONE native call per feature stack over the B*N points (icon_query_points_batch),
+        so the reference's batch-global outlier cmap list (lib/net/HGPIFuNet.py:303-305) is reproduced and the number of
+        launches does not depend on B"""
+        B, n = int(points.shape[0]), int(points.shape[2])
+        if not points.is_cuda:
+            raise IconAmdError("points are on the CPU; icon_amd has no CPU path")
+        if transforms is not None:
+            raise IconAmdError("query(transforms=...) is not supported: the reference's own orthogonal() raises for any "
+                               "`transforms` (lib/net/geometry.py:57-60) and none of its callers passes one")
+        if calibs.dim() != 3 or int(calibs.shape[0]) != B or tuple(calibs.shape[1:]) not in ((4, 4), (3, 4)):
+            raise IconAmdError(f"calibs {tuple(calibs.shape)} must be [{B},4,4] or [{B},3,4] (torch.baddbmm does not broadcast a batch)")
+        for im_feat in features:
+            if im_feat.dim() != 4 or int(im_feat.shape[0]) != B:
+                raise IconAmdError(f"feature stack {tuple(im_feat.shape)} must be [{B},C,H,W]")
+        if B * n >= 2 ** 31:
+            raise IconAmdError(f"B * N = {B * n}: a batched call holds fewer than 2^31 points")
+        if self.prior_type == "pamir":
+            raise IconAmdError("the pamir prior is evaluated at batch size 1 only (per-subject voxelisation + volume encoder)")
+        if self.search == "brute":
+            raise IconAmdError("search='brute' (validation path) is evaluated at batch size 1 only")
+        if self.tie_rule is not None:
+            raise IconAmdError("tie_rule (diagnostics) is evaluated at batch size 1 only")
+        reg = self._bound_regressor(regressor)
+        if len(features) and self._composed_reason(reg, features[-1]) is not None:
+            raise IconAmdError("this regressor / feature layout takes the composed path (icon_amd/composed.py), which is evaluated at batch size 1 only")
+        if self._callnorm_spec(reg) is not None:
+            raise IconAmdError("Group / InstanceNorm regressors (icon_amd/callnorm.py) are evaluated at batch size 1 only")
+        mb = self._mesh_batch_handle(B) if self.prior_type == "icon" else None
+        mlp = self._mlp_handle(regressor)
+        if n == 0:
+            return [torch.empty((B, 1, 0), dtype=torch.float32, device=points.device) for _ in features]
+        # calibrations stay on (or go to) the device: the kernels read subject b's 12 floats themselves
+        calib12 = calibs[:, :3, :4].detach().to(points.device, torch.float32).contiguous()
+        pts = points.detach().transpose(1, 2).to(torch.float32).contiguous()
+        cache, preds = {}, []
+        for im_feat in features:
+            feat = self._feat_batch_handle(im_feat, cache)
+            occ = torch.empty(B * n, dtype=torch.float32, device=points.device)
+            check(_lib.lib().icon_query_points_batch(
+                mb.h if mb is not None else C.c_void_p(0), feat.h, mlp.h, C.c_int(_lib.PRIOR[self.prior_type]),
+                C.c_float(np.float32(self.sdf_clip)), C.c_int(_lib.CMAP[self.cmap_mode]), ptr(calib12), ptr(pts), C.c_int64(n),
+                C.c_int(B), ptr(occ), C.c_int(_lib.SEARCH[self.search]), C.c_int(self._precision()), self._work().h, _stream()),
+                "icon_query_points_batch")
+            preds.append(occ.view(B, 1, n))
+        self._featb = cache
         return preds
 
     # ---- dense lattice (one rank's share of reconEngine) ------------------------------------------------

@@ -226,6 +226,40 @@ int icon_query_points_dcalib(const icon_mesh_t *mesh, const icon_feat_t *feat, c
                              int search, int precision, icon_work_t *work, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Batched HGPIFuNet.query: B subjects per call, as the reference's own query takes them (points [B,3,N],
+ * calibs [B,4,4], every feature stack [B,C,H,W], smpl_feat_dict tensors [B,...]; lib/net/HGPIFuNet.py:268-367,
+ * lib/dataset/mesh_util.py:357-396).  The call is ONE point-mode call over the B*N points in subject-major order
+ * (point i belongs to subject i / N): the outlier sign list of the reference cmap mode is therefore the reference's
+ * batch-global list (smpl_sdf[outlier].repeat(1,1,3) flattens all B subjects, HGPIFuNet.py:303-305), and the number of
+ * kernel launches does not depend on B.
+ *
+ * icon_mesh_batch_create: B meshes built by icon_mesh_create(_arena) (one subject each), which must outlive the batch.
+ * V and F must agree (ICON_ERR_ARG otherwise).  check_sign(verts, faces[0], points) (mesh_util.py:393) uses subject 0's
+ * faces for every subject: the batch compares every subject's faces with subject 0's ON THE DEVICE (no read-back) and
+ * reports a difference through icon_mesh_batch_status, as the device mesh build reports bad input.  Enqueued on `stream`.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct icon_mesh_batch icon_mesh_batch_t;
+int icon_mesh_batch_create(const icon_mesh_t *const *meshes, int B, void *stream, icon_mesh_batch_t **out);
+int icon_mesh_batch_destroy(icon_mesh_batch_t *mb);
+/* bits = 0: the subjects share their faces; -1: the check has not run yet (wait = 0 never blocks); otherwise ICON_ERR_ARG
+ * ("faces differ") with bits = ICON_MESH_BATCH_FACES_DIFFER.  wait = 1 synchronises with the check. */
+#define ICON_MESH_BATCH_FACES_DIFFER 0x10
+int icon_mesh_batch_status(const icon_mesh_batch_t *mb, int wait, int *bits);
+
+/* B feature stacks d_planes [B,C,H,W] in ONE repack launch; the handle holds B plane sets at a fixed stride.  No volume
+ * (the pamir prior is refused at B > 1). */
+int icon_feat_create_batch(const float *d_planes, int B, int C, int H, int W, int n_select, void *stream, icon_feat_t **out);
+
+/* d_calibs [B,12] (calibs[:, :3, :4] row-major, DEVICE), d_points [B,N,3] (the [B,3,N] tensor transposed), d_occ [B,N].
+ * mb: a batch of B meshes (icon prior), NULL otherwise; feat: a batch of B plane sets (icon_feat_create_batch).
+ * ICON_ERR_UNSUPPORTED: the pamir prior, search = ICON_SEARCH_BRUTE, a workspace with a tie rule; ICON_ERR_ARG: batch
+ * sizes that disagree, B*N >= 2^31.  No synchronisation. */
+int icon_query_points_batch(const icon_mesh_batch_t *mb, const icon_feat_t *feat, const icon_mlp_t *mlp,
+                            int prior_type, float sdf_clip, int cmap_mode, const float *d_calibs,
+                            const float *d_points, int64_t N, int B, float *d_occ,
+                            int search, int precision, icon_work_t *work, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Dense lattice evaluation: one rank's Z-slab of reconEngine (lib/common/seg3d_lossless.py).
  * Lattice of `res`^3 points (res odd, :84-86), world mapping of batch_eval (:125-137) with
  * align_corners=True, b_min=[-1,1,-1], b_max=[1,-1,1] (apps/ICON.py:78-90), identity calibration
