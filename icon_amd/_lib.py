@@ -35,6 +35,7 @@ SYMBOLS = [
     "icon_export_mesh", "icon_mc_count", "icon_mc_emit", "icon_mc_count_range", "icon_mc_emit_keyed", "icon_debug_traversal_stats", "icon_debug_set_unfused",
     "icon_visibility", "icon_mesh_components", "icon_clean_mesh", "icon_semantic_voxelize",
     "icon_mesh_batch_create", "icon_mesh_batch_destroy", "icon_mesh_batch_status", "icon_feat_create_batch", "icon_query_points_batch",
+    "icon_feat_batch_set_volume", "icon_semantic_voxelize_batch",
 ]
 
 _lib = None

@@ -23,6 +23,7 @@ __device__ __forceinline__ FeatDev batch_feat(const FeatDev &f, const BatchDev &
 {
     FeatDev g = f;
     g.planes = f.planes + b * bd.plane_stride;
+    g.vol = f.vol + b * bd.vol_stride;        // (no volume: null, stride 0)
     return g;
 }
 

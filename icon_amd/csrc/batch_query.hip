@@ -11,7 +11,7 @@
 // Launches per call and feature stack do not depend on B:
 //   icon, N*B < kPacketMinPoints : k_nearest_coop_batch, k_sign_batch, [outlier list], fused kernel + rescue
 //   icon, larger calls           : Morton keys + radix sort, k_nearest_batch, k_sign_batch, [outlier list], fused + rescue
-//   pifu                         : fused kernel + rescue
+//   pamir / pifu                 : fused kernel + rescue (pamir: subject b's packed volume, icon_feat_batch_set_volume)
 // (f32 / ICON_AMD_UNFUSED=1: k_features_batch, [patch], the MLP kernels over the materialised rows instead of the fused kernel.)
 //
 // The packet search needs every wavefront's 64 points to belong to one subject (it walks that subject's BVH with scalar loads):
@@ -186,11 +186,17 @@ __global__ __launch_bounds__(kBatchBlock) void k_features_batch(BatchDev bd, Fea
         row[hh++] = s;
         if (f.smpl_mask & kSmplCmap) { row[hh] = cmv.x; row[hh + 1] = cmv.y; row[hh + 2] = cmv.z; hh += 3; }
         if (f.smpl_mask & kSmplNorm) { row[hh] = o.nrm.x; row[hh + 1] = o.nrm.y; row[hh + 2] = o.nrm.z; }
-    } else {                                  // pifu
+    } else {                                  // pamir / pifu
         gather_planes_dyn(f, 0, p.x, p.y, g);
         const int h = f.csel;
         for (int k = 0; k < h; ++k) row[k] = g[k];
-        row[h] = p.z;
+        if (PRIOR == ICON_PRIOR_PAMIR) {      // subject b's volume (batch_feat), as k_features
+            float v[8];
+            if (f.vpad == 8) gather_volume<2>(f, p.x, p.y, p.z, v); else gather_volume<1>(f, p.x, p.y, p.z, v);
+            for (int k = 0; k < f.Cv; ++k) row[h + k] = v[k];
+        } else {
+            row[h] = p.z;
+        }
     }
     row[kCodeSlot] = __int_as_float((int)code);
     if (live) { store_row(X, i, row); code8[i] = (uint8_t)code; }
@@ -297,6 +303,30 @@ extern "C" int icon_feat_create_batch(const float *d_planes, int B, int C, int H
     return ICON_OK;
 }
 
+extern "C" int icon_feat_batch_set_volume(icon_feat_t *feat, const float *d_vol, int B, int Cv, int Dv, int Hv, int Wv, void *stream)
+{
+    ICON_ARG(feat != nullptr && d_vol != nullptr, "icon_feat_batch_set_volume: null argument");
+    ICON_ARG(B == feat->batch, "icon_feat_batch_set_volume: the volume holds another number of subjects than the feature handle");
+    ICON_ARG(feat->dev.vol == nullptr, "icon_feat_batch_set_volume: the handle already holds a volume");
+    ICON_ARG(Cv > 0 && Dv > 1 && Hv > 1 && Wv > 1, "icon_feat_batch_set_volume: bad volume");
+    if (Cv > 8) return fail(ICON_ERR_UNSUPPORTED, "icon_feat_batch_set_volume: more than 8 volume channels");
+    hipStream_t st = (hipStream_t)stream;
+    // icon_feat_create's layout per subject: a volume is a "plane" of D*H rows, channel-last, zero padded to vpad
+    const int vpad = (Cv + 3) & ~3;
+    const int64_t stride = (int64_t)Dv * Hv * Wv * vpad;
+    float *d = nullptr;
+    hipError_t e = hipMalloc((void **)&d, (size_t)stride * B * sizeof(float));
+    if (e != hipSuccess) return fail(ICON_ERR_HIP, std::string("hipMalloc vol: ") + hipGetErrorString(e));
+    hipLaunchKernelGGL(k_pack_planes_batch, dim3((unsigned)std::max(1, 1024 / B), 1, (unsigned)B), dim3(256), 0, st, d_vol, Cv, Dv * Hv, Wv, 1,
+                       Cv, vpad, stride, d);
+    e = hipGetLastError();
+    if (e != hipSuccess) { (void)hipFree(d); return fail(ICON_ERR_HIP, std::string("pack volume: ") + hipGetErrorString(e)); }
+    feat->d_vol = d; feat->vol_stride = stride;
+    FeatDev &f = feat->dev;
+    f.vol = d; f.Cv = Cv; f.Dv = Dv; f.Hv = Hv; f.Wv = Wv; f.vpad = vpad;
+    return ICON_OK;
+}
+
 extern "C" int icon_query_points_batch(const icon_mesh_batch_t *mb, const icon_feat_t *feat, const icon_mlp_t *mlp,
                                        int prior_type, float sdf_clip, int cmap_mode, const float *d_calibs,
                                        const float *d_points, int64_t N, int B, float *d_occ,
@@ -305,10 +335,9 @@ extern "C" int icon_query_points_batch(const icon_mesh_batch_t *mb, const icon_f
     ICON_ARG(mlp && work && feat && d_points && d_occ && d_calibs, "icon_query_points_batch: null argument");
     ICON_ARG(N >= 0 && B >= 1, "icon_query_points_batch: bad N / B");
     ICON_ARG(N * (int64_t)B < (1ll << 31), "icon_query_points_batch: B * N must be below 2^31");
-    if (prior_type == ICON_PRIOR_PAMIR) return fail(ICON_ERR_UNSUPPORTED, "icon_query_points_batch: the pamir prior is evaluated at batch size 1 only");
     if (search == ICON_SEARCH_BRUTE) return fail(ICON_ERR_UNSUPPORTED, "icon_query_points_batch: search 'brute' is evaluated at batch size 1 only");
     if (work->tie_rule != 0) return fail(ICON_ERR_UNSUPPORTED, "icon_query_points_batch: tie rules are evaluated at batch size 1 only");
-    ICON_ARG(prior_type == ICON_PRIOR_ICON || prior_type == ICON_PRIOR_PIFU, "icon_query_points_batch: unknown prior_type");
+    ICON_ARG(prior_type == ICON_PRIOR_ICON || prior_type == ICON_PRIOR_PAMIR || prior_type == ICON_PRIOR_PIFU, "icon_query_points_batch: unknown prior_type");
     ICON_ARG(feat->batch == B, "icon_query_points_batch: the feature handle holds another number of subjects");
     const FeatDev &f = feat->dev;
     int c0 = 0;
@@ -316,6 +345,11 @@ extern "C" int icon_query_points_batch(const icon_mesh_batch_t *mb, const icon_f
         ICON_ARG(mb != nullptr, "icon_query_points_batch: the icon prior needs a mesh batch");
         ICON_ARG(mb->B == B, "icon_query_points_batch: the mesh batch holds another number of subjects");
         c0 = f.csel + 1 + ((f.smpl_mask & kSmplCmap) ? 3 : 0) + ((f.smpl_mask & kSmplNorm) ? 3 : 0);
+    } else if (prior_type == ICON_PRIOR_PAMIR) {
+        // [index(im_feat, xy) | index(vol_feat, xyz)] per subject (lib/net/HGPIFuNet.py:346-353): no mesh, no search, no sign pass
+        ICON_ARG(f.n_select == 1, "icon_query_points_batch: pamir prior needs n_select = 1");
+        ICON_ARG(f.vol != nullptr, "icon_query_points_batch: the pamir prior needs a feature handle with a volume (icon_feat_batch_set_volume)");
+        c0 = f.csel + f.Cv;
     } else {
         ICON_ARG(f.n_select == 1, "icon_query_points_batch: pifu prior needs n_select = 1");
         c0 = f.csel + 1;
@@ -332,6 +366,7 @@ extern "C" int icon_query_points_batch(const icon_mesh_batch_t *mb, const icon_f
     const icon_mesh *mesh0 = (prior_type == ICON_PRIOR_ICON) ? mb->subj[0] : nullptr;
     BatchDev bd{};
     bd.meshes = mesh0 ? mb->d_table : nullptr; bd.calibs = d_calibs; bd.n = N; bd.plane_stride = feat->plane_stride; bd.B = B;
+    bd.vol_stride = feat->vol_stride;
     const bool needs_patch = prior_type == ICON_PRIOR_ICON && cmap_mode == ICON_CMAP_REFERENCE && (f.smpl_mask & kSmplCmap);
     const int local = (cmap_mode == ICON_CMAP_LOCAL) ? 1 : 0;
     work_mark(work, 0, st);
@@ -383,6 +418,8 @@ extern "C" int icon_query_points_batch(const icon_mesh_batch_t *mb, const icon_f
     const unsigned nb = (unsigned)((NB + kBatchBlock - 1) / kBatchBlock);
     if (prior_type == ICON_PRIOR_ICON)
         hipLaunchKernelGGL(k_features_batch<ICON_PRIOR_ICON>, dim3(nb), dim3(kBatchBlock), 0, st, bd, f, d_points, NB, local, near, work->d_x, work->d_code8);
+    else if (prior_type == ICON_PRIOR_PAMIR)
+        hipLaunchKernelGGL(k_features_batch<ICON_PRIOR_PAMIR>, dim3(nb), dim3(kBatchBlock), 0, st, bd, f, d_points, NB, local, near, work->d_x, work->d_code8);
     else
         hipLaunchKernelGGL(k_features_batch<ICON_PRIOR_PIFU>, dim3(nb), dim3(kBatchBlock), 0, st, bd, f, d_points, NB, local, near, work->d_x, work->d_code8);
     ICON_HIP(hipGetLastError());

@@ -225,6 +225,7 @@ struct BatchDev {
     int64_t n;                  // points per subject
     int64_t plane_stride;       // floats between two subjects' packed plane sets (FeatDev::planes of subject 0)
     int B;
+    int64_t vol_stride;         // floats between two subjects' packed volumes (FeatDev::vol of subject 0; pamir prior)
 };
 
 }  // namespace icon
@@ -249,6 +250,7 @@ struct icon_feat {
     icon::FeatDev dev{};
     int batch = 1;                    // plane sets held (icon_feat_create_batch), plane_stride floats apart
     int64_t plane_stride = 0;
+    int64_t vol_stride = 0;           // volumes of a batched handle (icon_feat_batch_set_volume), vol_stride floats apart
 };
 
 // B subject meshes of a batched call (icon_mesh_batch_create): their MeshDev descriptors in one device table

@@ -398,7 +398,7 @@ __device__ __forceinline__ void build_row(const FusedGeom &G, int64_t q, float *
     }
 }
 
-// build_row for work item q of a batched point-mode call: subject q / n's calibration, planes and mesh
+// build_row for work item q of a batched point-mode call: subject q / n's calibration, planes, mesh and volume
 template <int PRIOR>
 __device__ __forceinline__ void build_row_batch(const FusedGeom &G, const BatchDev &bd, int64_t q, float *xrow, int64_t K, int64_t rank0)
 {
@@ -408,9 +408,16 @@ __device__ __forceinline__ void build_row_batch(const FusedGeom &G, const BatchD
     if (PRIOR == ICON_PRIOR_ICON) {
         const MeshDev m = bd.meshes[b];
         icon_row_on(G, m, f, p, q, xrow, K, rank0);
-    } else {                                              // pifu (the pamir prior is refused at B > 1)
+    } else {
         gather_planes_dyn(f, 0, p.x, p.y, xrow);
-        xrow[f.csel] = p.z;
+        if (PRIOR == ICON_PRIOR_PAMIR) {                  // index(vol_feat, xyz) of subject b's volume, as build_row
+            float v[8];
+            if (f.vpad == 8) gather_volume<2>(f, p.x, p.y, p.z, v); else gather_volume<1>(f, p.x, p.y, p.z, v);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) if (k < f.Cv) xrow[f.csel + k] = v[k];
+        } else {
+            xrow[f.csel] = p.z;
+        }
         xrow[kCodeSlot] = __int_as_float((int)in_cube_bit(p));
     }
 }
@@ -1016,9 +1023,10 @@ int launch_fused_f16x3(const icon_mesh *mesh, const icon_feat *feat, const icon_
         debug_sync("k_rescue_fused_batch", st);                                                                            \
     } while (0)
     if (bd) {                                    // batched point mode (no lattice, no device-side size, no deferred flag)
-        if (lattice || defer || work->q_n_dev || prior == ICON_PRIOR_PAMIR) return fail(ICON_ERR_UNSUPPORTED, "fused: batched call outside point mode");
+        if (lattice || defer || work->q_n_dev) return fail(ICON_ERR_UNSUPPORTED, "fused: batched call outside point mode");
         if (small) ICON_FUSED_BATCH(ICON_PRIOR_ICON, 11, true);
         else if (prior == ICON_PRIOR_ICON) ICON_FUSED_BATCH(ICON_PRIOR_ICON, 12, false);
+        else if (prior == ICON_PRIOR_PAMIR) ICON_FUSED_BATCH(ICON_PRIOR_PAMIR, 14, false);
         else ICON_FUSED_BATCH(ICON_PRIOR_PIFU, 13, false);
     }
     else if (small) { if (lattice) ICON_FUSED(ICON_PRIOR_ICON, true, 9, true); else ICON_FUSED(ICON_PRIOR_ICON, false, 10, true); }

@@ -16,6 +16,8 @@
 // k_vox_occ: one thread per tetrahedron sweeps the voxels of its bounding box (25k tetrahedra, boxes of a few
 //            voxels).  k_vox_sem: one thread per voxel, 256 consecutive x per workgroup; workgroups without an
 //            inside voxel leave after one ballot; the others stream the surface vertices through LDS tiles.
+// k_vox_occ_batch / k_vox_sem_batch: the same bodies for B subjects in one launch each (icon_semantic_voxelize_batch, the
+//            batched pamir query: subject 0's tetrahedra and one code table for every subject, lib/net/HGPIFuNet.py:316-324).
 #pragma clang fp contract(off)
 #include "common.h"
 
@@ -30,10 +32,10 @@ __device__ __forceinline__ float vox_det3(const float *o, const float *u, const 
     return fmaf(cz, pz, fmaf(cy, py, cx * px));
 }
 
-__global__ __launch_bounds__(256) void k_vox_occ(const float *__restrict__ verts, int64_t V, const int64_t *__restrict__ tets, int64_t T,
-                                                 int res, uint8_t *__restrict__ occ)
+// the occupancy sweep of tetrahedron t of one subject (k_vox_occ, and subject blockIdx.y of k_vox_occ_batch)
+__device__ __forceinline__ void vox_occ_tet(const float *__restrict__ verts, int64_t V, const int64_t *__restrict__ tets, int64_t T,
+                                            int res, uint8_t *__restrict__ occ, int64_t t)
 {
-    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (t >= T) return;
     const int64_t ia = tets[4 * t], ib = tets[4 * t + 1], ic = tets[4 * t + 2], id = tets[4 * t + 3];
     if (ia < 0 || ib < 0 || ic < 0 || id < 0 || ia >= V || ib >= V || ic >= V || id >= V) return;
@@ -61,14 +63,30 @@ __global__ __launch_bounds__(256) void k_vox_occ(const float *__restrict__ verts
             }
 }
 
+__global__ __launch_bounds__(256) void k_vox_occ(const float *__restrict__ verts, int64_t V, const int64_t *__restrict__ tets, int64_t T,
+                                                 int res, uint8_t *__restrict__ occ)
+{
+    vox_occ_tet(verts, V, tets, T, res, occ, (int64_t)blockIdx.x * 256 + threadIdx.x);
+}
+
+// B subjects in one launch (grid y = subject): subject b's vertices [V][3] at verts + 3 V b, its occupancy at occ + res^3 b; the
+// tetrahedra are shared (subject 0's, update_param(smpl_tetra=voxel_faces[0]), lib/net/HGPIFuNet.py:321-323)
+__global__ __launch_bounds__(256) void k_vox_occ_batch(const float *__restrict__ verts, int64_t V, const int64_t *__restrict__ tets, int64_t T,
+                                                       int res, uint8_t *__restrict__ occ)
+{
+    const int64_t b = blockIdx.y;
+    vox_occ_tet(verts + 3 * V * b, V, tets, T, res, occ + (int64_t)res * res * res * b, (int64_t)blockIdx.x * 256 + threadIdx.x);
+}
+
 constexpr int kVoxTile = 256;
 
-__global__ __launch_bounds__(256) void k_vox_sem(const float *__restrict__ verts, int64_t V_surf, const float *__restrict__ code,
-                                                 int res, float k2, const uint8_t *__restrict__ occ, float *__restrict__ out)
+// the semantic value of voxel i of one subject (k_vox_sem, and subject blockIdx.y of k_vox_sem_batch); every thread of the
+// workgroup takes part (LDS tiles, one barrier-reduction)
+__device__ __forceinline__ void vox_sem_voxel(const float *__restrict__ verts, int64_t V_surf, const float *__restrict__ code,
+                                              int res, float k2, const uint8_t *__restrict__ occ, float *__restrict__ out, int64_t i)
 {
     __shared__ float sv[kVoxTile * 3], sc[kVoxTile * 3];
     const int64_t n = (int64_t)res * res * res;
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const bool in = i < n && occ[i];
     if (i < n && !in) { out[3 * i] = 0.0f; out[3 * i + 1] = 0.0f; out[3 * i + 2] = 0.0f; }
     if (!__syncthreads_or(in ? 1 : 0)) return;
@@ -90,6 +108,21 @@ __global__ __launch_bounds__(256) void k_vox_sem(const float *__restrict__ verts
             }
     }
     if (in) { out[3 * i] = s0 / ws; out[3 * i + 1] = s1 / ws; out[3 * i + 2] = s2 / ws; }
+}
+
+__global__ __launch_bounds__(256) void k_vox_sem(const float *__restrict__ verts, int64_t V_surf, const float *__restrict__ code,
+                                                 int res, float k2, const uint8_t *__restrict__ occ, float *__restrict__ out)
+{
+    vox_sem_voxel(verts, V_surf, code, res, k2, occ, out, (int64_t)blockIdx.x * 256 + threadIdx.x);
+}
+
+// B subjects in one launch (grid y = subject): subject b's surface vertices are the first V_surf of its V, the code table is
+// shared (smpl_vertex_code_batch is the table tiled, lib/net/voxelize.py:84-85), its volume [res][res][res][3] at out + 3 res^3 b
+__global__ __launch_bounds__(256) void k_vox_sem_batch(const float *__restrict__ verts, int64_t V, int64_t V_surf, const float *__restrict__ code,
+                                                       int res, float k2, const uint8_t *__restrict__ occ, float *__restrict__ out)
+{
+    const int64_t b = blockIdx.y, n = (int64_t)res * res * res;
+    vox_sem_voxel(verts + 3 * V * b, V_surf, code, res, k2, occ + n * b, out + 3 * n * b, (int64_t)blockIdx.x * 256 + threadIdx.x);
 }
 
 }  // namespace icon
@@ -116,5 +149,27 @@ extern "C" int icon_semantic_voxelize(const float *d_verts, int64_t V, int64_t V
     if (e == hipSuccess) e = hipStreamSynchronize(st);       // the scratch occupancy is freed below
     (void)hipFree(d_occ);
     if (e != hipSuccess) return fail(ICON_ERR_HIP, std::string("icon_semantic_voxelize: ") + hipGetErrorString(e));
+    return ICON_OK;
+}
+
+extern "C" int icon_semantic_voxelize_batch(const float *d_verts, int B, int64_t V, int64_t V_surf, const float *d_code,
+                                            const int64_t *d_tets, int64_t T, int res, float sigma, uint8_t *d_occ, float *d_out, void *stream)
+{
+    ICON_ARG(d_verts && d_code && d_out && d_occ && (T == 0 || d_tets), "icon_semantic_voxelize_batch: null argument");
+    ICON_ARG(B >= 1 && B <= 65535, "icon_semantic_voxelize_batch: B must be 1 .. 65,535");
+    ICON_ARG(V > 0 && V_surf > 0 && V_surf <= V && T >= 0, "icon_semantic_voxelize_batch: bad sizes");
+    ICON_ARG(res >= 2 && res <= 1024 && sigma > 0.0f, "icon_semantic_voxelize_batch: bad resolution / sigma");
+    ICON_ARG((T + 255) / 256 < (1ll << 31), "icon_semantic_voxelize_batch: too many tetrahedra for one launch");
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t n = (int64_t)res * res * res;
+    // no allocation and no synchronisation: the occupancy scratch [B][res^3] is the caller's, cleared on the stream
+    hipError_t e = hipMemsetAsync(d_occ, 0, (size_t)n * B, st);
+    if (e == hipSuccess && T > 0)
+        hipLaunchKernelGGL(k_vox_occ_batch, dim3((unsigned)((T + 255) / 256), (unsigned)B), dim3(256), 0, st, d_verts, V, d_tets, T, res, d_occ);
+    if (e == hipSuccess)
+        hipLaunchKernelGGL(k_vox_sem_batch, dim3((unsigned)((n + 255) / 256), (unsigned)B), dim3(256), 0, st, d_verts, V, V_surf, d_code, res,
+                           1.0f / (2.0f * sigma * sigma), d_occ, d_out);
+    if (e == hipSuccess) e = hipGetLastError();
+    if (e != hipSuccess) return fail(ICON_ERR_HIP, std::string("icon_semantic_voxelize_batch: ") + hipGetErrorString(e));
     return ICON_OK;
 }

@@ -256,10 +256,12 @@ class FeatHandle(_Handle):
 
 
 class FeatBatchHandle(_Handle):
-    """Feature planes ``[B,C,H,W]`` of a batched query(): B plane sets repacked by one launch (icon_feat_create_batch)."""
+    """Feature planes ``[B,C,H,W]`` of a batched query(): B plane sets repacked by one launch (icon_feat_create_batch) and, for
+    PaMIR, the B volume encoder outputs ``[B,Cv,D,H,W]`` (icon_feat_batch_set_volume)."""
     _destroy = "icon_feat_destroy"
 
-    def __init__(self, planes: torch.Tensor, n_select: int, smpl_feats: Sequence[str] = ("sdf", "norm", "vis", "cmap")):
+    def __init__(self, planes: torch.Tensor, n_select: int, smpl_feats: Sequence[str] = ("sdf", "norm", "vis", "cmap"),
+                 vol: Optional[torch.Tensor] = None):
         super().__init__()
         p = _dev_f32(planes, "features")
         if p.dim() != 4:
@@ -269,6 +271,13 @@ class FeatBatchHandle(_Handle):
         with _on(p):
             check(_lib.lib().icon_feat_create_batch(ptr(p), C.c_int(B), C.c_int(Cc), C.c_int(H), C.c_int(W), C.c_int(n_select), _stream(),
                                                     C.byref(self.h)), "icon_feat_create_batch")
+            if vol is not None:
+                v = _dev_f32(vol, "vol_feat")
+                if v.dim() != 5:
+                    raise IconAmdError(f"vol_feat {tuple(v.shape)} must be [B,Cv,D,H,W]")
+                Bv, Cv, Dv, Hv, Wv = (int(x) for x in v.shape)
+                check(_lib.lib().icon_feat_batch_set_volume(self.h, ptr(v), C.c_int(Bv), C.c_int(Cv), C.c_int(Dv), C.c_int(Hv), C.c_int(Wv),
+                                                            _stream()), "icon_feat_batch_set_volume")
         if set(smpl_feats) | {"vis"} != {"sdf", "norm", "vis", "cmap"}:
             check(_lib.lib().icon_feat_set_smpl_feats(self.h, C.c_int(int("cmap" in smpl_feats)), C.c_int(int("norm" in smpl_feats))),
                   "icon_feat_set_smpl_feats")
@@ -513,6 +522,7 @@ class IconQueryEngine:
         self._mlp = self._mlp_key = self._mlp_src = None
         self._vol = self._vol_key = self._vol_src = None
         self._vol_cached = None
+        self._volb_key = self._volb_src = self._volb_cached = None     # pamir at B > 1: its own cache (_pamir_volume_batch)
         self._smpl_feat_dict = None
         self._regressor = None
 
@@ -546,7 +556,8 @@ class IconQueryEngine:
 
     def set_volume_features(self, vol_feat: torch.Tensor) -> None:
         """PaMIR: the VolumeEncoder output [1,Cv,D,H,W] (lib/net/HGPIFuNet.py:321-325), computed once
-        per image on PyTorch-ROCm by the caller (hoisted out of query())."""
+        per image on PyTorch-ROCm by the caller (hoisted out of query()).  A batched query() takes
+        [B,Cv,D,H,W], one volume per subject; a B other than the points' raises."""
         self._vol = vol_feat
 
     # ---- handle caches ---------------------------------------------------------------------------
@@ -677,6 +688,39 @@ class IconQueryEngine:
                 self._vol_cached = netG.ve(vol, intermediate_output=False)[-1]
             self._vol_key, self._vol_src = k, (d["voxel_verts"], d["voxel_faces"])
         return self._vol_cached
+
+    def _pamir_volume_batch(self, B: int) -> torch.Tensor:
+        """VolumeEncoder output [B,Cv,D,H,W] of a batch (lib/net/HGPIFuNet.py:314-325 at batch size B), once per batch of voxel
+        tensors, cached apart from the B = 1 volume of _pamir_volume.  The reference strips every subject's padding with
+        subject 0's counts (:316-319) and voxelises every subject with subject 0's tetrahedra (:321-323)."""
+        if self._vol is not None:
+            v = self._vol
+            if v.dim() != 5 or int(v.shape[0]) != B:
+                raise IconAmdError(f"set_volume_features: vol_feat {tuple(v.shape)} does not hold the {B} subjects of the points ([B,Cv,D,H,W])")
+            return v
+        netG = self.netG
+        if netG is None or not hasattr(netG, "voxelization") or not hasattr(netG, "ve"):
+            raise IconAmdError("pamir prior: call set_volume_features(vol_feat) (VolumeEncoder output [B,Cv,D,H,W])")
+        d = netG.smpl_feat_dict
+        k = _key(d["voxel_verts"], d["voxel_faces"])
+        if k != self._volb_key:
+            if d["voxel_verts"].dim() != 3 or int(d["voxel_verts"].shape[0]) != B or d["voxel_faces"].dim() != 3 or int(d["voxel_faces"].shape[0]) != B:
+                raise IconAmdError(f"voxel_verts {tuple(d['voxel_verts'].shape)} / voxel_faces {tuple(d['voxel_faces'].shape)} do not hold the {B} "
+                                   "subjects of the points")
+            vv = d["voxel_verts"][:, :-int(d["pad_v_num"][0]), :]          # subject 0's counts for every subject (:316-319)
+            vf = d["voxel_faces"][:, :-int(d["pad_f_num"][0]), :]
+            vox = netG.voxelization
+            if self._use_reference_voxelizer():
+                with torch.no_grad():
+                    vox.update_param(batch_size=vf.shape[0], smpl_tetra=vf[0].detach().cpu().numpy())   # HGPIFuNet.py:321-323
+                    vol = vox(vv)                                                                        # :324
+            else:
+                vol = semantic_voxelization_batch(vv, vf[0], vox.smpl_vertex_code, res=int(getattr(vox, "volume_res", 128)),
+                                                  sigma=float(getattr(vox, "sigma", 0.05)))
+            with torch.no_grad():
+                self._volb_cached = netG.ve(vol, intermediate_output=False)[-1]       # eval: [out_lst[-1]] (VE.py:166-183)
+            self._volb_key, self._volb_src = k, (d["voxel_verts"], d["voxel_faces"])
+        return self._volb_cached
 
     def _use_reference_voxelizer(self) -> bool:
         """voxelizer='reference': always netG.voxelization (needs the voxelize_cuda wheel); 'hip': always the HIP
@@ -911,15 +955,16 @@ class IconQueryEngine:
             self._mesh_b.status()
         return self._mesh_b
 
-    def _feat_batch_handle(self, im_feat: torch.Tensor, cache: dict) -> FeatBatchHandle:
-        """one handle per feature stack of the call, kept while the next call passes the same tensors (``cache``: this call's)"""
-        k = _key(im_feat)
+    def _feat_batch_handle(self, im_feat: torch.Tensor, cache: dict, vol: Optional[torch.Tensor] = None) -> FeatBatchHandle:
+        """one handle per feature stack (and pamir volume) of the call, kept while the next call passes the same tensors (``cache``:
+        this call's)"""
+        k = _key(im_feat) + (_key(vol) if vol is not None else ())
         old = getattr(self, "_featb", {})
         if k in old:
             cache[k] = old[k]
         elif k not in cache:
             select = 2 if (self.prior_type == "icon" and "vis" in self.smpl_feats) else 1
-            cache[k] = (FeatBatchHandle(im_feat, select, smpl_feats=self.smpl_feats), im_feat)
+            cache[k] = (FeatBatchHandle(im_feat, select, smpl_feats=self.smpl_feats, vol=vol), im_feat, vol)
         return cache[k][0]
 
     def _query_batch(self, features, points, calibs, transforms, regressor):
@@ -939,8 +984,11 @@ class IconQueryEngine:
                 raise IconAmdError(f"feature stack {tuple(im_feat.shape)} must be [{B},C,H,W]")
         if B * n >= 2 ** 31:
             raise IconAmdError(f"B * N = {B * n}: a batched call holds fewer than 2^31 points")
-        if self.prior_type == "pamir":
-            raise IconAmdError("the pamir prior is evaluated at batch size 1 only (per-subject voxelisation + volume encoder)")
+        if self.prior_type == "pamir" and len(features) > 1:
+            # zip(features, vol_feats) with the one-element vol_feats of eval evaluates features[0] only (HGPIFuNet.py:325,329);
+            # filter() hands eval callers exactly one stack (:250-252)
+            raise IconAmdError("the pamir prior at batch size B > 1 evaluates exactly one feature stack (lib/net/HGPIFuNet.py:325,329 "
+                               f"zips {len(features)} stacks with the single volume of eval)")
         if self.search == "brute":
             raise IconAmdError("search='brute' (validation path) is evaluated at batch size 1 only")
         if self.tie_rule is not None:
@@ -957,9 +1005,10 @@ class IconQueryEngine:
         # calibrations stay on (or go to) the device: the kernels read subject b's 12 floats themselves
         calib12 = calibs[:, :3, :4].detach().to(points.device, torch.float32).contiguous()
         pts = points.detach().transpose(1, 2).to(torch.float32).contiguous()
+        vol = self._pamir_volume_batch(B) if self.prior_type == "pamir" and len(features) else None
         cache, preds = {}, []
         for im_feat in features:
-            feat = self._feat_batch_handle(im_feat, cache)
+            feat = self._feat_batch_handle(im_feat, cache, vol)
             occ = torch.empty(B * n, dtype=torch.float32, device=points.device)
             check(_lib.lib().icon_query_points_batch(
                 mb.h if mb is not None else C.c_void_p(0), feat.h, mlp.h, C.c_int(_lib.PRIOR[self.prior_type]),
@@ -1145,6 +1194,33 @@ def semantic_voxelization(voxel_verts: torch.Tensor, voxel_tets: torch.Tensor, v
                                             C.c_int64(t.shape[0]), C.c_int(res), C.c_float(sigma), ptr(out), _stream()),
           "icon_semantic_voxelize")
     return out.permute(3, 0, 1, 2).unsqueeze(0)
+
+
+def semantic_voxelization_batch(voxel_verts: torch.Tensor, voxel_tets: torch.Tensor, vertex_code, res: int = 128,
+                                sigma: float = 0.05) -> torch.Tensor:
+    """``Voxelization.forward`` at batch size B (lib/net/voxelize.py:119-137, as HGPIFuNet.query calls it at :316-324) in one launch
+    of each kernel: ``voxel_verts [B,V,3]`` (padding stripped with subject 0's count), ``voxel_tets [T,4]`` (or [1,T,4]) - subject 0's
+    tetrahedra, which update_param tiles over the batch - and ``vertex_code [Vs,3]`` shared by every subject ->
+    ``[B,3,res,res,res]`` (b,c,d,h,w).  Subject b is bit for bit ``semantic_voxelization(voxel_verts[b:b+1], voxel_tets)``."""
+    if not voxel_verts.is_cuda:
+        raise IconAmdError("semantic_voxelization_batch needs device tensors (there is no CPU path)")
+    if voxel_verts.dim() != 3 or voxel_verts.shape[2] != 3:
+        raise IconAmdError(f"voxel_verts {tuple(voxel_verts.shape)} must be [B,V,3]")
+    dev = voxel_verts.device
+    v = voxel_verts.detach().to(torch.float32).contiguous()
+    B, V = int(v.shape[0]), int(v.shape[1])
+    t = voxel_tets.detach().to(dev, torch.int64).reshape(-1, 4).contiguous()
+    code = torch.as_tensor(np.asarray(vertex_code, dtype=np.float32) if not isinstance(vertex_code, torch.Tensor) else vertex_code)
+    code = code.detach().to(dev, torch.float32).reshape(-1, 3).contiguous()
+    if code.shape[0] > V:
+        raise IconAmdError("semantic_voxelization_batch: more vertex codes than vertices")
+    occ = torch.empty(B * res ** 3, dtype=torch.uint8, device=dev)
+    out = torch.empty((B, res, res, res, 3), dtype=torch.float32, device=dev)
+    with _on(v):
+        check(_lib.lib().icon_semantic_voxelize_batch(ptr(v), C.c_int(B), C.c_int64(V), C.c_int64(code.shape[0]), ptr(code), ptr(t),
+                                                      C.c_int64(t.shape[0]), C.c_int(res), C.c_float(sigma), ptr(occ), ptr(out), _stream()),
+              "icon_semantic_voxelize_batch")
+    return out.permute(0, 4, 1, 2, 3)
 
 
 def get_visibility(xy: torch.Tensor, z: torch.Tensor, faces: torch.Tensor, image_size: int = 2 ** 12) -> torch.Tensor:

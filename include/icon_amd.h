@@ -246,14 +246,23 @@ int icon_mesh_batch_destroy(icon_mesh_batch_t *mb);
 #define ICON_MESH_BATCH_FACES_DIFFER 0x10
 int icon_mesh_batch_status(const icon_mesh_batch_t *mb, int wait, int *bits);
 
-/* B feature stacks d_planes [B,C,H,W] in ONE repack launch; the handle holds B plane sets at a fixed stride.  No volume
- * (the pamir prior is refused at B > 1). */
+/* B feature stacks d_planes [B,C,H,W] in ONE repack launch; the handle holds B plane sets at a fixed stride.  No volume:
+ * the pamir prior adds one with icon_feat_batch_set_volume. */
 int icon_feat_create_batch(const float *d_planes, int B, int C, int H, int W, int n_select, void *stream, icon_feat_t **out);
 
+/* pamir prior at batch size B: the VolumeEncoder output of every subject, d_vol [B,Cv,D,H,W] f32 - what
+ * self.ve(vol, intermediate_output=False) returns for the [B,3,D,H,W] semantic volume (lib/net/HGPIFuNet.py:324-325,
+ * lib/net/VE.py:166-183) - packed by ONE launch into the layout icon_feat_create gives a single volume, B volumes at a
+ * fixed stride.  Subject b's points sample subject b's volume (index(vol_feat, xyz), HGPIFuNet.py:349-353).
+ * ICON_ERR_ARG: B other than the handle's, a handle that already holds a volume, bad sizes; ICON_ERR_UNSUPPORTED: Cv > 8.
+ * Enqueued on `stream`; allocates once (the handle's volume), no synchronisation. */
+int icon_feat_batch_set_volume(icon_feat_t *feat, const float *d_vol, int B, int Cv, int Dv, int Hv, int Wv, void *stream);
+
 /* d_calibs [B,12] (calibs[:, :3, :4] row-major, DEVICE), d_points [B,N,3] (the [B,3,N] tensor transposed), d_occ [B,N].
- * mb: a batch of B meshes (icon prior), NULL otherwise; feat: a batch of B plane sets (icon_feat_create_batch).
- * ICON_ERR_UNSUPPORTED: the pamir prior, search = ICON_SEARCH_BRUTE, a workspace with a tie rule; ICON_ERR_ARG: batch
- * sizes that disagree, B*N >= 2^31.  No synchronisation. */
+ * mb: a batch of B meshes (icon prior), NULL otherwise; feat: a batch of B plane sets (icon_feat_create_batch) - for the
+ * pamir prior with B volumes (icon_feat_batch_set_volume; MLP input [img(C) | vol(Cv)], HGPIFuNet.py:346-353).
+ * ICON_ERR_UNSUPPORTED: search = ICON_SEARCH_BRUTE, a workspace with a tie rule; ICON_ERR_ARG: batch sizes that
+ * disagree, B*N >= 2^31, a pamir call on a handle without a volume.  No synchronisation. */
 int icon_query_points_batch(const icon_mesh_batch_t *mb, const icon_feat_t *feat, const icon_mlp_t *mlp,
                             int prior_type, float sdf_clip, int cmap_mode, const float *d_calibs,
                             const float *d_points, int64_t N, int B, float *d_occ,
@@ -451,6 +460,16 @@ int icon_mc_emit_keyed(float *d_verts, int64_t *d_faces, int64_t *d_keys, icon_w
  * d_out [res,res,res,3] f32 in (z,y,x,c) order - the layout lib/net/voxelize.py:22 documents.  Synchronises. */
 int icon_semantic_voxelize(const float *d_verts, int64_t V, int64_t V_surf, const float *d_code,
                            const int64_t *d_tets, int64_t T, int res, float sigma, float *d_out, void *stream);
+
+/* The same for B subjects in one launch of each kernel, as Voxelization.forward takes a batch (lib/net/voxelize.py:119-137,
+ * HGPIFuNet.py:316-324): d_verts [B,V,3] (each subject's padding already stripped with subject 0's count, :316-317), ONE
+ * tetrahedron table d_tets [T,4] for every subject (update_param(smpl_tetra=voxel_faces[0]) tiles subject 0's, :321-323;
+ * vertices_to_tetrahedrons indexes each subject's own vertices with it), ONE code table d_code [V_surf,3]
+ * (smpl_vertex_code_batch is the table tiled; its length is the surface vertex count, voxelize.py:84-85,128-129),
+ * d_occ a caller-supplied scratch of B*res^3 bytes, d_out [B,res,res,res,3].  Subject b is bit for bit what
+ * icon_semantic_voxelize gives for its vertices.  Enqueued on `stream`: no allocation, no synchronisation. */
+int icon_semantic_voxelize_batch(const float *d_verts, int B, int64_t V, int64_t V_surf, const float *d_code,
+                                 const int64_t *d_tets, int64_t T, int res, float sigma, uint8_t *d_occ, float *d_out, void *stream);
 
 /* ---- connected components of a triangle mesh --------------------------------------------------------
  * the engine of clean_mesh (lib/dataset/mesh_util.py:778-791: trimesh split, keep the component with the
