@@ -92,7 +92,9 @@ struct FusedGeom {
     // XCD's list once its own is exhausted.  A die that holds a lower clock under the power limit leaves groups to the others;
     // tiles change XCD - and with them the triangles and texels in that XCD's L2 - only for the few percent that really move.
     // steal[8] counts the workgroups that have finished; the last one zeroes all nine words (clean for the next launch, no
-    // memset).  steal == nullptr: the whole launch is static (SMALL variants, device-side N).
+    // memset).  steal == nullptr: the whole launch is static (SMALL variants, and every launch whose N lives on the device: the
+    // launcher sizes steal_static from the host's upper bound, the spans are cut from the real count - a span shorter than
+    // steal_static would leave its last tile to a pool group that starts behind it).
     unsigned int *steal;
     int steal_static, steal_grp, steal_ngrp;
 };
@@ -995,7 +997,8 @@ int launch_fused_f16x3(const icon_mesh *mesh, const icon_feat *feat, const icon_
         // steal_permille / 1000 of every workgroup's span is handed out in groups to whoever finishes first.
         const int per = (int)(ntiles / grid);
         const int pool_len = (int)((int64_t)per * work->steal_permille / 1000);
-        if (!small && work->d_steal && pool_len > 0 && ntiles > (int64_t)grid) {
+        // (a schedule level's N is the bound r^3: its device-side count gets the static partition - see FusedGeom::steal)
+        if (!small && !work->q_n_dev && work->d_steal && pool_len > 0 && ntiles > (int64_t)grid) {
             G.steal = work->d_steal; G.steal_grp = std::min(work->steal_grp, kMaxStealGroup);
             G.steal_static = per - pool_len;
             G.steal_ngrp = (pool_len + 1 + G.steal_grp - 1) / G.steal_grp;     // covers the spans that are one tile longer

@@ -565,3 +565,96 @@ def test_fused_kernel_tile_partition_covers_every_tile_once():
                 seen[got[0]:got[0] + got[1]] += 1
         assert (seen == 1).all(), (grid, ntiles, permille, grp, np.flatnonzero(seen != 1)[:8])
         assert all(counters[x] >= ((grid - x + 7) >> 3) * ngrp for x in range(8))
+
+
+def _launcher_steal(ntiles, grid, permille, grp, small=False, count_on_device=False, pool_on_device_count=False):
+    """launch_fused_f16x3's choice of partition, from the HOST tile count (a schedule level's bound r^3): None (static) or
+    (steal_static, steal_grp, steal_ngrp).  ``pool_on_device_count``: the rule before the fix (a pool whenever pool_len > 0,
+    also when the real count lives on the device)."""
+    per = ntiles // grid
+    pool_len = per * permille // 1000
+    if small or (count_on_device and not pool_on_device_count) or pool_len <= 0 or ntiles <= grid:
+        return None
+    grp = min(grp, 127)
+    return per - pool_len, grp, (pool_len + 1 + grp - 1) // grp
+
+
+def _kernel_tiles(ntiles, grid, steal, rng):
+    """k_fused_f16x3 + pool_draw with the DEVICE tile count: per / rem / spans from ``ntiles``, the launcher's ``steal`` and
+    ``grid`` as passed; the workgroups draw in random order from random home XCDs -> evaluations per tile"""
+    per, rem = ntiles // grid, ntiles % grid
+    seen = np.zeros(ntiles, np.int32)
+    span = lambda b: (b * per + min(b, rem), b * per + min(b, rem) + per + (1 if b < rem else 0))
+    if steal is None:
+        for b in range(grid):
+            seen[span(b)[0]:span(b)[1]] += 1
+        return seen
+    stat, grp, ngrp = steal
+    for b in range(grid):
+        seen[span(b)[0]:span(b)[0] + min(stat, per)] += 1
+    counters, masks = [0] * 8, [0] * grid
+    active, home = list(range(grid)), rng.randint(0, 8, grid)
+    while active:
+        b = active[int(rng.randint(len(active)))]
+        got = None
+        for s in range(8):
+            x = (int(home[b]) + s) & 7
+            if (masks[b] >> x) & 1:
+                continue
+            nwg = (grid - x + 7) >> 3
+            while got is None:
+                t = counters[x]; counters[x] += 1
+                if t >= nwg * ngrp:
+                    masks[b] |= 1 << x
+                    break
+                k, g = divmod(t, ngrp)
+                sb, eb = span(x + 8 * k)
+                a = sb + stat + g * grp
+                if a < eb:
+                    got = (a, min(grp, eb - a))
+            if got is not None:
+                break
+        if got is None:
+            active.remove(b)
+        else:
+            seen[got[0]:got[0] + got[1]] += 1
+    return seen
+
+
+def test_fused_kernel_tile_partition_with_device_side_count():
+    """A level of the coarse-to-fine schedule (csrc/adaptive.hip) launches the fused kernel with N = r^3, an upper bound: the
+    launcher sizes the grid and the partition from it, the kernel cuts its spans from the real count it reads on the device
+    (FusedGeom::n_dev).  Restated on the host with two tile counts - the bound for the launcher, a random count <= the bound
+    for the kernel: every tile is evaluated exactly once under the launcher's rule (a count that lives on the device is
+    static).  Fed the rule before it (a pool whenever pool_len > 0), the restatement finds the tiles that fall between a
+    span's end and its first pool group: `rem` of them whenever the device-side `per` is below steal_static."""
+    rng = np.random.RandomState(12)
+    cus = 256
+    # the launcher's numbers of a 256-CU device: the 129^3 / 257^3 levels of the [33 .. 513] schedule, default set_steal(150, 2)
+    for bound, npts, permille, grp, lost in [(129 ** 3, 100_000, 150, 2, 135), (129 ** 3, 1_500_000, 150, 2, 228),
+                                             (257 ** 3, 2_000_000, 150, 2, 133), (129 ** 3, 1_870_000, 150, 2, 0),
+                                             (129 ** 3, 1_870_000, 40, 1, 137)]:
+        nt_host, nt_dev = -(-bound // 256), -(-npts // 256)
+        grid = min(nt_host, cus)
+        for before, want in ((True, lost), (False, 0)):
+            steal = _launcher_steal(nt_host, grid, permille, grp, count_on_device=True, pool_on_device_count=before)
+            seen = _kernel_tiles(nt_dev, grid, steal, rng)
+            assert (seen <= 1).all() and int((seen == 0).sum()) == want, (bound, npts, permille, grp, before)
+    found = 0
+    for trial in range(600):
+        grid = int(rng.choice([1, 3, 7, 8, 9, 31, 64, 200, 240, 256]))
+        nt_host = int(grid + 1 + rng.randint(0, 40 * grid))
+        nt_dev = int(rng.randint(0, nt_host + 1)) if trial % 4 else nt_host
+        permille = int(rng.choice([1, 37, 40, 100, 150, 500, 999, 1000]))
+        grp = int(rng.choice([1, 2, 3, 8, 127]))
+        small = trial % 7 == 0                       # the icon prior's SMALL launches: static whatever the setting
+        seen = _kernel_tiles(nt_dev, grid, _launcher_steal(nt_host, grid, permille, grp, small, count_on_device=True), rng)
+        assert (seen == 1).all(), (grid, nt_host, nt_dev, permille, grp, np.flatnonzero(seen != 1)[:8])
+        # the rule before the fix: exactly the `rem` extra tiles are lost when the device-side per is below steal_static
+        before = _launcher_steal(nt_host, grid, permille, grp, small, count_on_device=True, pool_on_device_count=True)
+        seen = _kernel_tiles(nt_dev, grid, before, rng)
+        per, rem = nt_dev // grid, nt_dev % grid
+        lost = rem if before is not None and before[0] > per else 0
+        assert (seen <= 1).all() and int((seen == 0).sum()) == lost, (grid, nt_host, nt_dev, permille, grp)
+        found += lost > 0
+    assert found > 50                                # the random trials do reach the regime that lost tiles
