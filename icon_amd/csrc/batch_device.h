@@ -1,6 +1,7 @@
 // batch_device.h - per-subject lookups of a batched point-mode call (icon_query_points_batch): point i of the call belongs to
-// subject b = i / n; its calibration, mesh and feature planes come from the BatchDev descriptor (common.h).  Shared by
-// batch_query.hip (search, sign, materialised rows) and fused_f16x3.hip (the fused kernel's batched variant).
+// subject b = i / n; its calibration, mesh and feature planes come from the BatchDev descriptor (common.h).  The one place that
+// says how: read by the batched instantiations of the point-mode kernel templates (query_device.h: k_nearest_coop, k_features;
+// fused_f16x3.hip: k_sign_wide, build_row of k_fused_f16x3 / k_rescue_fused) and by k_nearest_batch (batch_query.hip).
 #pragma once
 #pragma clang fp contract(off)
 

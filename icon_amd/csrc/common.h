@@ -218,7 +218,7 @@ struct FusedSigns {
 
 // Batched point-mode calls (icon_query_points_batch): the B*N points of a call in subject-major order, point i of subject
 // i / n.  What differs per subject is looked up through this descriptor; the per-call structs (MeshDev, FeatDev, Calib,
-// FusedGeom) keep their layout and the kernels of the unbatched calls never see it.
+// FusedGeom) keep their layout.
 struct BatchDev {
     const MeshDev *meshes;      // [B] device table (icon prior), null otherwise
     const float *calibs;        // [B][12] device: calibs[b, :3, :4] row-major
@@ -227,6 +227,10 @@ struct BatchDev {
     int B;
     int64_t vol_stride;         // floats between two subjects' packed volumes (FeatDev::vol of subject 0; pamir prior)
 };
+// Where the work items of a point-mode kernel template come from - a compile-time property of an instantiation: only the
+// Src::Batch ones read a BatchDev (batch_device.h); the others take mesh and calibration as launch-uniform kernel arguments
+// and compile to what they were before the batched call existed (profiles/kernel_resources_*.txt).
+enum class Src { Lattice, Points, Batch };
 
 }  // namespace icon
 
@@ -329,7 +333,7 @@ float f16_to_f32(uint16_t h);
 float pick_scale(const std::vector<float> &W);     // power of two that brings max|W| to ~8192
 // fused_f16x3.hip
 int launch_sign(const icon_mesh *mesh, const Calib &cal, int res, int z0, const float *d_points, int64_t N, float sdf_clip,
-                const icon_work *work, bool lattice, hipStream_t st);
+                const icon_work *work, bool lattice, hipStream_t st, const BatchDev *bd = nullptr);
 // lattice: evaluates the planes [za, zb) of the slab L (global plane numbers; the whole slab = [L.z0, L.z0 + L.nz)),
 // d_occ is the SLAB's output buffer; points: the N points of the call
 // bd: a batched point-mode call (icon_query_points_batch) - mesh, planes and calibration per subject
@@ -340,12 +344,12 @@ int launch_fused_f16x3(const icon_mesh *mesh, const icon_feat *feat, const icon_
 // sort_points.hip: Morton order of a batched call's B*n points, subject first: subject b's points are the sorted positions
 // [b n, (b + 1) n) (the key carries the subject above the Morton bits)
 int morton_order_batch(icon_work *w, const float *d_points, const float *d_calibs, int64_t n, int B, hipStream_t st, const int32_t **perm);
-// query_kernels.hip: pieces of the point-mode pipeline the batched call shares
-int ensure_work_rows(icon_work *w, int64_t n_points, bool need_x);
-int outlier_list_counted(icon_work *w, int64_t N, hipStream_t st);
-int patch_self_rows(icon_work *w, int64_t N, int cmap_slot, hipStream_t st);
-bool fused_path(int precision, int search);
-void work_mark(icon_work *w, int k, hipStream_t st);
+// query_kernels.hip: pieces of the point-mode pipeline the batched call (batch_query.hip) shares
+int ensure_work(icon_work *w, int64_t n_points, bool need_x);                          // scratch for n_points (need_x: the 64-byte input rows too)
+int outlier_list(icon_work *w, int64_t N, int8_t *signs, bool counted, hipStream_t st);   // counted: k_sign left the block counts
+int patch_self(icon_work *w, int64_t N, int cmap_slot, hipStream_t st);
+bool want_fused(int precision, int search);
+void mark(icon_work *w, int k, hipStream_t st);                                       // profiling event k of the call
 // per-device launch facts (CU count; one-off kernel attributes): a process may drive several devices
 int device_cu_count(int *n_cu);
 int once_per_device(int kernel_id, const std::function<hipError_t()> &set);   // runs `set` once per (kernel_id, current device), under a mutex

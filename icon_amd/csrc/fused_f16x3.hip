@@ -190,19 +190,26 @@ __global__ __launch_bounds__(256) void k_sign(MeshDev m, Calib cal, int res, int
 // Point mode, calls of few points (the levels of the reference's schedule): FOUR lanes per point walk the point's ray-bin list
 // (every 4th entry each; the parities add up) - one thread per point was a ~30 us launch of pure latency (a chain of ~100
 // dependent load pairs).  A workgroup is still one 256-point block of the outlier scan / one tile of the fused kernel.
+// BATCH (icon_query_points_batch): the block is 256 points of the linear order of the B*n points; every point's mesh and
+// calibration are its subject's (looked up per lane: a block may straddle two subjects), no device-side size.
+template <bool BATCH>
 __global__ __launch_bounds__(1024) void k_sign_wide(MeshDev m, Calib cal, const float *__restrict__ pts, int64_t N, float sdf_clip, NearRef near,
                                                     uint8_t *__restrict__ code8, int32_t *__restrict__ block_counts,
                                                     unsigned long long *__restrict__ grp_mask, float far_box2, const int *__restrict__ n_dev,
-                                                    int *__restrict__ range_flag)
+                                                    int *__restrict__ range_flag, BatchDev bd)
 {
     __shared__ unsigned long long gm[4];
     if (range_flag && blockIdx.x == 0 && threadIdx.x == 0) *range_flag = 0;
-    if (n_dev) { N = *n_dev; if ((int64_t)blockIdx.x * 256 >= N) return; }
+    if (!BATCH && n_dev) { N = *n_dev; if ((int64_t)blockIdx.x * 256 >= N) return; }
     if (threadIdx.x < 4) gm[threadIdx.x] = 0ull;
     __syncthreads();
     const int s = threadIdx.x & 3, pt = threadIdx.x >> 2;        // point of the block, lane of the point
     const int64_t i = (int64_t)blockIdx.x * 256 + pt;
     const bool live = i < N;
+    if (BATCH) {                                                 // the point's subject: its mesh and calibration replace the call's
+        const int64_t b = (live ? i : N - 1) / bd.n;
+        m = bd.meshes[b]; cal = batch_calib(bd, b);
+    }
     uint32_t code = 0;
     const MeshDyn &d = *m.dyn;
     f3 p = mk3(0.f, 0.f, 0.f);
@@ -321,7 +328,7 @@ __device__ __forceinline__ int64_t uniform64(int64_t v)
 // (Requesting the texels of BOTH feature halves up front - their addresses depend on the position only - instead of after
 //  the dependent chain slot -> triangle attributes -> visibility flag was measured: 14.69 vs 14.36 ms; the phase is bound by
 //  the number of loads, not by the length of the chain.)
-__device__ __forceinline__ void icon_row_on(const FusedGeom &G, const MeshDev &m, const FeatDev &f, f3 p, int64_t i, float *xrow, int64_t K, int64_t rank0)
+__device__ __forceinline__ void icon_row(const FusedGeom &G, const MeshDev &m, const FeatDev &f, f3 p, int64_t i, float *xrow, int64_t K, int64_t rank0)
 {
     const uint32_t code = G.code8[i];
     Nearest nr;
@@ -362,63 +369,38 @@ __device__ __forceinline__ void icon_row_on(const FusedGeom &G, const MeshDev &m
     xrow[kCodeSlot] = __int_as_float((int)(code & kCodeInCube));
 }
 
-__device__ __forceinline__ void icon_row(const FusedGeom &G, f3 p, int64_t i, float *xrow, int64_t K, int64_t rank0)
-{
-    icon_row_on(G, G.m, G.f, p, i, xrow, K, rank0);
-}
-
 // The MLP input row of work item q of the launch (16 floats: reference channel order, zeros, slot kCodeSlot = the in_cube
 // bit): what the feature phase of k_fused_f16x3 writes into LDS - and what k_rescue_fused rebuilds for a point to redo.
-template <int PRIOR, bool LATTICE>
-__device__ __forceinline__ void build_row(const FusedGeom &G, int64_t q, float *xrow, int64_t K, int64_t rank0)
+// Src::Batch: work item q is point q of the B*n points of a batched call, subject q / n - its calibration, planes, volume and
+// mesh come from bd (batch_device.h); the other sources never read bd.
+template <int PRIOR, Src SRC>
+__device__ __forceinline__ void build_row(const FusedGeom &G, const BatchDev &bd, int64_t q, float *xrow, int64_t K, int64_t rank0)
 {
     // work item -> point: its world position p and its index i in the linear order of the call
     f3 p;
     int64_t i;
-    if (LATTICE) {
+    const int64_t b = SRC == Src::Batch ? q / bd.n : 0;
+    if (SRC == Src::Lattice) {
         int ix, iy, iz;
         i = lattice_item(G, q, ix, iy, iz);
         p = lattice_world(G.res, ix, iy, iz);
     } else {
         i = q;
-        p = project(resolve_calib(G.cal), mk3(G.pts[3 * i], G.pts[3 * i + 1], G.pts[3 * i + 2]));
+        p = project(SRC == Src::Batch ? batch_calib(bd, b) : resolve_calib(G.cal), mk3(G.pts[3 * i], G.pts[3 * i + 1], G.pts[3 * i + 2]));
     }
+    const FeatDev f = SRC == Src::Batch ? batch_feat(G.f, bd, b) : G.f;
     if (PRIOR == ICON_PRIOR_ICON) {
-        icon_row(G, p, i, xrow, K, rank0);
-    } else {
-        gather_planes_dyn(G.f, 0, p.x, p.y, xrow);
-        const int hh = G.f.csel;
-        if (PRIOR == ICON_PRIOR_PAMIR) {
-            float v[8];
-            if (G.f.vpad == 8) gather_volume<2>(G.f, p.x, p.y, p.z, v); else gather_volume<1>(G.f, p.x, p.y, p.z, v);
-#pragma unroll
-            for (int k = 0; k < 8; ++k) if (k < G.f.Cv) xrow[hh + k] = v[k];
-        } else {
-            xrow[hh] = p.z;
-        }
-        xrow[kCodeSlot] = __int_as_float((int)in_cube_bit(p));
-    }
-}
-
-// build_row for work item q of a batched point-mode call: subject q / n's calibration, planes, mesh and volume
-template <int PRIOR>
-__device__ __forceinline__ void build_row_batch(const FusedGeom &G, const BatchDev &bd, int64_t q, float *xrow, int64_t K, int64_t rank0)
-{
-    const int64_t b = q / bd.n;
-    const f3 p = project(batch_calib(bd, b), mk3(G.pts[3 * q], G.pts[3 * q + 1], G.pts[3 * q + 2]));
-    const FeatDev f = batch_feat(G.f, bd, b);
-    if (PRIOR == ICON_PRIOR_ICON) {
-        const MeshDev m = bd.meshes[b];
-        icon_row_on(G, m, f, p, q, xrow, K, rank0);
+        icon_row(G, SRC == Src::Batch ? bd.meshes[b] : G.m, f, p, i, xrow, K, rank0);
     } else {
         gather_planes_dyn(f, 0, p.x, p.y, xrow);
-        if (PRIOR == ICON_PRIOR_PAMIR) {                  // index(vol_feat, xyz) of subject b's volume, as build_row
+        const int hh = f.csel;
+        if (PRIOR == ICON_PRIOR_PAMIR) {
             float v[8];
             if (f.vpad == 8) gather_volume<2>(f, p.x, p.y, p.z, v); else gather_volume<1>(f, p.x, p.y, p.z, v);
 #pragma unroll
-            for (int k = 0; k < 8; ++k) if (k < f.Cv) xrow[f.csel + k] = v[k];
+            for (int k = 0; k < 8; ++k) if (k < f.Cv) xrow[hh + k] = v[k];
         } else {
-            xrow[f.csel] = p.z;
+            xrow[hh] = p.z;
         }
         xrow[kCodeSlot] = __int_as_float((int)in_cube_bit(p));
     }
@@ -440,8 +422,8 @@ __device__ __forceinline__ void sign_list_extent(const FusedGeom &G, int64_t &K,
 // MLP, waves 4-7 only issue their share of the weight DMA and keep the barriers - twice the CUs at work, half the chain per
 // tile.  Decided in the kernel (the point count of a schedule level lives on the device).  SMALL = false compiles the
 // 257^3 kernel as it was.
-template <int PRIOR, bool LATTICE, bool SMALL = false>
-__global__ __launch_bounds__(kF16Block, 2) void k_fused_f16x3(FusedGeom G, float *__restrict__ out, MlpF16Dev w)
+template <int PRIOR, Src SRC, bool SMALL = false>
+__global__ __launch_bounds__(kF16Block, 2) void k_fused_f16x3(FusedGeom G, float *__restrict__ out, MlpF16Dev w, BatchDev bd)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane0 = threadIdx.x & 63, wave0 = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -462,7 +444,7 @@ __global__ __launch_bounds__(kF16Block, 2) void k_fused_f16x3(FusedGeom G, float
     // 250-register vector budget of the MFMA chain
     K = uniform64(K); rank0 = uniform64(rank0);
 
-    if (G.n_dev) { G.N = *G.n_dev; if (G.N <= 0) return; }
+    if (SRC != Src::Batch && G.n_dev) { G.N = *G.n_dev; if (G.N <= 0) return; }
     // every workgroup walks a CONTIGUOUS run of tiles: consecutive tiles share the cache lines at their common boundary
     // (a tile of interior rows does not end on a line) and the triangles / feature texels of neighbouring points, and a
     // workgroup stays on one XCD - interleaved over the grid, those lines were fetched into two L2s (105 vs 91 MB of HBM
@@ -509,7 +491,7 @@ __global__ __launch_bounds__(kF16Block, 2) void k_fused_f16x3(FusedGeom G, float
         const bool worker = t < tp;                             // wave-uniform
         int64_t q = (int64_t)tile * tp + (worker ? t : 0);
         if (q >= G.N) q = G.N - 1;                               // padding lanes of the last tile recompute its last item
-        if (worker) build_row<PRIOR, LATTICE>(G, q, Xs + t * kXRow, K, rank0);
+        if (worker) build_row<PRIOR, SRC>(G, bd, q, Xs + t * kXRow, K, rank0);
         __syncthreads();          // tile visible; chunk 0 (and, the first time, W0 + side arrays) landed
 
         nb = (!SMALL && draw) ? __builtin_amdgcn_readfirstlane(pool[kPoolNext]) : -1;
@@ -587,183 +569,7 @@ __global__ __launch_bounds__(kF16Block, 2) void k_fused_f16x3(FusedGeom G, float
         const int64_t oq = (int64_t)tile * tp + pt;
         if (h == 0 && oq < G.N) {
             int ix, iy, iz;
-            out[LATTICE ? lattice_item(G, oq, ix, iy, iz) : (G.out_map ? (int64_t)G.out_map[oq] : oq)] = masked_result(y, maskf != 0.0f, w.flag);
-        }
-        // the next tile: the one behind this, or the first of the group drawn during this one
-        if (!SMALL && nb >= 0) {
-            tile = nb & ((1 << kPoolLenShift) - 1);
-            tile_end = tile + (nb >> kPoolLenShift);
-        } else ++tile;
-    }
-    if (!SMALL && stealing && threadIdx.x == 0) {
-        // the last workgroup to finish leaves the pair clean for the next launch (every draw of this launch precedes its
-        // workgroup's arrival here in program order; agent-scope atomics on both words)
-        __threadfence();
-        if (atomicAdd(G.steal + 8, 1u) == gridDim.x - 1)
-            for (int k = 0; k < 9; ++k) atomicExch(G.steal + k, 0u);
-    }
-    if (G.clock && threadIdx.x == 0 && blockIdx.x < kMaxProfGrid) {
-        if (blockIdx.x == 0) wg_stamp(G.clock + 2);
-        unsigned long long *rec = G.clock + 4 + kWgRec * blockIdx.x;
-        wg_stamp(rec + 2);
-        unsigned xcc, hw;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-        rec[4] = ((unsigned long long)xcc << 32) | hw;
-        rec[5] = SMALL ? 0ull : (unsigned long long)pool[kPoolDone];
-    }
-}
-
-// The batched point-mode variant (icon_query_points_batch): work item q is point q of the B*n points, subject q / n, whose row
-// build_row_batch assembles from that subject's calibration, planes and mesh.  The body is k_fused_f16x3's point mode line for
-// line; it is a kernel of its own so that the existing instantiations keep their code (routing them through a shared body
-// function was measured to move the SMALL icon variants from 0 to ~220 bytes of scratch per lane).
-template <int PRIOR, bool SMALL>
-__global__ __launch_bounds__(kF16Block, 2) void k_fused_f16x3_batch(FusedGeom G, float *__restrict__ out, MlpF16Dev w, BatchDev bd)
-{
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int lane0 = threadIdx.x & 63, wave0 = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    float *Xs = reinterpret_cast<float *>(smem + kXsOff);
-    if (G.clock && threadIdx.x == 0) {
-        if (blockIdx.x == 0) wg_stamp(G.clock);
-        if (blockIdx.x < kMaxProfGrid) wg_stamp(G.clock + 4 + kWgRec * blockIdx.x);
-    }
-
-    // ---- once per workgroup: resident layer-0 operands, side arrays, sign-list geometry ------------------
-    issue_units(w.image, smem + kW0Off, kW0Bytes / 1024, wave0, lane0);
-    float *side = reinterpret_cast<float *>(smem + kSideOff);
-    for (int i = threadIdx.x; i < kSideFloats; i += kF16Block) side[i] = w.side[i];
-    const float *sb0 = side, *sb1 = side + 512, *sb2 = side + 768, *sw3 = side + 896;
-    int64_t K = 0, rank0 = 0;
-    if (PRIOR == ICON_PRIOR_ICON) sign_list_extent(G, K, rank0);
-    // wave-uniform 64-bit values that live across the whole MLP body: keep them in SGPRs, not in the
-    // 250-register vector budget of the MFMA chain
-    K = uniform64(K); rank0 = uniform64(rank0);
-
-    // every workgroup walks a CONTIGUOUS run of tiles: consecutive tiles share the cache lines at their common boundary
-    // (a tile of interior rows does not end on a line) and the triangles / feature texels of neighbouring points, and a
-    // workgroup stays on one XCD - interleaved over the grid, those lines were fetched into two L2s (105 vs 91 MB of HBM
-    // reads per 257^3 launch when the tiles stopped being 1 KiB-aligned runs of the linear order)
-    const int tp = (SMALL && G.N <= (int64_t)(kTilePts / 2) * gridDim.x) ? kTilePts / 2 : kTilePts;       // points per tile (wave-uniform)
-    const int ntiles = (int)((G.N + tp - 1) / tp);                  // N < 2^31 (checked by the launcher)
-    // the workgroup's span of the tiles, and of it the static run it evaluates itself (all of it when the launch is static)
-    const bool stealing = !SMALL && G.steal != nullptr;
-    const int per = ntiles / (int)gridDim.x, rem = ntiles % (int)gridDim.x;
-    int tile = (int)blockIdx.x * per + min((int)blockIdx.x, rem);
-    int tile_end = tile + (stealing ? min(G.steal_static, per) : per + ((int)blockIdx.x < rem ? 1 : 0));
-    tile = __builtin_amdgcn_readfirstlane(tile);
-    tile_end = __builtin_amdgcn_readfirstlane(tile_end);
-    volatile int *pool = reinterpret_cast<volatile int *>(smem + kPoolOff);
-    if (!SMALL) {
-        if (threadIdx.x == 0) {
-            pool[kPoolPer] = per; pool[kPoolRem] = rem; pool[kPoolStatic] = G.steal_static; pool[kPoolGroup] = G.steal_grp;
-            pool[kPoolNGrp] = G.steal_ngrp; pool[kPoolGrid] = (int)gridDim.x; pool[kPoolDone] = 0; pool[kPoolMask] = 0; pool[kPoolNext] = -1;
-            if (stealing && tile >= tile_end) pool_draw(G.steal, pool);      // no static run at all: draw now
-        }
-        __syncthreads();
-        if (stealing && tile >= tile_end) {
-            const int word = __builtin_amdgcn_readfirstlane(pool[kPoolNext]);
-            __syncthreads();                                 // (every wave has read the word before a draw of the loop rewrites it)
-            if (word >= 0) { tile = word & ((1 << kPoolLenShift) - 1); tile_end = tile + (word >> kPoolLenShift); }
-        }
-    }
-    if (tile < tile_end) issue_chunk(w.image, smem, 0, wave0, lane0);
-
-    // `nb`: the group drawn while the LAST tile of the current run is in flight (first tile | tiles << 24; -1: none, or no draw) -
-    // a few returned atomics of wave 4, which has no work item in the feature phase; the barrier that publishes the tile publishes it
-    for (int nb = -1; tile < tile_end;) {
-        // Everything derived from the thread index is re-derived per tile from an opaque copy: hoisted out of
-        // the loop, those ~20 lane-dependent addresses would have to stay live across the 250-register MFMA
-        // body, i.e. be spilled to scratch (measured: 1.5 GB of scratch writes per 257^3 launch).
-        int tid = threadIdx.x;
-        asm volatile("" : "+v"(tid));
-        const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-        const int j = lane & 31, h = lane >> 5;
-        // ---- feature phase: waves 0-3, one work item per thread -> Xs[t][16] -----------------------------
-        const int t = tid;
-        const bool draw = !SMALL && stealing && tile + 1 == tile_end;       // wave-uniform: this is the run's last tile
-        if (!SMALL && draw && t == 256) pool_draw(G.steal, pool);           // (-1: every list is exhausted)
-        const bool worker = t < tp;                             // wave-uniform
-        int64_t q = (int64_t)tile * tp + (worker ? t : 0);
-        if (q >= G.N) q = G.N - 1;                               // padding lanes of the last tile recompute its last item
-        if (worker) build_row_batch<PRIOR>(G, bd, q, Xs + t * kXRow, K, rank0);
-        __syncthreads();          // tile visible; chunk 0 (and, the first time, W0 + side arrays) landed
-
-        nb = (!SMALL && draw) ? __builtin_amdgcn_readfirstlane(pool[kPoolNext]) : -1;
-        if (!SMALL && tid == 0) pool[kPoolDone] = pool[kPoolDone] + 1;
-        const bool more = tile + 1 < tile_end || nb >= 0;       // the first chunks of the next tile ride on the last ones
-        if (SMALL && wave >= (tp >> 5)) {
-            // a wave without points (128-point tiles): its share of the weight stream, the same barriers as the body below
-            for (int c = 0; c < 16; ++c) {
-                issue_chunk(w.image, smem + ((c + 1) & 1) * kBufBytes, c + 1, wave, lane);
-                ICON_CHUNK_BARRIER();
-            }
-            issue_chunk(w.image, smem + kBufBytes, 17, wave, lane);
-            ICON_CHUNK_BARRIER();
-            issue_chunk(w.image, smem, 18, wave, lane);
-            ICON_CHUNK_BARRIER();
-            issue_chunk(w.image, smem + kBufBytes, 19, wave, lane);
-            ICON_CHUNK_BARRIER();
-            if (more) issue_chunk(w.image, smem, 0, wave, lane);
-            ++tile;
-            continue;
-        }
-        // ---- MLP: one wave = 32 points, lane (j,h) holds input slots 8h..8h+7 of point j ------------------
-        const int pt = wave * 32 + j;
-        float xr[8];
-        {
-            const float4 *q = reinterpret_cast<const float4 *>(Xs + pt * kXRow + 8 * h);
-            const float4 a = q[0], b4 = q[1];
-            xr[0] = a.x; xr[1] = a.y; xr[2] = a.z; xr[3] = a.w; xr[4] = b4.x; xr[5] = b4.y; xr[6] = b4.z; xr[7] = b4.w;
-        }
-        const float maskf = (__float_as_int(Xs[pt * kXRow + kCodeSlot]) & (int)kCodeInCube) ? 1.0f : 0.0f;
-#pragma unroll
-        for (int s = 0; s < 8; ++s) xr[s] = (s + 8 * h < w.c0) ? xr[s] : 0.0f;
-        half8 xhi, xlo;
-        split8(xr, xhi, xlo);
-
-        f32x16 acc1[8];
-#pragma unroll
-        for (int m = 0; m < 8; ++m) acc1[m] = ld16(sb1 + (m * 2 + h) * 16);
-        half8 bh[2], bl[2];
-        activate_split(l0_tile(smem + kW0Off, sb0, 0, xhi, xlo, h, lane), LeakyK{w.inv0, w.p0, w.q0}, bh, bl);
-        f32x16 acc2[4];
-        for (int c = 0; c < 16; ++c) {
-            l01_chunk(smem + (c & 1) * kBufBytes, smem + ((c + 1) & 1) * kBufBytes, smem + kW0Off, sb0, w.image, c, acc1, xhi, xlo,
-                      LeakyK{w.inv0, w.p0, w.q0}, h, lane, wave, bh, bl);
-            ICON_CHUNK_BARRIER();
-        }
-#pragma unroll
-        for (int m2 = 0; m2 < 4; ++m2) acc2[m2] = ld16(sb2 + (m2 * 2 + h) * 16);
-        activate_split(acc1[0], LeakyK{w.inv1, w.p1, w.q1}, bh, bl);
-        l2_chunk<0>(smem, smem + kBufBytes, w.image, acc1, acc2, xhi, xlo, LeakyK{w.inv1, w.p1, w.q1}, lane, wave, bh, bl);
-        ICON_CHUNK_BARRIER();
-        l2_chunk<1>(smem + kBufBytes, smem, w.image, acc1, acc2, xhi, xlo, LeakyK{w.inv1, w.p1, w.q1}, lane, wave, bh, bl);
-        ICON_CHUNK_BARRIER();
-        l2_chunk<2>(smem, smem + kBufBytes, w.image, acc1, acc2, xhi, xlo, LeakyK{w.inv1, w.p1, w.q1}, lane, wave, bh, bl);
-        ICON_CHUNK_BARRIER();
-        l2_chunk<3>(smem + kBufBytes, smem, w.image, acc1, acc2, xhi, xlo, LeakyK{w.inv1, w.p1, w.q1}, lane, wave, bh, bl, more ? 0 : -1);
-
-        // ---- layer 3 on the VALU (f32) ---------------------------------------------------------------------
-        const float *w3 = sw3 + h * 72;
-        float part = 0.0f;
-#pragma unroll
-        for (int m2 = 0; m2 < 4; ++m2) {
-            const f32x16 wv = ld16(w3 + m2 * 16);
-#pragma unroll
-            for (int tt = 0; tt < 16; ++tt) {
-                part = fmaf(wv[tt], leaky_scaled(acc2[m2][tt], LeakyK{w.inv2, w.p2, w.q2}), part);
-            }
-        }
-#pragma unroll
-        for (int s = 0; s < 8; ++s) part = fmaf(w3[64 + s], xr[s], part);
-        const float other = __shfl_xor(part, 32);
-        const float y = apply_last_op((part + other) + w.b3, w.last_op);
-        // where this point's occupancy goes is re-derived from the work item (a handful of integer instructions):
-        // nothing lane-dependent lives across the MFMA body
-        const int64_t oq = (int64_t)tile * tp + pt;
-        if (h == 0 && oq < G.N) {
-            out[oq] = masked_result(y, maskf != 0.0f, w.flag);
+            out[SRC == Src::Lattice ? lattice_item(G, oq, ix, iy, iz) : ((SRC == Src::Points && G.out_map) ? (int64_t)G.out_map[oq] : oq)] = masked_result(y, maskf != 0.0f, w.flag);
         }
         // the next tile: the one behind this, or the first of the group drawn during this one
         if (!SMALL && nb >= 0) {
@@ -792,19 +598,19 @@ __global__ __launch_bounds__(kF16Block, 2) void k_fused_f16x3_batch(FusedGeom G,
 
 // The range safety net (mlp_plain_device.h): when the fused kernel raised the flag, find the work items whose result is not
 // finite, rebuild their input rows exactly as the feature phase did and redo them in plain f32.  One wave per 64 work items.
-template <int PRIOR, bool LATTICE>
-__global__ __launch_bounds__(64) void k_rescue_fused(FusedGeom G, float *__restrict__ out, MlpPlain P, const int *flag, int always)
+template <int PRIOR, Src SRC>
+__global__ __launch_bounds__(64) void k_rescue_fused(FusedGeom G, float *__restrict__ out, MlpPlain P, const int *flag, int always, BatchDev bd)
 {
     __shared__ float s[kPlainLds];
     if (!always && *flag == 0) return;                        // the usual case: one word read per workgroup of a small grid
-    if (G.n_dev) G.N = *G.n_dev;
+    if (SRC != Src::Batch && G.n_dev) G.N = *G.n_dev;
     const int lane = threadIdx.x;
     int64_t K = 0, rank0 = 0;
     if (PRIOR == ICON_PRIOR_ICON) sign_list_extent(G, K, rank0);
     for (int64_t base = (int64_t)blockIdx.x * 64; base < G.N; base += (int64_t)gridDim.x * 64) {
         const int64_t q = base + lane;
         int ix, iy, iz;
-        const int64_t o = q < G.N ? (LATTICE ? lattice_item(G, q, ix, iy, iz) : (G.out_map ? (int64_t)G.out_map[q] : q)) : 0;
+        const int64_t o = q < G.N ? (SRC == Src::Lattice ? lattice_item(G, q, ix, iy, iz) : ((SRC == Src::Points && G.out_map) ? (int64_t)G.out_map[q] : q)) : 0;
         const float v = q < G.N ? out[o] : 0.0f;
         unsigned long long todo = __ballot(not_finite(v));
         while (todo) {
@@ -814,39 +620,7 @@ __global__ __launch_bounds__(64) void k_rescue_fused(FusedGeom G, float *__restr
                 float row[kXRow];
 #pragma unroll
                 for (int k = 0; k < kXRow; ++k) row[k] = 0.0f;
-                build_row<PRIOR, LATTICE>(G, q, row, K, rank0);
-#pragma unroll
-                for (int k = 0; k < kXRow; ++k) s[k] = k < P.c0 ? row[k] : 0.0f;
-            }
-            const float y = mlp_plain_wave(P, s, lane);
-            if (lane == b) out[o] = y;       // only in-cube results are ever non-finite (masked_result): no mask to apply
-            __builtin_amdgcn_wave_barrier();
-        }
-    }
-}
-
-// k_rescue_fused for the batched point-mode variant
-template <int PRIOR>
-__global__ __launch_bounds__(64) void k_rescue_fused_batch(FusedGeom G, float *__restrict__ out, MlpPlain P, const int *flag, int always, BatchDev bd)
-{
-    __shared__ float s[kPlainLds];
-    if (!always && *flag == 0) return;                        // the usual case: one word read per workgroup of a small grid
-    const int lane = threadIdx.x;
-    int64_t K = 0, rank0 = 0;
-    if (PRIOR == ICON_PRIOR_ICON) sign_list_extent(G, K, rank0);
-    for (int64_t base = (int64_t)blockIdx.x * 64; base < G.N; base += (int64_t)gridDim.x * 64) {
-        const int64_t q = base + lane;
-        const int64_t o = q < G.N ? q : 0;
-        const float v = q < G.N ? out[o] : 0.0f;
-        unsigned long long todo = __ballot(not_finite(v));
-        while (todo) {
-            const int b = __ffsll((long long)todo) - 1;
-            todo &= todo - 1;
-            if (lane == b) {
-                float row[kXRow];
-#pragma unroll
-                for (int k = 0; k < kXRow; ++k) row[k] = 0.0f;
-                build_row_batch<PRIOR>(G, bd, q, row, K, rank0);
+                build_row<PRIOR, SRC>(G, bd, q, row, K, rank0);
 #pragma unroll
                 for (int k = 0; k < kXRow; ++k) s[k] = k < P.c0 ? row[k] : 0.0f;
             }
@@ -870,7 +644,7 @@ __global__ void k_seg_offsets(const int8_t *__restrict__ gathered, int64_t strid
 // host side
 // ---------------------------------------------------------------------------------------------
 int launch_sign(const icon_mesh *mesh, const Calib &cal, int res, int z0, const float *d_points, int64_t N, float sdf_clip,
-                const icon_work *work, bool lattice, hipStream_t st)
+                const icon_work *work, bool lattice, hipStream_t st, const BatchDev *bd)
 {
     const int64_t nb = (N + 255) / 256;
     ICON_ARG(nb > 0 && nb < (1ll << 31), "too many workgroups for one launch");
@@ -878,9 +652,12 @@ int launch_sign(const icon_mesh *mesh, const Calib &cal, int res, int z0, const 
     if (lattice) hipLaunchKernelGGL(k_sign<true>, dim3((unsigned)nb), dim3(256), 0, st, mesh->dev, cal, res, z0, d_points, N, sdf_clip,
                                     work->d_row_count, work->d_row_slots, work_near(work, mesh), work->d_code8, work->d_block_counts,
                                     (unsigned long long *)work->d_grp_mask, far_box2, (const int *)nullptr, work->d_flag);
+    else if (bd)                                  // a batched call: every point in its subject's mesh (`mesh`: subject 0, for the slot width)
+        hipLaunchKernelGGL(k_sign_wide<true>, dim3((unsigned)nb), dim3(1024), 0, st, MeshDev{}, Calib{}, d_points, N, sdf_clip, work_near(work, mesh), work->d_code8,
+                           work->d_block_counts, (unsigned long long *)work->d_grp_mask, far_box2, (const int *)nullptr, work->d_flag, *bd);
     else if (work->q_n_dev || N <= 262144)        // few points (a level of the schedule: the size on the device is a few percent of N)
-        hipLaunchKernelGGL(k_sign_wide, dim3((unsigned)nb), dim3(1024), 0, st, mesh->dev, cal, d_points, N, sdf_clip, work_near(work, mesh), work->d_code8,
-                           work->d_block_counts, (unsigned long long *)work->d_grp_mask, far_box2, work->q_n_dev, work->d_flag);
+        hipLaunchKernelGGL(k_sign_wide<false>, dim3((unsigned)nb), dim3(1024), 0, st, mesh->dev, cal, d_points, N, sdf_clip, work_near(work, mesh), work->d_code8,
+                           work->d_block_counts, (unsigned long long *)work->d_grp_mask, far_box2, work->q_n_dev, work->d_flag, BatchDev{});
     else hipLaunchKernelGGL(k_sign<false>, dim3((unsigned)nb), dim3(256), 0, st, mesh->dev, cal, res, z0, d_points, N, sdf_clip,
                             (const int32_t *)nullptr, (const int32_t *)nullptr, work_near(work, mesh), work->d_code8, work->d_block_counts,
                             (unsigned long long *)work->d_grp_mask, far_box2, work->q_n_dev, work->d_flag);
@@ -1005,39 +782,30 @@ int launch_fused_f16x3(const icon_mesh *mesh, const icon_feat *feat, const icon_
         }
     }
     if (G.clock) work->clock_grid = (int)std::min<unsigned>(grid, (unsigned)kMaxProfGrid);
-#define ICON_FUSED(P, L_, ID, ...)                                                                                         \
+    const BatchDev batch = bd ? *bd : BatchDev{};                // (read by the Src::Batch instantiations only)
+#define ICON_FUSED(P, S, ID, ...)                                                                                          \
     do {                                                                                                                   \
-        if ((rc = once_per_device(ID, [] { return hipFuncSetAttribute(reinterpret_cast<const void *>(k_fused_f16x3<P, L_, ##__VA_ARGS__>),   \
+        if ((rc = once_per_device(ID, [] { return hipFuncSetAttribute(reinterpret_cast<const void *>(k_fused_f16x3<P, Src::S, ##__VA_ARGS__>), \
                                                                     hipFuncAttributeMaxDynamicSharedMemorySize, kFusedLds); }))) return rc; \
-        hipLaunchKernelGGL((k_fused_f16x3<P, L_, ##__VA_ARGS__>), dim3(grid), dim3(kF16Block), kFusedLds, st, G, d_occ, w); \
+        hipLaunchKernelGGL((k_fused_f16x3<P, Src::S, ##__VA_ARGS__>), dim3(grid), dim3(kF16Block), kFusedLds, st, G, d_occ, w, batch); \
         debug_sync("k_fused_f16x3", st);                                                                                   \
         if (!defer) {                                                                                                      \
-            hipLaunchKernelGGL((k_rescue_fused<P, L_>), dim3((unsigned)n_resc), dim3(64), 0, st, G, d_occ, plain, w.flag, rescue_always()); \
+            hipLaunchKernelGGL((k_rescue_fused<P, Src::S>), dim3((unsigned)n_resc), dim3(64), 0, st, G, d_occ, plain, w.flag, rescue_always(), batch); \
             debug_sync("k_rescue_fused", st);                                                                              \
         }                                                                                                                  \
     } while (0)
-#define ICON_FUSED_BATCH(P, ID, ...)                                                                                       \
-    do {                                                                                                                   \
-        if ((rc = once_per_device(ID, [] { return hipFuncSetAttribute(reinterpret_cast<const void *>(k_fused_f16x3_batch<P, ##__VA_ARGS__>), \
-                                                                    hipFuncAttributeMaxDynamicSharedMemorySize, kFusedLds); }))) return rc; \
-        hipLaunchKernelGGL((k_fused_f16x3_batch<P, ##__VA_ARGS__>), dim3(grid), dim3(kF16Block), kFusedLds, st, G, d_occ, w, *bd); \
-        debug_sync("k_fused_f16x3_batch", st);                                                                             \
-        hipLaunchKernelGGL((k_rescue_fused_batch<P>), dim3((unsigned)n_resc), dim3(64), 0, st, G, d_occ, plain, w.flag, rescue_always(), *bd); \
-        debug_sync("k_rescue_fused_batch", st);                                                                            \
-    } while (0)
     if (bd) {                                    // batched point mode (no lattice, no device-side size, no deferred flag)
         if (lattice || defer || work->q_n_dev) return fail(ICON_ERR_UNSUPPORTED, "fused: batched call outside point mode");
-        if (small) ICON_FUSED_BATCH(ICON_PRIOR_ICON, 11, true);
-        else if (prior == ICON_PRIOR_ICON) ICON_FUSED_BATCH(ICON_PRIOR_ICON, 12, false);
-        else if (prior == ICON_PRIOR_PAMIR) ICON_FUSED_BATCH(ICON_PRIOR_PAMIR, 14, false);
-        else ICON_FUSED_BATCH(ICON_PRIOR_PIFU, 13, false);
+        if (small) ICON_FUSED(ICON_PRIOR_ICON, Batch, 11, true);
+        else if (prior == ICON_PRIOR_ICON) ICON_FUSED(ICON_PRIOR_ICON, Batch, 12);
+        else if (prior == ICON_PRIOR_PAMIR) ICON_FUSED(ICON_PRIOR_PAMIR, Batch, 14);
+        else ICON_FUSED(ICON_PRIOR_PIFU, Batch, 13);
     }
-    else if (small) { if (lattice) ICON_FUSED(ICON_PRIOR_ICON, true, 9, true); else ICON_FUSED(ICON_PRIOR_ICON, false, 10, true); }
-    else if (prior == ICON_PRIOR_ICON) { if (lattice) ICON_FUSED(ICON_PRIOR_ICON, true, 0); else ICON_FUSED(ICON_PRIOR_ICON, false, 1); }
-    else if (prior == ICON_PRIOR_PAMIR) { if (lattice) ICON_FUSED(ICON_PRIOR_PAMIR, true, 2); else ICON_FUSED(ICON_PRIOR_PAMIR, false, 3); }
-    else { if (lattice) ICON_FUSED(ICON_PRIOR_PIFU, true, 4); else ICON_FUSED(ICON_PRIOR_PIFU, false, 5); }
+    else if (small) { if (lattice) ICON_FUSED(ICON_PRIOR_ICON, Lattice, 9, true); else ICON_FUSED(ICON_PRIOR_ICON, Points, 10, true); }
+    else if (prior == ICON_PRIOR_ICON) { if (lattice) ICON_FUSED(ICON_PRIOR_ICON, Lattice, 0); else ICON_FUSED(ICON_PRIOR_ICON, Points, 1); }
+    else if (prior == ICON_PRIOR_PAMIR) { if (lattice) ICON_FUSED(ICON_PRIOR_PAMIR, Lattice, 2); else ICON_FUSED(ICON_PRIOR_PAMIR, Points, 3); }
+    else { if (lattice) ICON_FUSED(ICON_PRIOR_PIFU, Lattice, 4); else ICON_FUSED(ICON_PRIOR_PIFU, Points, 5); }
 #undef ICON_FUSED
-#undef ICON_FUSED_BATCH
     ICON_HIP(hipGetLastError());
     return ICON_OK;
 }

@@ -12,11 +12,9 @@
 // -ffp-contract=off; the pragma below is a second line of defence.
 #pragma clang fp contract(off)
 
-#include "geom_device.h"
+#include "query_device.h"
 
 namespace icon {
-
-constexpr int kBlock = 256;
 
 // ---------------------------------------------------------------------------------------------
 // kernels
@@ -46,18 +44,6 @@ __global__ __launch_bounds__(kBlock) void k_sdf_query(MeshDev m, const float *__
     vis[i] = o.vis;
     if (face) face[i] = nr.face;
     if (inside_out) inside_out[i] = ins ? 1 : 0;
-}
-
-// point mode, one wavefront per point (see nearest_coop)
-__global__ __launch_bounds__(kCoopWaves * 64) void k_nearest_coop(MeshDev m, Calib cal, const float *__restrict__ pts, int64_t N,
-                                                                 NearRef near, int cap, float sdf_clip)
-{
-    extern __shared__ __attribute__((aligned(16))) char coop_smem[];
-    const int64_t i = (int64_t)blockIdx.x * kCoopWaves + (threadIdx.x >> 6);
-    if (i >= N) return;
-    const f3 p = project(resolve_calib(cal), mk3(pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]));
-    const Nearest nr = nearest_coop(m, p, coop_lds(coop_smem, threadIdx.x >> 6, cap));
-    if ((threadIdx.x & 63) == 0) store_near(near, i, nr, sdf_clip);
 }
 
 __global__ __launch_bounds__(kCoopWaves * 64) void k_sdf_query_coop(MeshDev m, const float *__restrict__ pts, int64_t N,
@@ -166,102 +152,6 @@ __global__ __launch_bounds__(kBlock) void k_nearest_ties(MeshDev m, const float 
     face[i] = nr.face;
     face2[i] = has2 ? f2 : -1;
     ulps[i] = (uint8_t)(has2 ? min(b2 - b1, 255u) : 255u);
-}
-
-// Feature assembly: one 16-float row per point,
-//   icon : [img(csel) | sdf | cmap r g b | norm x y z | 0.. | code]
-//   pamir: [img(C) | vol(Cv) | 0.. | code]      pifu: [img(C) | z | 0.. | code]
-// Rows are indexed by the point's linear index (lattice: (z*R + y)*R + x relative to plane z0).
-template <int PRIOR, bool LATTICE, bool BRUTE>
-__global__ __launch_bounds__(kBlock) void k_features(MeshDev m, FeatDev f, Calib cal, LatticeMap L,
-                                                     const float *__restrict__ pts, int64_t N,
-                                                     float sdf_clip, int cmap_local,
-                                                     const int32_t *__restrict__ row_count, const int32_t *__restrict__ row_slots,
-                                                     NearRef near,
-                                                     float *__restrict__ X, uint8_t *__restrict__ code8, int skip_shell)
-{
-    __shared__ int lds[(PRIOR == ICON_PRIOR_ICON && BRUTE) ? kBruteTile * 24 : 1];
-    int64_t i; bool live; f3 p;
-    if (LATTICE) {
-        // L tiles the WHOLE slab here (every point gets a row); skip_shell: the geometry pre-pass left the shell out
-        int ix, iy, iz, cx, cy, cz;
-        live = lattice_point(L, ix, iy, iz);
-        lattice_clamp(L, ix, iy, iz, cx, cy, cz);
-        p = lattice_world(L.res, cx, cy, cz + L.z0);
-        i = ((int64_t)cz * L.res + cy) * L.res + cx;
-        if (skip_shell && !in_cube_bit(p)) {
-            // a shell point: multiplied by 0 whatever its row holds (in_cube, HGPIFuNet.py:363) - a zero row and the code
-            // byte k_sign wrote (icon) / in_cube = 0, without touching the search results that do not exist for it
-            if (live) {
-                float z[kXRow];
-#pragma unroll
-                for (int k = 0; k < kXRow; ++k) z[k] = 0.0f;
-                uint32_t c = 0;
-                if (PRIOR == ICON_PRIOR_ICON) c = code8[i];
-                z[kCodeSlot] = __int_as_float((int)c);
-                store_row(X, i, z);
-                if (PRIOR != ICON_PRIOR_ICON) code8[i] = (uint8_t)c;
-            }
-            return;
-        }
-    } else {
-        i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-        live = i < N;
-        if (!live) i = N - 1;
-        p = project(resolve_calib(cal), mk3(pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]));
-    }
-    float row[kXRow];
-#pragma unroll
-    for (int k = 0; k < kXRow; ++k) row[k] = 0.0f;
-    uint32_t code = in_cube_bit(p);
-    if (PRIOR == ICON_PRIOR_ICON) {
-        Nearest nr;
-        bool ins;
-        float s;
-        f3 cmv;
-        SdfOut o;
-        if (BRUTE) {
-            nr = nearest_brute<kBlock>(m, p, reinterpret_cast<float *>(lds)); ins = inside_brute(m, p);
-            o = sdf_attrs(m, p, nr, ins);
-            code = sign_code(p, nr.d2, ins, sdf_clip);
-        } else {
-            // the geometry pre-pass ran on the same stream just before: slot of the nearest triangle, the code byte
-            // (outlier / sign / inside / in_cube) and, for points inside the clip band only, d^2
-            code = code8[i];
-            nr.slot = near_slot_of(near, i); nr.face = 0;
-            nr.d2 = (code & kCodeOutlier) ? 0.0f : near_d2(near, i);
-            ins = (code & kCodeInside) != 0;
-            o = sdf_attrs(m, p, nr, ins);
-        }
-        s = o.sdf;
-        cmv = o.cm;
-        if (code & kCodeOutlier) {            // HGPIFuNet.py:298-305
-            s = (float)((int)((code >> kCodeSignShift) & 3u) - 1);
-            if (cmap_local) cmv = mk3(s, s, s);   // reference mode: patched later from the sign list
-        }
-        float g[16];
-        gather_planes_dyn(f, (f.n_select == 2 && o.vis == 0.0f) ? 1 : 0, p.x, p.y, g);   // feat_select: vis==1 -> front half; no 'vis': all channels
-        const int h = f.csel;
-        for (int k = 0; k < h; ++k) row[k] = g[k];
-        int hh = h;                                       // [img | sdf | cmap (if) | norm (if)], HGPIFuNet.py:301-311
-        row[hh++] = s;
-        if (f.smpl_mask & kSmplCmap) { row[hh] = cmv.x; row[hh + 1] = cmv.y; row[hh + 2] = cmv.z; hh += 3; }
-        if (f.smpl_mask & kSmplNorm) { row[hh] = o.nrm.x; row[hh + 1] = o.nrm.y; row[hh + 2] = o.nrm.z; }
-    } else {
-        float g[16];
-        gather_planes_dyn(f, 0, p.x, p.y, g);
-        const int h = f.csel;
-        for (int k = 0; k < h; ++k) row[k] = g[k];
-        if (PRIOR == ICON_PRIOR_PAMIR) {
-            float v[8];
-            if (f.vpad == 8) gather_volume<2>(f, p.x, p.y, p.z, v); else gather_volume<1>(f, p.x, p.y, p.z, v);
-            for (int k = 0; k < f.Cv; ++k) row[h + k] = v[k];
-        } else {
-            row[h] = p.z;
-        }
-    }
-    row[kCodeSlot] = __int_as_float((int)code);
-    if (live) { store_row(X, i, row); code8[i] = (uint8_t)code; }   // byte copy of the code word: the outlier passes stream 1 B/pt
 }
 
 // diagnostics: per-wavefront BVH work of the lattice traversal (DESIGN.md reports visited nodes / point)
@@ -583,15 +473,19 @@ __global__ __launch_bounds__(256) void k_pack_signs(const int8_t *__restrict__ s
     msg[8 + t] = (uint8_t)b;
 }
 
-// repack feature planes [C][H][W] -> [n_select][H][W][cpad] (channel-last, zero padded)
-__global__ void k_pack_planes(const float *__restrict__ src, int C, int H, int W, int n_select, int csel, int cpad, float *dst)
+// repack B feature stacks [B][C][H][W] -> B plane sets [n_select][H][W][cpad] (channel-last, zero padded), `stride` floats
+// apart; grid z = subject
+__global__ void k_pack_planes(const float *__restrict__ src, int C, int H, int W, int n_select, int csel, int cpad, int64_t stride,
+                              float *__restrict__ dst)
 {
     const int64_t n = (int64_t)n_select * H * W * cpad;
+    const float *s = src + (int64_t)blockIdx.z * C * H * W;
+    float *d = dst + (int64_t)blockIdx.z * stride;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         const int c = (int)(i % cpad);
         const int64_t pix = (i / cpad) % ((int64_t)H * W);
         const int sel = (int)(i / ((int64_t)cpad * H * W));
-        dst[i] = (c < csel) ? src[((int64_t)(sel * csel + c)) * H * W + pix] : 0.0f;
+        d[i] = (c < csel) ? s[((int64_t)(sel * csel + c)) * H * W + pix] : 0.0f;
     }
 }
 
@@ -637,6 +531,51 @@ extern "C" int icon_sdf_query(const icon_mesh_t *mesh, const float *d_points, in
     return ICON_OK;
 }
 
+// ---- feature handles: B plane sets (and, pamir prior, B volumes) at a fixed stride; icon_feat_create is B = 1 ----------------
+namespace {
+
+// allocates *dst and packs B stacks into it in one launch (B = 1: the grid of 1024 workgroups a single stack always had)
+int pack_planes(const float *d_src, int B, int C, int H, int W, int n_select, int cpad, hipStream_t st, const char *what, float **dst, int64_t *stride)
+{
+    *stride = (int64_t)n_select * H * W * cpad;
+    hipError_t e = hipMalloc((void **)dst, (size_t)*stride * B * sizeof(float));
+    if (e != hipSuccess) return fail(ICON_ERR_HIP, std::string("hipMalloc ") + what + ": " + hipGetErrorString(e));
+    hipLaunchKernelGGL(k_pack_planes, dim3((unsigned)std::max(1, 1024 / B), 1, (unsigned)B), dim3(256), 0, st, d_src, C, H, W, n_select,
+                       C / n_select, cpad, *stride, *dst);
+    e = hipGetLastError();
+    if (e != hipSuccess) { (void)hipFree(*dst); *dst = nullptr; return fail(ICON_ERR_HIP, std::string("pack ") + what + ": " + hipGetErrorString(e)); }
+    return ICON_OK;
+}
+
+// (the exported entry points have checked the arguments, each under its own name)
+int feat_create(const float *d_planes, int B, int C, int H, int W, int n_select, hipStream_t st, icon_feat_t **out)
+{
+    icon_feat *f = new icon_feat();
+    FeatDev &d = f->dev;
+    d.C = C; d.H = H; d.W = W; d.n_select = n_select; d.csel = C / n_select; d.cpad = (d.csel + 3) & ~3;
+    d.smpl_mask = kSmplCmap | kSmplNorm;
+    d.vol = nullptr; d.Cv = 0; d.Dv = d.Hv = d.Wv = 0; d.vpad = 0;
+    f->batch = B;
+    const int rc = pack_planes(d_planes, B, C, H, W, n_select, d.cpad, st, "planes", &f->d_planes, &f->plane_stride);
+    if (rc) { delete f; return rc; }
+    d.planes = f->d_planes;
+    *out = f;
+    return ICON_OK;
+}
+
+// a volume is a "plane" of H' = D*H rows: same channel-last repack, zero padded to vpad
+int feat_set_volume(icon_feat *f, const float *d_vol, int Cv, int Dv, int Hv, int Wv, hipStream_t st)
+{
+    const int vpad = (Cv + 3) & ~3;
+    const int rc = pack_planes(d_vol, f->batch, Cv, Dv * Hv, Wv, 1, vpad, st, "volume", &f->d_vol, &f->vol_stride);
+    if (rc) return rc;
+    FeatDev &d = f->dev;
+    d.vol = f->d_vol; d.Cv = Cv; d.Dv = Dv; d.Hv = Hv; d.Wv = Wv; d.vpad = vpad;
+    return ICON_OK;
+}
+
+}  // namespace
+
 extern "C" int icon_feat_create(const float *d_planes, int C, int H, int W, int n_select,
                                 const float *d_vol, int Cv, int Dv, int Hv, int Wv,
                                 void *stream, icon_feat_t **out)
@@ -646,36 +585,38 @@ extern "C" int icon_feat_create(const float *d_planes, int C, int H, int W, int 
     ICON_ARG(d_planes && C > 0 && H > 1 && W > 1, "icon_feat_create: bad planes");
     ICON_ARG(n_select == 1 || n_select == 2, "icon_feat_create: n_select must be 1 or 2");
     ICON_ARG(C % n_select == 0, "icon_feat_create: C not divisible by n_select");
-    const int csel = C / n_select;
-    const int cpad = (csel + 3) & ~3;
-    if (cpad > 16) return fail(ICON_ERR_UNSUPPORTED, "icon_feat_create: more than 16 channels per tap");
+    if (C / n_select > 16) return fail(ICON_ERR_UNSUPPORTED, "icon_feat_create: more than 16 channels per tap");
     if (d_vol) {
         ICON_ARG(Cv > 0 && Dv > 1 && Hv > 1 && Wv > 1, "icon_feat_create: bad volume");
         if (Cv > 8) return fail(ICON_ERR_UNSUPPORTED, "icon_feat_create: more than 8 volume channels");
     }
-    hipStream_t st = (hipStream_t)stream;
-    icon_feat *f = new icon_feat();
-    const size_t n = (size_t)n_select * H * W * cpad;
-    hipError_t e = hipMalloc((void **)&f->d_planes, n * sizeof(float));
-    if (e != hipSuccess) { delete f; return fail(ICON_ERR_HIP, std::string("hipMalloc planes: ") + hipGetErrorString(e)); }
-    hipLaunchKernelGGL(k_pack_planes, dim3(1024), dim3(256), 0, st, d_planes, C, H, W, n_select, csel, cpad, f->d_planes);
-    FeatDev &d = f->dev;
-    d.planes = f->d_planes; d.C = C; d.H = H; d.W = W; d.n_select = n_select; d.csel = csel; d.cpad = cpad;
-    d.smpl_mask = kSmplCmap | kSmplNorm;
-    d.vol = nullptr; d.Cv = 0; d.Dv = d.Hv = d.Wv = 0; d.vpad = 0;
-    if (d_vol) {
-        const int vpad = (Cv + 3) & ~3;
-        const size_t nv = (size_t)Dv * Hv * Wv * vpad;
-        e = hipMalloc((void **)&f->d_vol, nv * sizeof(float));
-        if (e != hipSuccess) { icon_feat_destroy(f); return fail(ICON_ERR_HIP, std::string("hipMalloc vol: ") + hipGetErrorString(e)); }
-        // a volume is a "plane" of H' = D*H rows: same channel-last repack
-        hipLaunchKernelGGL(k_pack_planes, dim3(1024), dim3(256), 0, st, d_vol, Cv, Dv * Hv, Wv, 1, Cv, vpad, f->d_vol);
-        d.vol = f->d_vol; d.Cv = Cv; d.Dv = Dv; d.Hv = Hv; d.Wv = Wv; d.vpad = vpad;
-    }
-    e = hipGetLastError();
-    if (e != hipSuccess) { icon_feat_destroy(f); return fail(ICON_ERR_HIP, std::string("pack planes: ") + hipGetErrorString(e)); }
-    *out = f;
-    return ICON_OK;
+    icon_feat *f = nullptr;
+    int rc = feat_create(d_planes, 1, C, H, W, n_select, (hipStream_t)stream, &f);
+    if (!rc && d_vol && (rc = feat_set_volume(f, d_vol, Cv, Dv, Hv, Wv, (hipStream_t)stream))) icon_feat_destroy(f);
+    if (!rc) *out = f;
+    return rc;
+}
+
+extern "C" int icon_feat_create_batch(const float *d_planes, int B, int C, int H, int W, int n_select, void *stream, icon_feat_t **out)
+{
+    ICON_ARG(out != nullptr, "icon_feat_create_batch: out is null");
+    *out = nullptr;
+    ICON_ARG(d_planes && B >= 1 && C > 0 && H > 1 && W > 1, "icon_feat_create_batch: bad planes");
+    ICON_ARG(n_select == 1 || n_select == 2, "icon_feat_create_batch: n_select must be 1 or 2");
+    ICON_ARG(C % n_select == 0, "icon_feat_create_batch: C not divisible by n_select");
+    ICON_ARG(B <= 65535, "icon_feat_create_batch: more than 65,535 subjects");
+    if (C / n_select > 16) return fail(ICON_ERR_UNSUPPORTED, "icon_feat_create_batch: more than 16 channels per tap");
+    return feat_create(d_planes, B, C, H, W, n_select, (hipStream_t)stream, out);
+}
+
+extern "C" int icon_feat_batch_set_volume(icon_feat_t *feat, const float *d_vol, int B, int Cv, int Dv, int Hv, int Wv, void *stream)
+{
+    ICON_ARG(feat != nullptr && d_vol != nullptr, "icon_feat_batch_set_volume: null argument");
+    ICON_ARG(B == feat->batch, "icon_feat_batch_set_volume: the volume holds another number of subjects than the feature handle");
+    ICON_ARG(feat->dev.vol == nullptr, "icon_feat_batch_set_volume: the handle already holds a volume");
+    ICON_ARG(Cv > 0 && Dv > 1 && Hv > 1 && Wv > 1, "icon_feat_batch_set_volume: bad volume");
+    if (Cv > 8) return fail(ICON_ERR_UNSUPPORTED, "icon_feat_batch_set_volume: more than 8 volume channels");
+    return feat_set_volume(feat, d_vol, Cv, Dv, Hv, Wv, (hipStream_t)stream);
 }
 
 extern "C" int icon_feat_set_smpl_feats(icon_feat_t *f, int has_cmap, int has_norm)
@@ -917,11 +858,8 @@ int work_check_err(icon_work *w)
     return fail(ICON_ERR_STATE, buf);
 }
 
-}  // namespace icon
 
-namespace {
-
-inline void mark(icon_work *w, int k, hipStream_t st)
+void mark(icon_work *w, int k, hipStream_t st)
 {
     if (w->prof) { (void)hipEventRecord(w->ev[k], st); if (k == 3) w->ev_valid = true; }
 }
@@ -970,6 +908,10 @@ int ensure_work(icon_work *w, int64_t n_points, bool need_x)
     if (!w->d_seg) ICON_HIP(hipMalloc((void **)&w->d_seg, (kMaxWorld + 1) * sizeof(int64_t)));
     return ICON_OK;
 }
+
+}  // namespace icon
+
+namespace {
 
 int check_prior(const icon_mesh_t *mesh, const icon_feat_t *feat, int prior, int *c0)
 {
@@ -1036,8 +978,8 @@ int launch_nearest(const icon_mesh_t *mesh, const Calib &cal, const LatticeMap &
     const bool alt = work->tie_rule != 0;        // diagnostics: the alternative tie rule lives in the packet kernel only
     if (!LATTICE && !alt && mode != 3 && (N < kPacketMinPoints || mode == 2)) {
         const int cap = coop_cap(mesh->depth_bound);
-        hipLaunchKernelGGL(k_nearest_coop, dim3((unsigned)((N + kCoopWaves - 1) / kCoopWaves)), dim3(kCoopWaves * 64),
-                           kCoopWaves * coop_wave_bytes(cap), st, mesh->dev, cal, d_points, N, near, cap, sdf_clip);
+        hipLaunchKernelGGL(k_nearest_coop<false>, dim3((unsigned)((N + kCoopWaves - 1) / kCoopWaves)), dim3(kCoopWaves * 64),
+                           kCoopWaves * coop_wave_bytes(cap), st, mesh->dev, cal, d_points, N, near, cap, sdf_clip, BatchDev{});
     } else if (nb > 0) {                         // nb == 0: a slab that is all shell (nothing to search)
         if (!LATTICE) {
             const int rc = morton_order(work, d_points, cal.m, cal.d, N, st, &perm);
@@ -1081,7 +1023,7 @@ int launch_features(const icon_mesh_t *mesh, const icon_feat_t *feat, int prior,
     const MeshDev md = mesh ? mesh->dev : MeshDev{};
     const int local = (cmap_mode == ICON_CMAP_LOCAL) ? 1 : 0;
     const bool brute = (search == ICON_SEARCH_BRUTE);
-#define ICON_LAUNCH(P, B) hipLaunchKernelGGL((k_features<P, LATTICE, B>), grid, block, 0, st, md, feat->dev, cal, Lf, d_points, N, sdf_clip, local, work->d_row_count, work->d_row_slots, work_near(work, mesh), work->d_x, work->d_code8, skip_shell)
+#define ICON_LAUNCH(P, B) hipLaunchKernelGGL((k_features<P, LATTICE ? Src::Lattice : Src::Points, B>), grid, block, 0, st, md, feat->dev, cal, Lf, d_points, N, sdf_clip, local, work->d_row_count, work->d_row_slots, work_near(work, mesh), work->d_x, work->d_code8, skip_shell, BatchDev{})
     if (prior == ICON_PRIOR_ICON) { if (brute) ICON_LAUNCH(ICON_PRIOR_ICON, true); else ICON_LAUNCH(ICON_PRIOR_ICON, false); }
     else if (prior == ICON_PRIOR_PAMIR) ICON_LAUNCH(ICON_PRIOR_PAMIR, false);
     else ICON_LAUNCH(ICON_PRIOR_PIFU, false);
@@ -1090,6 +1032,9 @@ int launch_features(const icon_mesh_t *mesh, const icon_feat_t *feat, int prior,
     return ICON_OK;
 }
 
+}  // namespace
+
+namespace icon {
 // count + scan + compact over the codes of points [0, N): fills w->d_block_offsets, w->d_total, and `signs`
 int outlier_list(icon_work *w, int64_t N, int8_t *signs, bool counted, hipStream_t st)
 {
@@ -1112,9 +1057,6 @@ int outlier_list(icon_work *w, int64_t N, int8_t *signs, bool counted, hipStream
     return ICON_OK;
 }
 
-}  // namespace
-
-namespace icon {
 // the call's outlier sign list when its size is known on the device only (k_sign left the block counts): w->d_signs, w->d_total
 int outlier_list_dev(icon_work *w, const int *n_dev, int64_t n_max, hipStream_t st)
 {
@@ -1133,14 +1075,11 @@ int outlier_list_dev(icon_work *w, const int *n_dev, int64_t n_max, hipStream_t 
     return ICON_OK;
 }
 int ensure_work_points(icon_work *w, int64_t n_points) { return ensure_work(w, n_points, false); }
-}  // namespace icon
-
-namespace {
 
 int patch_self(icon_work *w, int64_t N, int cmap_slot, hipStream_t st)
 {
     const int64_t nblk = (N + kScanBlock - 1) / kScanBlock;
-    hipLaunchKernelGGL(icon::k_outlier_patch_self, dim3((unsigned)nblk), dim3(kScanBlock), 0, st, w->d_x, w->d_code8, N, cmap_slot,
+    hipLaunchKernelGGL(k_outlier_patch_self, dim3((unsigned)nblk), dim3(kScanBlock), 0, st, w->d_x, w->d_code8, N, cmap_slot,
                        w->d_block_offsets, w->d_signs, w->d_total);
     ICON_HIP(hipGetLastError());
     return ICON_OK;
@@ -1149,12 +1088,16 @@ int patch_self(icon_work *w, int64_t N, int cmap_slot, hipStream_t st)
 // The f16x3 precision (the default) with the BVH search runs FUSED: no input rows in HBM (fused_f16x3.hip).
 // ICON_AMD_UNFUSED=1 forces the materialising path (tests compare the two bit for bit).
 int g_unfused = -1;      // -1: read ICON_AMD_UNFUSED once; 0 / 1: set by icon_debug_set_unfused
-int g_shell_skip = -1;   // -1: read ICON_AMD_SHELL_SKIP once (default on); 0 / 1: set by icon_debug_set_shell_skip
-inline bool want_fused(int precision, int search)
+bool want_fused(int precision, int search)
 {
     if (g_unfused < 0) g_unfused = (getenv("ICON_AMD_UNFUSED") && atoi(getenv("ICON_AMD_UNFUSED")) != 0) ? 1 : 0;
     return !g_unfused && precision == ICON_PRECISION_F16X3 && search != ICON_SEARCH_BRUTE;
 }
+}  // namespace icon
+
+namespace {
+
+int g_shell_skip = -1;   // -1: read ICON_AMD_SHELL_SKIP once (default on); 0 / 1: set by icon_debug_set_shell_skip
 
 // Phase 1 of every query: what can be done before the outlier sign list of the whole call is known.
 //   icon prior, BVH: nearest search + k_sign (+ the call's own sign list in reference cmap mode); no rows yet
@@ -1260,15 +1203,6 @@ FusedSigns self_signs(const icon_work *work)
 }
 
 }  // namespace
-
-namespace icon {
-// the point-mode pipeline's pieces, for the batched call (batch_query.hip)
-int ensure_work_rows(icon_work *w, int64_t n_points, bool need_x) { return ensure_work(w, n_points, need_x); }
-int outlier_list_counted(icon_work *w, int64_t N, hipStream_t st) { return outlier_list(w, N, w->d_signs, true, st); }
-int patch_self_rows(icon_work *w, int64_t N, int cmap_slot, hipStream_t st) { return patch_self(w, N, cmap_slot, st); }
-bool fused_path(int precision, int search) { return want_fused(precision, search); }
-void work_mark(icon_work *w, int k, hipStream_t st) { mark(w, k, st); }
-}  // namespace icon
 
 extern "C" int icon_debug_set_unfused(int on)
 {

@@ -219,55 +219,20 @@ class MeshBatchHandle(_Handle):
             m.close()
 
 
-class FeatHandle(_Handle):
-    """Feature planes ``features[-1]`` of HGPIFuNet.filter ([1,C,H,W]) and, for PaMIR, the volume
-    encoder output ([1,Cv,D,H,W]); icon_feat_create."""
-    _destroy = "icon_feat_destroy"
-
-    def __init__(self, planes: torch.Tensor, n_select: int, vol: Optional[torch.Tensor] = None,
-                 smpl_feats: Sequence[str] = ("sdf", "norm", "vis", "cmap")):
-        super().__init__()
-        _lib.require_device()
-        p = _dev_f32(planes, "features")
-        if p.dim() == 4:
-            if p.shape[0] != 1:
-                raise IconAmdError("batch size must be 1 (lib/common/seg3d_lossless.py:73)")
-            p = p[0]
-        p = p.contiguous()
-        Cc, H, W = (int(s) for s in p.shape)
-        vp, Cv, Dv, Hv, Wv = C.c_void_p(0), 0, 0, 0, 0
-        if vol is not None:
-            v = _dev_f32(vol, "vol_feat")
-            if v.dim() == 5:
-                v = v[0]
-            v = v.contiguous()
-            Cv, Dv, Hv, Wv = (int(s) for s in v.shape)
-            vp = ptr(v)
-        self.C, self.H, self.W, self.n_select, self.Cv = Cc, H, W, n_select, Cv
-        with _on(p):
-            check(_lib.lib().icon_feat_create(ptr(p), C.c_int(Cc), C.c_int(H), C.c_int(W), C.c_int(n_select), vp,
-                                              C.c_int(Cv), C.c_int(Dv), C.c_int(Hv), C.c_int(Wv), _stream(),
-                                              C.byref(self.h)), "icon_feat_create")
-        if set(smpl_feats) | {"vis"} != {"sdf", "norm", "vis", "cmap"}:
-            check(_lib.lib().icon_feat_set_smpl_feats(self.h, C.c_int(int("cmap" in smpl_feats)), C.c_int(int("norm" in smpl_feats))),
-                  "icon_feat_set_smpl_feats")
-        # no synchronisation: the repack kernel is enqueued on the current stream, and the caching allocator
-        # recycles the (possibly temporary) source tensors in stream order
-
-
 class FeatBatchHandle(_Handle):
-    """Feature planes ``[B,C,H,W]`` of a batched query(): B plane sets repacked by one launch (icon_feat_create_batch) and, for
+    """Feature planes ``[B,C,H,W]`` of a query(): B plane sets repacked by one launch (icon_feat_create_batch) and, for
     PaMIR, the B volume encoder outputs ``[B,Cv,D,H,W]`` (icon_feat_batch_set_volume)."""
     _destroy = "icon_feat_destroy"
 
     def __init__(self, planes: torch.Tensor, n_select: int, smpl_feats: Sequence[str] = ("sdf", "norm", "vis", "cmap"),
                  vol: Optional[torch.Tensor] = None):
         super().__init__()
+        _lib.require_device()
         p = _dev_f32(planes, "features")
         if p.dim() != 4:
             raise IconAmdError("features must be [B,C,H,W]")
         B, Cc, H, W = (int(x) for x in p.shape)
-        self.B, self.C, self.H, self.W, self.n_select = B, Cc, H, W, n_select
+        self.B, self.C, self.H, self.W, self.n_select, self.Cv = B, Cc, H, W, n_select, 0
         with _on(p):
             check(_lib.lib().icon_feat_create_batch(ptr(p), C.c_int(B), C.c_int(Cc), C.c_int(H), C.c_int(W), C.c_int(n_select), _stream(),
                                                     C.byref(self.h)), "icon_feat_create_batch")
@@ -275,12 +240,27 @@ class FeatBatchHandle(_Handle):
                 v = _dev_f32(vol, "vol_feat")
                 if v.dim() != 5:
                     raise IconAmdError(f"vol_feat {tuple(v.shape)} must be [B,Cv,D,H,W]")
-                Bv, Cv, Dv, Hv, Wv = (int(x) for x in v.shape)
-                check(_lib.lib().icon_feat_batch_set_volume(self.h, ptr(v), C.c_int(Bv), C.c_int(Cv), C.c_int(Dv), C.c_int(Hv), C.c_int(Wv),
+                Bv, self.Cv, Dv, Hv, Wv = (int(x) for x in v.shape)
+                check(_lib.lib().icon_feat_batch_set_volume(self.h, ptr(v), C.c_int(Bv), C.c_int(self.Cv), C.c_int(Dv), C.c_int(Hv), C.c_int(Wv),
                                                             _stream()), "icon_feat_batch_set_volume")
         if set(smpl_feats) | {"vis"} != {"sdf", "norm", "vis", "cmap"}:
             check(_lib.lib().icon_feat_set_smpl_feats(self.h, C.c_int(int("cmap" in smpl_feats)), C.c_int(int("norm" in smpl_feats))),
                   "icon_feat_set_smpl_feats")
+        # no synchronisation: the repack kernels are enqueued on the current stream, and the caching allocator
+        # recycles the (possibly temporary) source tensors in stream order
+
+
+class FeatHandle(FeatBatchHandle):
+    """Feature planes ``features[-1]`` of HGPIFuNet.filter ([1,C,H,W] or [C,H,W]) and, for PaMIR, the volume encoder output
+    ([1,Cv,D,H,W] or [Cv,D,H,W]): a batch of one."""
+
+    def __init__(self, planes: torch.Tensor, n_select: int, vol: Optional[torch.Tensor] = None,
+                 smpl_feats: Sequence[str] = ("sdf", "norm", "vis", "cmap")):
+        if planes.dim() == 4 and planes.shape[0] != 1:
+            raise IconAmdError("batch size must be 1 (lib/common/seg3d_lossless.py:73)")
+        if vol is not None:
+            vol = vol[:1] if vol.dim() == 5 else vol[None]
+        super().__init__(planes if planes.dim() == 4 else planes[None], n_select, smpl_feats, vol)
 
 
 def _np32(t) -> np.ndarray:
@@ -522,7 +502,7 @@ class IconQueryEngine:
         self._mlp = self._mlp_key = self._mlp_src = None
         self._vol = self._vol_key = self._vol_src = None
         self._vol_cached = None
-        self._volb_key = self._volb_src = self._volb_cached = None     # pamir at B > 1: its own cache (_pamir_volume_batch)
+        self._volb_key = self._volb_src = self._volb_cached = None     # pamir at B > 1: its own cache (_pamir_volume(B))
         self._smpl_feat_dict = None
         self._regressor = None
 
@@ -650,30 +630,45 @@ class IconQueryEngine:
             self._zr_key = self._mesh_key
         return self._zr
 
+    def _feat_new(self, cls, im_feat: torch.Tensor, vol: Optional[torch.Tensor]):
+        """(cache key, factory) of the feature handle for these planes (and pamir volume)"""
+        select = 2 if (self.prior_type == "icon" and "vis" in self.smpl_feats) else 1
+        return (_key(im_feat) + (_key(vol) if vol is not None else ()),
+                lambda: cls(im_feat, select, smpl_feats=self.smpl_feats, vol=vol))
+
     def _feat_handle(self, im_feat: torch.Tensor) -> FeatHandle:
         vol = self._pamir_volume() if self.prior_type == "pamir" else None
-        k = _key(im_feat) + (_key(vol) if vol is not None else ())
+        k, new = self._feat_new(FeatHandle, im_feat, vol)
         if k != self._feat_key:
-            select = 2 if (self.prior_type == "icon" and "vis" in self.smpl_feats) else 1
-            self._feat = FeatHandle(im_feat, select, vol, smpl_feats=self.smpl_feats)
+            self._feat = new()
             self._feat_key, self._feat_src = k, (im_feat, vol)
         return self._feat
 
-    def _pamir_volume(self) -> torch.Tensor:
-        """VolumeEncoder output [1,Cv,D,H,W] of the current image (lib/net/HGPIFuNet.py:314-325).  The
-        reference voxelises and encodes on EVERY query() call; both only depend on the image, so they run once
-        per set of voxel tensors: the semantic volume on the HIP voxeliser (semantic_voxelization - no
-        voxelize_cuda wheel needed), the 3-D convolutions of ``netG.ve`` on PyTorch-ROCm."""
+    def _pamir_volume(self, B: Optional[int] = None) -> torch.Tensor:
+        """VolumeEncoder output of the current image(s) (lib/net/HGPIFuNet.py:314-325): [1,Cv,D,H,W] for the unbatched call
+        (B = None), [B,Cv,D,H,W] for a batched one - two caches, one per kind of call.  The reference voxelises and encodes on
+        EVERY query() call; both only depend on the image, so they run once per set of voxel tensors: the semantic volume on
+        the HIP voxeliser (semantic_voxelization / _batch - no voxelize_cuda wheel needed), the 3-D convolutions of
+        ``netG.ve`` on PyTorch-ROCm.  At batch size B the reference strips every subject's padding
+        with subject 0's counts (:316-319) and voxelises every subject with subject 0's tetrahedra (:321-323)."""
+        batched = B is not None
         if self._vol is not None:
-            return self._vol
+            v = self._vol
+            if batched and (v.dim() != 5 or int(v.shape[0]) != B):
+                raise IconAmdError(f"set_volume_features: vol_feat {tuple(v.shape)} does not hold the {B} subjects of the points ([B,Cv,D,H,W])")
+            return v
         netG = self.netG
         if netG is None or not hasattr(netG, "voxelization") or not hasattr(netG, "ve"):
-            raise IconAmdError("pamir prior: call set_volume_features(vol_feat) (VolumeEncoder output)")
+            raise IconAmdError("pamir prior: call set_volume_features(vol_feat) (VolumeEncoder output" + (" [B,Cv,D,H,W])" if batched else ")"))
         d = netG.smpl_feat_dict
-        k = _key(d["voxel_verts"], d["voxel_faces"])
-        if k != self._vol_key:
-            vv = d["voxel_verts"][:, :-int(d["pad_v_num"][0]), :]
-            vf = d["voxel_faces"][:, :-int(d["pad_f_num"][0]), :]
+        src = (d["voxel_verts"], d["voxel_faces"])
+        k = _key(*src)
+        if k != (self._volb_key if batched else self._vol_key):
+            if batched and any(t.dim() != 3 or int(t.shape[0]) != B for t in src):
+                raise IconAmdError(f"voxel_verts {tuple(src[0].shape)} / voxel_faces {tuple(src[1].shape)} do not hold the {B} "
+                                   "subjects of the points")
+            vv = src[0][:, :-int(d["pad_v_num"][0]), :]          # subject 0's counts for every subject (:316-319)
+            vf = src[1][:, :-int(d["pad_f_num"][0]), :]
             vox = netG.voxelization
             if self._use_reference_voxelizer():
                 # the reference's own leaf (lib/net/voxelize.py:119-137 -> voxelize_cuda wheel), exactly as
@@ -682,45 +677,16 @@ class IconQueryEngine:
                     vox.update_param(batch_size=vf.shape[0], smpl_tetra=vf[0].detach().cpu().numpy())   # HGPIFuNet.py:321-323
                     vol = vox(vv)                                                                        # :324, vol ~ [0,1]
             else:
-                vol = semantic_voxelization(vv, vf, vox.smpl_vertex_code, res=int(getattr(vox, "volume_res", 128)),
-                                            sigma=float(getattr(vox, "sigma", 0.05)))
+                kw = dict(res=int(getattr(vox, "volume_res", 128)), sigma=float(getattr(vox, "sigma", 0.05)))
+                vol = (semantic_voxelization_batch(vv, vf[0], vox.smpl_vertex_code, **kw) if batched
+                       else semantic_voxelization(vv, vf, vox.smpl_vertex_code, **kw))
             with torch.no_grad():
-                self._vol_cached = netG.ve(vol, intermediate_output=False)[-1]
-            self._vol_key, self._vol_src = k, (d["voxel_verts"], d["voxel_faces"])
-        return self._vol_cached
-
-    def _pamir_volume_batch(self, B: int) -> torch.Tensor:
-        """VolumeEncoder output [B,Cv,D,H,W] of a batch (lib/net/HGPIFuNet.py:314-325 at batch size B), once per batch of voxel
-        tensors, cached apart from the B = 1 volume of _pamir_volume.  The reference strips every subject's padding with
-        subject 0's counts (:316-319) and voxelises every subject with subject 0's tetrahedra (:321-323)."""
-        if self._vol is not None:
-            v = self._vol
-            if v.dim() != 5 or int(v.shape[0]) != B:
-                raise IconAmdError(f"set_volume_features: vol_feat {tuple(v.shape)} does not hold the {B} subjects of the points ([B,Cv,D,H,W])")
-            return v
-        netG = self.netG
-        if netG is None or not hasattr(netG, "voxelization") or not hasattr(netG, "ve"):
-            raise IconAmdError("pamir prior: call set_volume_features(vol_feat) (VolumeEncoder output [B,Cv,D,H,W])")
-        d = netG.smpl_feat_dict
-        k = _key(d["voxel_verts"], d["voxel_faces"])
-        if k != self._volb_key:
-            if d["voxel_verts"].dim() != 3 or int(d["voxel_verts"].shape[0]) != B or d["voxel_faces"].dim() != 3 or int(d["voxel_faces"].shape[0]) != B:
-                raise IconAmdError(f"voxel_verts {tuple(d['voxel_verts'].shape)} / voxel_faces {tuple(d['voxel_faces'].shape)} do not hold the {B} "
-                                   "subjects of the points")
-            vv = d["voxel_verts"][:, :-int(d["pad_v_num"][0]), :]          # subject 0's counts for every subject (:316-319)
-            vf = d["voxel_faces"][:, :-int(d["pad_f_num"][0]), :]
-            vox = netG.voxelization
-            if self._use_reference_voxelizer():
-                with torch.no_grad():
-                    vox.update_param(batch_size=vf.shape[0], smpl_tetra=vf[0].detach().cpu().numpy())   # HGPIFuNet.py:321-323
-                    vol = vox(vv)                                                                        # :324
+                out = netG.ve(vol, intermediate_output=False)[-1]                  # eval: [out_lst[-1]] (VE.py:166-183)
+            if batched:
+                self._volb_cached, self._volb_key, self._volb_src = out, k, src
             else:
-                vol = semantic_voxelization_batch(vv, vf[0], vox.smpl_vertex_code, res=int(getattr(vox, "volume_res", 128)),
-                                                  sigma=float(getattr(vox, "sigma", 0.05)))
-            with torch.no_grad():
-                self._volb_cached = netG.ve(vol, intermediate_output=False)[-1]       # eval: [out_lst[-1]] (VE.py:166-183)
-            self._volb_key, self._volb_src = k, (d["voxel_verts"], d["voxel_faces"])
-        return self._volb_cached
+                self._vol_cached, self._vol_key, self._vol_src = out, k, src
+        return self._volb_cached if batched else self._vol_cached
 
     def _use_reference_voxelizer(self) -> bool:
         """voxelizer='reference': always netG.voxelization (needs the voxelize_cuda wheel); 'hip': always the HIP
@@ -888,12 +854,10 @@ class IconQueryEngine:
         """features: list of [B,C,H,W]; points [B,3,N]; calibs [B,4,4] (or [B,3,4]) -> list of [B,1,N]"""
         if points.dim() != 3 or points.shape[1] != 3 or points.shape[0] < 1:
             raise IconAmdError("points must be [B,3,N]")
-        if points.shape[0] != 1:
-            return self._query_batch(features, points, calibs, transforms, regressor)
         if not points.is_cuda:
             raise IconAmdError("points are on the CPU; icon_amd has no CPU path")
         n = int(points.shape[2])
-        if n == 0:
+        if n == 0 and points.shape[0] == 1:
             return [torch.empty((1, 1, 0), dtype=torch.float32, device=points.device) for _ in features]
         if transforms is not None:
             # lib/net/geometry.py:57-60 indexes `transforms[:2, :2]` / `transforms[:2, 2:3]` and feeds the slices to
@@ -902,6 +866,8 @@ class IconQueryEngine:
             # argument (tests/test_oracle_vs_reference.py pins that).  There is no behaviour to reproduce.
             raise IconAmdError("query(transforms=...) is not supported: the reference's own orthogonal() raises for any "
                                "`transforms` (lib/net/geometry.py:57-60) and none of its callers passes one")
+        if points.shape[0] != 1:
+            return self._query_batch(features, points, calibs, regressor)
         if calibs.is_cuda:
             # stays on the device: the kernels read the 12 floats themselves (no D2H copy / stream sync per query)
             calib12 = calibs[0, :3, :4].detach().to(torch.float32).contiguous()
@@ -958,25 +924,19 @@ class IconQueryEngine:
     def _feat_batch_handle(self, im_feat: torch.Tensor, cache: dict, vol: Optional[torch.Tensor] = None) -> FeatBatchHandle:
         """one handle per feature stack (and pamir volume) of the call, kept while the next call passes the same tensors (``cache``:
         this call's)"""
-        k = _key(im_feat) + (_key(vol) if vol is not None else ())
+        k, new = self._feat_new(FeatBatchHandle, im_feat, vol)
         old = getattr(self, "_featb", {})
         if k in old:
             cache[k] = old[k]
         elif k not in cache:
-            select = 2 if (self.prior_type == "icon" and "vis" in self.smpl_feats) else 1
-            cache[k] = (FeatBatchHandle(im_feat, select, smpl_feats=self.smpl_feats, vol=vol), im_feat, vol)
+            cache[k] = (new(), im_feat, vol)
         return cache[k][0]
 
-    def _query_batch(self, features, points, calibs, transforms, regressor):
+    def _query_batch(self, features, points, calibs, regressor):
         """HGPIFuNet.query at batch size B > 1: ONE native call per feature stack over the B*N points (icon_query_points_batch),
         so the reference's batch-global outlier cmap list (lib/net/HGPIFuNet.py:303-305) is reproduced and the number of
         launches does not depend on B"""
         B, n = int(points.shape[0]), int(points.shape[2])
-        if not points.is_cuda:
-            raise IconAmdError("points are on the CPU; icon_amd has no CPU path")
-        if transforms is not None:
-            raise IconAmdError("query(transforms=...) is not supported: the reference's own orthogonal() raises for any "
-                               "`transforms` (lib/net/geometry.py:57-60) and none of its callers passes one")
         if calibs.dim() != 3 or int(calibs.shape[0]) != B or tuple(calibs.shape[1:]) not in ((4, 4), (3, 4)):
             raise IconAmdError(f"calibs {tuple(calibs.shape)} must be [{B},4,4] or [{B},3,4] (torch.baddbmm does not broadcast a batch)")
         for im_feat in features:
@@ -1005,7 +965,7 @@ class IconQueryEngine:
         # calibrations stay on (or go to) the device: the kernels read subject b's 12 floats themselves
         calib12 = calibs[:, :3, :4].detach().to(points.device, torch.float32).contiguous()
         pts = points.detach().transpose(1, 2).to(torch.float32).contiguous()
-        vol = self._pamir_volume_batch(B) if self.prior_type == "pamir" and len(features) else None
+        vol = self._pamir_volume(B) if self.prior_type == "pamir" and len(features) else None
         cache, preds = {}, []
         for im_feat in features:
             feat = self._feat_batch_handle(im_feat, cache, vol)

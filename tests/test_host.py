@@ -336,8 +336,17 @@ def test_hot_kernels_do_not_spill():
             return out
     with ThreadPoolExecutor(3) as ex:
         fused, mlp, query = ex.map(lambda a: remarks(*a), [("fused_f16x3.hip", True), ("mlp_f16x3.hip", False), ("query_kernels.hip", True)])
-    icon_fused = {k: v for k, v in fused.items() if "k_fused_f16x3ILi0E" in k}
-    assert len(icon_fused) == 4, list(fused)                # lattice / points x (257^3 kernel, small-call variant)
+    # k_fused_f16x3<ICON, Src, SMALL> by mangled name: Src::Lattice = 0, Src::Points = 1, Src::Batch = 2 (common.h)
+    def icon_of(src):
+        return {k: v for k, v in fused.items() if f"k_fused_f16x3ILi0ELNS_3SrcE{src}ELb" in k}
+    icon_fused = {**icon_of(0), **icon_of(1)}
+    assert len(icon_of(0)) == 2 and len(icon_of(1)) == 2, list(fused)   # lattice / points x (257^3 kernel, small-call variant)
+    # the batched icon instantiations (large / small): the scratch size of the copies of the kernel they replaced
+    # (profiles/kernel_resources_before.txt) - 0 bytes
+    icon_batch = icon_of(2)
+    assert len(icon_batch) == 2, list(fused)
+    icon_fused.update(icon_batch)
+    assert len(icon_fused) == 6 == sum("k_fused_f16x3ILi0E" in k for k in fused), list(fused)
     print({k[-40:]: v for k, v in icon_fused.items()})
     for k, v in {**icon_fused, **{k: v for k, v in mlp.items() if "k_mlp_f16x3" in k}}.items():
         assert v["ScratchSize [bytes/lane]"] == 0, (k, v)
