@@ -2,7 +2,7 @@
 """End-to-end on the synthetic subject: what apps/ICON.py:test_single does after netG.filter() (lines 729-761) -
 reconEngine -> export_mesh -> clean_mesh -> vertices into the [-1,1] cube - through the HIP path, with timings.
 
-    python examples/dense_recon.py [--res 257] [--adaptive] [--out body.obj]
+    python examples/dense_recon.py [--res 257] [--adaptive] [--color] [--out body.obj]
 
 Needs an MI355X (there is no CPU path).  The inputs stand in for what the reference computes upstream of the hot path:
 `features` = HGPIFuNet.filter() output, the SMPL tensors = TestDataset.compute_vis_cmap(), the regressor = netG.if_regressor.
@@ -21,11 +21,12 @@ def main():
     ap.add_argument("--res", type=int, default=257)
     ap.add_argument("--adaptive", action="store_true", help="the reference's coarse-to-fine schedule instead of the dense lattice")
     ap.add_argument("--out", default=None, help="write the mesh as Wavefront OBJ")
+    ap.add_argument("--color", action="store_true", help="colour the vertices from a synthetic image (query_color, apps/infer.py:531); OBJ lines become v x y z r g b")
     args = ap.parse_args()
     import torch
     from icon_amd import synth
     from icon_amd.engine import IconQueryEngine, query_func
-    from icon_amd.recon import AdaptiveReconEngine, DenseReconEngine, clean_mesh
+    from icon_amd.recon import AdaptiveReconEngine, DenseReconEngine, clean_mesh, query_color
 
     dev = torch.device("cuda:0")
     a = synth.make_assets("body")
@@ -54,13 +55,24 @@ def main():
     t3 = sync()
     half = (res - 1) / 2.0
     verts = (verts.float() - half) / half                                       # apps/ICON.py:758-759
+    colors, color_ms = None, ""
+    if args.color:
+        import numpy as np
+        image = torch.from_numpy(np.tanh(synth.make_feature_planes(3, 512, 531)).astype(np.float32))    # stands in for the input photograph, in [-1,1]
+        query_color(verts, faces, image)                                        # warm-up: the call's scratch
+        t4 = sync()
+        colors = query_color(verts, faces, image)                               # [V,3] 0..255 on the CPU, as upstream
+        color_ms = f", query_color {1e3 * (sync() - t4):.2f} ms"
     print(f"{'adaptive' if args.adaptive else 'dense'} {res}^3: volume {1e3 * (t1 - t0):.2f} ms, marching cubes {1e3 * (t2 - t1):.2f} ms, "
-          f"clean_mesh {1e3 * (t3 - t2):.2f} ms -> {verts.shape[0]} vertices, {faces.shape[0]} faces, "
+          f"clean_mesh {1e3 * (t3 - t2):.2f} ms{color_ms} -> {verts.shape[0]} vertices, {faces.shape[0]} faces, "
           f"bbox {verts.min(0).values.tolist()} .. {verts.max(0).values.tolist()}")
     if args.out:
         v, f = verts.cpu().numpy(), faces.cpu().numpy() + 1
         with open(args.out, "w") as fh:
-            fh.writelines(f"v {x:.6f} {y:.6f} {z:.6f}\n" for x, y, z in v)
+            if colors is None:
+                fh.writelines(f"v {x:.6f} {y:.6f} {z:.6f}\n" for x, y, z in v)
+            else:                                                               # the common "v x y z r g b" extension, colours in 0..1
+                fh.writelines(f"v {x:.6f} {y:.6f} {z:.6f} {r:.6f} {g:.6f} {b:.6f}\n" for (x, y, z), (r, g, b) in zip(v, colors.numpy() / 255.0))
             fh.writelines(f"f {i} {j} {k}\n" for i, j, k in f)
         print("wrote", args.out)
 

@@ -36,6 +36,7 @@ SYMBOLS = [
     "icon_visibility", "icon_mesh_components", "icon_clean_mesh", "icon_semantic_voxelize",
     "icon_mesh_batch_create", "icon_mesh_batch_destroy", "icon_mesh_batch_status", "icon_feat_create_batch", "icon_query_points_batch",
     "icon_feat_batch_set_volume", "icon_semantic_voxelize_batch",
+    "icon_query_color_bytes", "icon_query_color",
 ]
 
 _lib = None

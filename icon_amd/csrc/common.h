@@ -149,6 +149,33 @@ struct FeatDev {
 };
 constexpr int kSmplCmap = 1, kSmplNorm = 2;
 
+// S7: where one grid_sample position (bilinear, zeros padding, align_corners=True) lands in an [H][W] plane - ATen's
+// unnormalisation and corner weights, in its operation order.  A tap outside the plane contributes 0 (b?? false).  The
+// sample is ((t00*nw + t01*ne) + t10*sw) + t11*se.  Callers are compiled with -ffp-contract=off.  The same expressions as
+// gather_planes (geom_device.h), which keeps them inline: routed through this struct the fused MLP kernels keep their
+// registers, scratch and spills but come out as another instruction schedule (their ISA differs in 34,633 lines of diff) -
+// a different binary of the benchmarked kernel, for no gain.  tests/test_query_color.py compares the two statements as text.
+struct BilinearTaps {
+    int x0, y0;                 // north-west tap; the others are x0 + 1 / y0 + 1
+    float nw, ne, sw, se;
+    bool bx0, bx1, by0, by1;    // column x0 / x0 + 1 and row y0 / y0 + 1 lie inside the plane
+};
+__device__ __forceinline__ BilinearTaps bilinear_taps(float x, float y, int H, int W)
+{
+    BilinearTaps t;
+    const float ix = ((x + 1.0f) / 2.0f) * (float)(W - 1);
+    const float iy = ((y + 1.0f) / 2.0f) * (float)(H - 1);
+    const float fx = floorf(ix), fy = floorf(iy);
+    t.x0 = (int)fx; t.y0 = (int)fy;
+    const int x1 = t.x0 + 1, y1 = t.y0 + 1;
+    t.nw = ((float)x1 - ix) * ((float)y1 - iy);
+    t.ne = (ix - (float)t.x0) * ((float)y1 - iy);
+    t.sw = ((float)x1 - ix) * (iy - (float)t.y0);
+    t.se = (ix - (float)t.x0) * (iy - (float)t.y0);
+    t.bx0 = t.x0 >= 0 && t.x0 < W; t.bx1 = x1 >= 0 && x1 < W; t.by0 = t.y0 >= 0 && t.y0 < H; t.by1 = y1 >= 0 && y1 < H;
+    return t;
+}
+
 // affine calibration (rot | trans), row-major [3][4]; when `d` is set the 12 floats are read from
 // device memory by the kernel itself (wave-uniform scalar loads), so a caller holding the calibration
 // on the device never has to copy it to the host (no stream synchronisation in query())
@@ -364,6 +391,7 @@ struct ShareDbg {
 int work_share_dbg(icon_work *w, ShareDbg *out);
 // ICON_ERR_STATE (and the record cleared) if a shared walk of an earlier launch on this workspace reported; no synchronisation
 int work_check_err(icon_work *w);
+extern int g_qc_lanes;                // query_color.hip: lanes per face of the colour call's rasteriser ("qc_lanes"; 0 = default)
 int share_waves_override();           // ICON_AMD_SHARE / icon_debug_set_option("share_waves"): -1 = by launch size
 }  // namespace icon
 

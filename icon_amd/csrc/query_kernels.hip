@@ -1488,6 +1488,7 @@ extern "C" int icon_debug_set_option(const char *key, int value)
     else if (k == "share_ring") { ICON_ARG(value == 0 || (value >= 2 && value <= 64 && (value & (value - 1)) == 0), "share_ring: 0 or a power of two in 2..64"); g_share_ring = value; }
     else if (k == "share_lose_push") { ICON_ARG(value >= 0, "share_lose_push: a ticket >= 1, or 0"); g_share_lose = value; }
     else if (k == "share_spin_log2") { ICON_ARG(value >= 0 && value < 30, "share_spin_log2: 0..29"); g_share_spin_log2 = value; }
+    else if (k == "qc_lanes") { ICON_ARG(value == 0 || value == 64, "qc_lanes: 0 (default) or 64"); g_qc_lanes = value; }
     else return fail(ICON_ERR_ARG, "icon_debug_set_option: unknown key " + k);
     return ICON_OK;
 }

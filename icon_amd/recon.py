@@ -799,6 +799,107 @@ def _mc_workspace(device: torch.device):
     return pool[idx]
 
 
+_qc_tls = threading.local()
+
+
+def _qc_scratch(device: torch.device, nbytes: int) -> torch.Tensor:
+    """query_color scratch: one tensor per (thread, device, stream), grown on demand and reused.  Per stream, because two calls
+    on different streams may run at once and must not share a z-buffer; and because torch's allocator orders the reuse of a
+    freed block only against the stream it was allocated on - which, keyed like this, is the stream that used it."""
+    pool = getattr(_qc_tls, "pool", None)
+    if pool is None:
+        pool = _qc_tls.pool = {}
+    idx = device.index if device.index is not None else torch.cuda.current_device()
+    key = (idx, torch.cuda.current_stream(idx).cuda_stream)
+    buf = pool.get(key)
+    if buf is None or buf.numel() < nbytes:
+        buf = pool[key] = torch.empty(nbytes, dtype=torch.uint8, device=torch.device("cuda", idx))
+    return buf
+
+
+def _qc_shapes(verts, faces, image):
+    if verts.dim() != 2 or verts.shape[1] != 3 or verts.shape[0] == 0:
+        raise IconAmdError(f"query_color: verts must be [V,3], got {tuple(verts.shape)}")
+    if faces.dim() != 2 or faces.shape[1] != 3 or faces.shape[0] == 0:
+        raise IconAmdError(f"query_color: faces must be [F,3], got {tuple(faces.shape)}")
+    if faces.dtype.is_floating_point or faces.dtype == torch.bool:
+        raise IconAmdError(f"query_color: faces must be an integer tensor, got {faces.dtype}")
+    if image.dim() != 4 or image.shape[1] != 3 or image.shape[2] == 0 or image.shape[3] == 0:
+        raise IconAmdError(f"query_color: image must be [1,3,H,W], got {tuple(image.shape)}")
+    if image.shape[0] != 1:
+        raise IconAmdError(f"query_color: image batch must be 1 (one grid of vertices is sampled), got {image.shape[0]}")
+
+
+def _query_color_launch(verts, faces, image, image_size, return_vis, return_bad):
+    """validates, enqueues icon_query_color on the current stream -> (colors, vis or None, bad or None); bad: a device int32 [1],
+    the number of faces the call skipped because they name a vertex that does not exist (copied out of the scratch header on
+    the same stream)"""
+    from .engine import _stream
+    _qc_shapes(verts, faces, image)
+    if not torch.cuda.is_available():
+        raise IconAmdError("query_color needs the HIP device (there is no CPU fallback)")
+    if not (verts.is_cuda and faces.is_cuda and image.is_cuda) or not (verts.device == faces.device == image.device):
+        raise IconAmdError("query_color_device: verts, faces and image must live on one HIP device (query_color moves host tensors)")
+    dev = verts.device
+    v = verts.detach().to(torch.float32).contiguous()
+    f = faces.detach()
+    if f.dtype not in (torch.int32, torch.int64):
+        f = f.to(torch.int64)
+    f = f.contiguous()
+    img = image.detach().to(torch.float32).contiguous()
+    L = _lib.lib()
+    with torch.cuda.device(dev):
+        nbytes = C.c_int64(0)
+        check(L.icon_query_color_bytes(C.c_int64(v.shape[0]), C.c_int64(f.shape[0]), C.c_int(int(image_size)), C.byref(nbytes)),
+              "icon_query_color_bytes")
+        scratch = _qc_scratch(dev, nbytes.value)
+        colors = torch.empty((v.shape[0], 3), dtype=torch.float32, device=dev)
+        vis = torch.empty(v.shape[0], dtype=torch.float32, device=dev) if return_vis else None
+        check(L.icon_query_color(_lib.ptr(v), C.c_int64(v.shape[0]), _lib.ptr(f), C.c_int64(f.shape[0]), C.c_int(1 if f.dtype == torch.int64 else 0),
+                                 _lib.ptr(img), C.c_int(img.shape[2]), C.c_int(img.shape[3]), C.c_int(int(image_size)), _lib.ptr(colors),
+                                 _lib.ptr(vis), _lib.ptr(scratch), C.c_int64(scratch.numel()), _stream()), "icon_query_color")
+        bad = scratch[:4].view(torch.int32).clone() if return_bad else None     # first word of the header (include/icon_amd.h)
+    return colors, vis, bad
+
+
+def query_color_device(verts: torch.Tensor, faces: torch.Tensor, image: torch.Tensor, image_size: int = 2 ** 12, return_vis: bool = False):
+    """``query_color`` with everything left on the device: ``verts [V,3]``, ``faces [F,3]`` (int32 - what clean_mesh returns -
+    or int64 - what export_mesh_device returns - read in place), ``image [1,3,H,W]``, all on one HIP device ->
+    ``colors [V,3]`` float32 there (and ``vis [V]`` with ``return_vis``).  ONE native call (icon_query_color) enqueued on the
+    current stream: nothing is allocated by it, nothing read back, the stream is not waited for - so a face that names a vertex
+    that does not exist cannot raise here; such a face is skipped (it covers no pixel and adds to no normal).  The call's
+    scratch is cached per (thread, device, stream): calls on different streams do not share it."""
+    colors, vis, _ = _query_color_launch(verts, faces, image, image_size, return_vis, False)
+    return (colors, vis) if return_vis else colors
+
+
+def query_color(verts: torch.Tensor, faces: torch.Tensor, image: torch.Tensor, device=None) -> torch.Tensor:
+    """Drop-in for ``lib.common.render.query_color`` (render.py:60-84; apps/infer.py:531 colours the reconstructed mesh with it):
+    ``verts [V,3]``, ``faces [F,3]``, ``image [1,3,H,W]`` in [-1,1], host or device tensors -> ``colors [V,3]`` float32 on the CPU,
+    0..255: the image sampled at (x, -y) for the vertices ``get_visibility(xy, z, faces[:, [0,2,1]])`` marks, the vertex
+    normal mapped to a colour for the others.  ``device``: the HIP device to run on (default: where ``verts`` lives, else the
+    current one).  No pytorch3d involved; there is no CPU path."""
+    verts, faces, image = torch.as_tensor(verts), torch.as_tensor(faces), torch.as_tensor(image)
+    _qc_shapes(verts, faces, image)
+    if not faces.is_cuda and (int(faces.min()) < 0 or int(faces.max()) >= verts.shape[0]):      # host data: no device involved
+        raise IconAmdError("query_color: face index out of range")
+    if not torch.cuda.is_available():
+        raise IconAmdError("query_color needs the HIP device (there is no CPU fallback)")
+    dev = torch.device(device) if device is not None else (verts.device if verts.is_cuda else torch.device("cuda", torch.cuda.current_device()))
+    if dev.type != "cuda":
+        raise IconAmdError(f"query_color: device must be a HIP device, got {dev} (there is no CPU fallback)")
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    f = faces.detach()
+    f = f.to(dev) if f.dtype in (torch.int32, torch.int64) else f.to(dev, torch.int64)
+    with torch.cuda.device(dev):
+        colors, _, bad = _query_color_launch(verts.detach().to(dev, torch.float32), f, image.detach().to(dev, torch.float32), 2 ** 12, False, faces.is_cuda)
+    out = colors.cpu()                                                    # the reference returns a CPU tensor: this waits for the stream
+    if bad is not None and int(bad.item()):                                # device faces were not looked at before the launch: the call counted what it skipped
+        raise IconAmdError("query_color: face index out of range")
+    return out
+
+
 def merge_keyed_meshes(keys, verts, faces):
     """The pieces of a sharded triangulation (DenseReconEngine.forward_mesh) -> one mesh.  Per rank, in rank order: keys [nv] int64
     (3 * cell + edge direction = the vertex's place in the vertex order of marching cubes on the whole volume; the crossings

@@ -382,7 +382,9 @@ int icon_debug_set_shell_skip(int on);
  * of the 257^3-class search derive its own tile set-up instead of reading the per-call record.  "share_waves" (-1 = by launch
  * size): wavefronts that share one packet's walk, 1 / 8 / 16 (4: adaptive schedule only).  "share_ring" (0 = 64): forced
  * ring size of the shared walks' hand-over queue; "share_lose_push" (0 = none): ticket of the push that is announced but never
- * stored; "share_spin_log2" (0 = 18): the wait bound, 2^n polls - the torture / fault-injection tests of the error path below. */
+ * stored; "share_spin_log2" (0 = 18): the wait bound, 2^n polls - the torture / fault-injection tests of the error path below.
+ * "qc_lanes" (0 = 8, the default mapping): 64 makes icon_query_color's rasteriser sweep a face with one whole wavefront,
+ * icon_visibility's mapping - tools/time_query_color.py times the two against each other; the result does not depend on it. */
 int icon_debug_set_option(const char *key, int value);
 /* The searches of coarse lattices and of the adaptive schedule share one packet's BVH walk between the wavefronts of a
  * workgroup through an LDS queue (csrc/geom_device.h nearest_shared).  Every wait in that hand-over is bounded; a wave that
@@ -496,6 +498,23 @@ int icon_clean_mesh(const float *d_verts, int64_t V, const int64_t *d_faces, int
  * d_faces [F,3] int64, d_vis [V] float32 out in {0,1}.  Synchronises the stream (frees its z-buffer). */
 int icon_visibility(const float *d_xy, const float *d_z, int64_t V, const int64_t *d_faces, int64_t F,
                     int image_size, float *d_vis, void *stream);
+
+/* ---- vertex colours of the reconstructed mesh --------------------------------------------------------
+ * replaces query_color (lib/common/render.py:60-84; called at apps/infer.py:531 on the cleaned marching-cubes mesh):
+ *   vis = get_visibility(xy, z, faces[:, [0,2,1]]) - icon_visibility's rule on the corner-swapped faces, z as it is;
+ *   colour = ((grid_sample(image, (x, -y), bilinear, zeros, align_corners=True) + 1) * 0.5) * 255 where vis == 1,
+ *            ((n + 1) * 0.5) * 255 with n the S1 vertex normal of the faces as given where vis == 0.
+ * d_verts [V,3] f32; d_faces [F,3], int64 when faces_int64 != 0 (icon_mc_emit), else int32 (icon_clean_mesh) - read in place;
+ * d_image [3,H,W] f32; d_colors [V,3] f32 out; d_vis [V] f32 out in {0,1}, or NULL.  A face that names a vertex that
+ * does not exist is skipped (it neither covers pixels nor adds to a normal) and counted: after the stream has been waited
+ * for, the first int32 of the scratch holds the number of such faces.  d_scratch: device memory of at least
+ * icon_query_color_bytes(V, F, image_size) bytes, 256-byte aligned, owned by the caller; its contents need not survive
+ * between calls.  Enqueued on `stream`: no allocation, no synchronisation, nothing read back; results are bit-identical from
+ * run to run. */
+int icon_query_color_bytes(int64_t V, int64_t F, int image_size, int64_t *bytes);
+int icon_query_color(const float *d_verts, int64_t V, const void *d_faces, int64_t F, int faces_int64,
+                     const float *d_image, int H, int W, int image_size, float *d_colors, float *d_vis,
+                     void *d_scratch, int64_t scratch_bytes, void *stream);
 
 #ifdef __cplusplus
 }
