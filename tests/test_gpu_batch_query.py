@@ -66,7 +66,9 @@ def test_batch_matches_reference_fixture(variant, precision):
 @pytest.mark.parametrize("variant", ["full", "sdf", "pifu"])
 def test_local_mode_equals_single_subject_calls(B, n, variant):
     """cmap_mode 'local' has no cross-subject coupling: subject b of the batch is bit for bit a B = 1 call on subject b (B * n
-    above kPacketMinPoints takes the Morton + packet search, the B = 1 calls the cooperative one)"""
+    above kPacketMinPoints takes the Morton + packet search, the B = 1 calls the cooperative one).  The packet case here has
+    n = 40,000 = 625 * 64: no subject's segment is padded, so no wave holds a parked lane - the padding of k_nearest_batch is
+    covered by tests/test_gpu_batch_oracle.py (n % 64 != 0)"""
     eng, S, feats = engine(variant, B=B, cmap_mode="local")
     pts = world_points(S, n, seed=5)
     calibs = T(S["calibs"])
