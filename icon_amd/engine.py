@@ -1157,11 +1157,12 @@ def semantic_voxelization(voxel_verts: torch.Tensor, voxel_tets: torch.Tensor, v
 
 
 def semantic_voxelization_batch(voxel_verts: torch.Tensor, voxel_tets: torch.Tensor, vertex_code, res: int = 128,
-                                sigma: float = 0.05) -> torch.Tensor:
+                                sigma: float = 0.05, return_occ: bool = False):
     """``Voxelization.forward`` at batch size B (lib/net/voxelize.py:119-137, as HGPIFuNet.query calls it at :316-324) in one launch
     of each kernel: ``voxel_verts [B,V,3]`` (padding stripped with subject 0's count), ``voxel_tets [T,4]`` (or [1,T,4]) - subject 0's
     tetrahedra, which update_param tiles over the batch - and ``vertex_code [Vs,3]`` shared by every subject ->
-    ``[B,3,res,res,res]`` (b,c,d,h,w).  Subject b is bit for bit ``semantic_voxelization(voxel_verts[b:b+1], voxel_tets)``."""
+    ``[B,3,res,res,res]`` (b,c,d,h,w).  Subject b is bit for bit ``semantic_voxelization(voxel_verts[b:b+1], voxel_tets)``.
+    With ``return_occ`` also the occupancy the kernels worked from, ``[B,res,res,res]`` uint8 (z,y,x), 1 = the centre is in a tetrahedron."""
     if not voxel_verts.is_cuda:
         raise IconAmdError("semantic_voxelization_batch needs device tensors (there is no CPU path)")
     if voxel_verts.dim() != 3 or voxel_verts.shape[2] != 3:
@@ -1180,7 +1181,8 @@ def semantic_voxelization_batch(voxel_verts: torch.Tensor, voxel_tets: torch.Ten
         check(_lib.lib().icon_semantic_voxelize_batch(ptr(v), C.c_int(B), C.c_int64(V), C.c_int64(code.shape[0]), ptr(code), ptr(t),
                                                       C.c_int64(t.shape[0]), C.c_int(res), C.c_float(sigma), ptr(occ), ptr(out), _stream()),
               "icon_semantic_voxelize_batch")
-    return out.permute(0, 4, 1, 2, 3)
+    vol = out.permute(0, 4, 1, 2, 3)
+    return (vol, occ.view(B, res, res, res)) if return_occ else vol
 
 
 def get_visibility(xy: torch.Tensor, z: torch.Tensor, faces: torch.Tensor, image_size: int = 2 ** 12) -> torch.Tensor:

@@ -123,14 +123,15 @@ def test_batched_voxeliser_is_the_single_subject_voxeliser(res):
     S = bp.subjects(bp.B_GOLDEN)
     vv = T(S["verts"])
     tets = T(S["tets"])
-    vol = semantic_voxelization_batch(vv, tets, S["code"], res=res, sigma=bp.SIGMA)
-    assert tuple(vol.shape) == (bp.B_GOLDEN, 3, res, res, res)
+    vol, occ_dev = semantic_voxelization_batch(vv, tets, S["code"], res=res, sigma=bp.SIGMA, return_occ=True)
+    assert tuple(vol.shape) == (bp.B_GOLDEN, 3, res, res, res) and tuple(occ_dev.shape) == (bp.B_GOLDEN, res, res, res)
     for b in range(bp.B_GOLDEN):
         one = semantic_voxelization(vv[b:b + 1], tets[None], S["code"], res=res, sigma=bp.SIGMA)
         assert torch.equal(vol[b], one[0]), f"subject {b}"
         got = vol[b].permute(1, 2, 3, 0).cpu().numpy()
         ref, occ = orc.semantic_voxelize(S["verts"][b], len(S["code"]), S["code"], S["tets"], res=res, sigma=bp.SIGMA, return_occ=True)
         assert np.array_equal(np.abs(got).sum(-1) > 0, occ)
+        assert np.array_equal(occ_dev[b].cpu().numpy(), occ.astype(np.uint8))                     # the occupancy itself, not inferred
         assert np.abs(got - ref).max() <= 1e-5
 
 

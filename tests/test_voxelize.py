@@ -40,7 +40,7 @@ def test_oracle_voxelizer_occupancy_is_the_body_interior():
 @pytest.mark.gpu
 @pytest.mark.parametrize("res", [32, 128])
 def test_semantic_voxelization_vs_oracle(res):
-    from icon_amd.engine import semantic_voxelization
+    from icon_amd.engine import semantic_voxelization, semantic_voxelization_batch
     a, (vv, tets, code) = _tetra()
     dev = torch.device("cuda:0")
     vol = semantic_voxelization(torch.from_numpy(vv)[None].to(dev), torch.from_numpy(tets)[None].to(dev), code, res=res, sigma=0.05)
@@ -48,6 +48,10 @@ def test_semantic_voxelization_vs_oracle(res):
     got = vol[0].permute(1, 2, 3, 0).cpu().numpy()                                                # (z, y, x, c)
     ref, occ = orc.semantic_voxelize(vv, len(code), code, tets, res=res, sigma=0.05, return_occ=True)
     assert np.array_equal(np.abs(got).sum(-1) > 0, occ)                                           # same float32 inside test
+    # the occupancy itself (the batch entry hands it out), not inferred from the values
+    volb, occb = semantic_voxelization_batch(torch.from_numpy(vv)[None].to(dev), torch.from_numpy(tets).to(dev), code, res=res, sigma=0.05,
+                                             return_occ=True)
+    assert torch.equal(volb, vol) and np.array_equal(occb[0].cpu().numpy(), occ.astype(np.uint8))
     assert np.abs(got - ref).max() <= 1e-5
     # padded inputs as the dataset delivers them (TestDataset.py:165-170) give the same volume after stripping
     pad_v = np.concatenate([vv, np.zeros((7, 3), np.float32)])
