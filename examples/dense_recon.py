@@ -2,7 +2,7 @@
 """End-to-end on the synthetic subject: what apps/ICON.py:test_single does after netG.filter() (lines 729-761) -
 reconEngine -> export_mesh -> clean_mesh -> vertices into the [-1,1] cube - through the HIP path, with timings.
 
-    python examples/dense_recon.py [--res 257] [--adaptive] [--color] [--out body.obj]
+    python examples/dense_recon.py [--res 257] [--adaptive] [--color] [--normal-maps] [--out body.obj]
 
 Needs an MI355X (there is no CPU path).  The inputs stand in for what the reference computes upstream of the hot path:
 `features` = HGPIFuNet.filter() output, the SMPL tensors = TestDataset.compute_vis_cmap(), the regressor = netG.if_regressor.
@@ -22,6 +22,8 @@ def main():
     ap.add_argument("--adaptive", action="store_true", help="the reference's coarse-to-fine schedule instead of the dense lattice")
     ap.add_argument("--out", default=None, help="write the mesh as Wavefront OBJ")
     ap.add_argument("--color", action="store_true", help="colour the vertices from a synthetic image (query_color, apps/infer.py:531); OBJ lines become v x y z r g b")
+    ap.add_argument("--normal-maps", action="store_true", help="render the cleaned mesh from the four cameras of lib/common/render.py (icon_amd.render) "
+                    "and write the normal maps as <out stem>_normal_<cam>.ppm")
     args = ap.parse_args()
     import torch
     from icon_amd import synth
@@ -66,6 +68,22 @@ def main():
     print(f"{'adaptive' if args.adaptive else 'dense'} {res}^3: volume {1e3 * (t1 - t0):.2f} ms, marching cubes {1e3 * (t2 - t1):.2f} ms, "
           f"clean_mesh {1e3 * (t3 - t2):.2f} ms{color_ms} -> {verts.shape[0]} vertices, {faces.shape[0]} faces, "
           f"bbox {verts.min(0).values.tolist()} .. {verts.max(0).values.tolist()}")
+    if args.normal_maps:
+        import os
+        from icon_amd.render import Render
+        render = Render(size=512, device=dev)
+        render.load_meshes(verts, faces)
+        render.get_rgb_image(cam_ids=[0, 1, 2, 3])                               # warm-up: the call's scratch
+        render.load_meshes(verts, faces)
+        t5 = sync()
+        maps = render.get_rgb_image(cam_ids=[0, 1, 2, 3])                        # four [1,3,512,512] tensors in [-1,1], on the device
+        print(f"render: four 512^2 normal maps in {1e3 * (sync() - t5):.2f} ms (mesh upload included)")
+        stem = os.path.splitext(args.out)[0] if args.out else "dense_recon"
+        for cam, m in enumerate(maps):
+            rgb = ((m[0].permute(1, 2, 0) + 1.0) * 127.5).round().clamp(0, 255).to(torch.uint8).cpu().numpy()
+            with open(f"{stem}_normal_{cam}.ppm", "wb") as fh:
+                fh.write(b"P6\n512 512\n255\n" + rgb.tobytes())
+        print(f"wrote {stem}_normal_0.ppm .. {stem}_normal_3.ppm")
     if args.out:
         v, f = verts.cpu().numpy(), faces.cpu().numpy() + 1
         with open(args.out, "w") as fh:

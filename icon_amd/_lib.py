@@ -37,6 +37,7 @@ SYMBOLS = [
     "icon_mesh_batch_create", "icon_mesh_batch_destroy", "icon_mesh_batch_status", "icon_feat_create_batch", "icon_query_points_batch",
     "icon_feat_batch_set_volume", "icon_semantic_voxelize_batch",
     "icon_query_color_bytes", "icon_query_color",
+    "icon_render_bytes", "icon_render_normal",
 ]
 
 _lib = None

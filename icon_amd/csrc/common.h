@@ -392,6 +392,7 @@ int work_share_dbg(icon_work *w, ShareDbg *out);
 // ICON_ERR_STATE (and the record cleared) if a shared walk of an earlier launch on this workspace reported; no synchronisation
 int work_check_err(icon_work *w);
 extern int g_qc_lanes;                // query_color.hip: lanes per face of the colour call's rasteriser ("qc_lanes"; 0 = default)
+extern int g_rn_lanes;                // render_normal.hip: lanes per face of the renderer's rasteriser ("rn_lanes"; 0 = default)
 int share_waves_override();           // ICON_AMD_SHARE / icon_debug_set_option("share_waves"): -1 = by launch size
 }  // namespace icon
 

@@ -1,0 +1,170 @@
+"""Normal maps and depth maps of a mesh from ICON's four orthographic cameras - the forward renderer.
+
+Replaces ``lib.common.render.Render.load_meshes`` / ``get_rgb_image`` / ``get_depth_map`` (a pytorch3d ``MeshRasterizer`` plus
+``cleanShader``; call sites lib/dataset/TestDataset.py:289-299, apps/ICON.py:387-392, apps/infer.py:423/448/482) by ONE native
+call, ``icon_render_normal`` (csrc/render_normal.hip; the rule is DESIGN.md 4.13).  No pytorch3d involved; there is no CPU path.
+The differentiable uses of the reference's renderer (gradients of the SMPL fit, the soft silhouette), video and point clouds
+are not covered.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import threading
+from typing import Sequence
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import IconAmdError, check
+
+_rn_tls = threading.local()
+
+
+def _rn_scratch(device: torch.device, nbytes: int) -> torch.Tensor:
+    """renderer scratch: one tensor per (thread, device, stream), grown on demand and reused - calls on different streams may
+    run at once and must not share a z-buffer (recon._qc_scratch has the allocator side of the argument)"""
+    pool = getattr(_rn_tls, "pool", None)
+    if pool is None:
+        pool = _rn_tls.pool = {}
+    idx = device.index if device.index is not None else torch.cuda.current_device()
+    key = (idx, torch.cuda.current_stream(idx).cuda_stream)
+    buf = pool.get(key)
+    if buf is None or buf.numel() < nbytes:
+        buf = pool[key] = torch.empty(nbytes, dtype=torch.uint8, device=torch.device("cuda", idx))
+    return buf
+
+
+def _need_device(what: str) -> None:
+    if not torch.cuda.is_available():
+        raise IconAmdError(f"{what} needs the HIP device (there is no CPU fallback)")
+
+
+def _check_cams(cam_ids) -> list:
+    cams = [int(c) for c in cam_ids]
+    if not 1 <= len(cams) <= 4 or any(c < 0 or c > 3 for c in cams):
+        raise IconAmdError(f"render: cam_ids must be 1..4 values in 0..3, got {list(cam_ids)}")
+    return cams
+
+
+def _check_size(size) -> int:
+    if int(size) != size or not 8 <= int(size) <= 2048:
+        raise IconAmdError(f"render: size must be an integer in 8..2048, got {size}")
+    return int(size)
+
+
+def render_normal_device(verts: torch.Tensor, faces: torch.Tensor, cam_ids: Sequence[int] = (0, 2), size: int = 512,
+                         return_depth: bool = False, return_faces: bool = False):
+    """``verts [V,3]`` (float), ``faces [F,3]`` (int32 or int64, read in place), both on one HIP device ->
+    ``images [n,3,size,size]`` float32 in [-1,1] there, view k from camera ``cam_ids[k]`` (0: from +z, 1: from +x, 2: from -z,
+    3: from -x; +y is up, the [-1,1] cube fills the image; background 0), then ``depth [n,size,size]`` (view depth, background
+    -1) with ``return_depth`` and ``pix_to_face [n,size,size]`` int32 (background -1) with ``return_faces``.  With exactly two
+    views the planes of camera 2 are mirrored left-right, as the reference's ``get_rgb_image`` does.  ONE native call enqueued
+    on the current stream: nothing is allocated by it, nothing read back, the stream is not waited for - so a face that names a
+    vertex that does not exist cannot raise here; it is skipped.  The scratch is cached per (thread, device, stream)."""
+    from .engine import _stream
+    cams, size = _check_cams(cam_ids), _check_size(size)
+    if not torch.is_tensor(verts) or verts.dim() != 2 or verts.shape[1] != 3 or verts.shape[0] == 0:
+        raise IconAmdError(f"render: verts must be a [V,3] tensor, got {tuple(getattr(verts, 'shape', ()))}")
+    if not torch.is_tensor(faces) or faces.dim() != 2 or faces.shape[1] != 3 or faces.shape[0] == 0:
+        raise IconAmdError(f"render: faces must be a [F,3] tensor, got {tuple(getattr(faces, 'shape', ()))}")
+    if faces.dtype.is_floating_point or faces.dtype == torch.bool:
+        raise IconAmdError(f"render: faces must be an integer tensor, got {faces.dtype}")
+    _need_device("render_normal_device")
+    if not (verts.is_cuda and faces.is_cuda) or verts.device != faces.device:
+        raise IconAmdError("render_normal_device: verts and faces must live on one HIP device (Render.load_meshes moves host data)")
+    dev = verts.device
+    v = verts.detach().to(torch.float32).contiguous()
+    f = faces.detach()
+    if f.dtype not in (torch.int32, torch.int64):
+        f = f.to(torch.int64)
+    f = f.contiguous()
+    n = len(cams)
+    L = _lib.lib()
+    with torch.cuda.device(dev):
+        nbytes = C.c_int64(0)
+        check(L.icon_render_bytes(C.c_int64(v.shape[0]), C.c_int64(f.shape[0]), C.c_int(size), C.c_int(n), C.byref(nbytes)), "icon_render_bytes")
+        scratch = _rn_scratch(dev, nbytes.value)
+        images = torch.empty((n, 3, size, size), dtype=torch.float32, device=dev)
+        depth = torch.empty((n, size, size), dtype=torch.float32, device=dev) if return_depth else None
+        pix = torch.empty((n, size, size), dtype=torch.int32, device=dev) if return_faces else None
+        check(L.icon_render_normal(_lib.ptr(v), C.c_int64(v.shape[0]), _lib.ptr(f), C.c_int64(f.shape[0]), C.c_int(1 if f.dtype == torch.int64 else 0),
+                                   (C.c_int * n)(*cams), C.c_int(n), C.c_int(size), _lib.ptr(images), _lib.ptr(depth), _lib.ptr(pix),
+                                   _lib.ptr(scratch), C.c_int64(scratch.numel()), _stream()), "icon_render_normal")
+    out = (images,) + ((depth,) if return_depth else ()) + ((pix,) if return_faces else ())
+    return out if len(out) > 1 else images
+
+
+class Render:
+    """Drop-in for the forward uses of ``lib.common.render.Render``::
+
+        render = Render(size=512, device=torch.device("cuda:0"))
+        render.load_meshes(verts, faces)
+        T_normal_F, T_normal_B = render.get_rgb_image()          # [1,3,S,S] each, in [-1,1]
+        depth_F, depth_B = render.get_depth_map(cam_ids=[0, 2])   # [S,S] each
+
+    The maps of one set of cameras are rendered once per ``load_meshes`` (one native call gives images and depths); the
+    tensors handed out are views of that result."""
+
+    def __init__(self, size: int = 512, device=None):
+        self.size = _check_size(size)
+        self.device = torch.device(device) if device is not None else torch.device("cuda")
+        if self.device.type != "cuda":
+            raise IconAmdError(f"Render: device must be a HIP device, got {self.device} (there is no CPU fallback)")
+        self.meshes = None
+        self._cache = {}
+
+    def _device(self) -> torch.device:
+        _need_device("Render")
+        return self.device if self.device.index is not None else torch.device("cuda", torch.cuda.current_device())
+
+    def load_meshes(self, verts, faces) -> None:
+        """``verts [V,3]`` / ``faces [F,3]``: tensors or arrays, on the host or the device (a leading batch axis of 1 is dropped).
+        Lists are taken element by element, as the reference does; element 0 is what the get_* calls render."""
+        dev = self._device()
+        if not isinstance(verts, (list, tuple)):
+            verts, faces = [verts], [faces]
+        meshes = []
+        for v, f in zip(verts, faces):
+            v = torch.as_tensor(np.asarray(v) if not torch.is_tensor(v) else v)
+            f = torch.as_tensor(np.asarray(f) if not torch.is_tensor(f) else f)
+            if v.dim() == 3 and v.shape[0] == 1:
+                v = v[0]
+            if f.dim() == 3 and f.shape[0] == 1:
+                f = f[0]
+            if f.dtype.is_floating_point or f.dtype == torch.bool:
+                raise IconAmdError(f"render: faces must be an integer tensor, got {f.dtype}")
+            meshes.append((v.detach().to(dev, torch.float32), f.detach().to(dev) if f.dtype in (torch.int32, torch.int64) else f.detach().to(dev, torch.int64)))
+        self.meshes = meshes
+        self._cache = {}
+
+    def _render(self, cams: tuple):
+        _need_device("Render")
+        if not self.meshes:
+            raise IconAmdError("Render: load_meshes has not been called")
+        if cams not in self._cache:
+            v, f = self.meshes[0]
+            self._cache[cams] = render_normal_device(v, f, cams, self.size, return_depth=True)
+        return self._cache[cams]
+
+    def get_rgb_image(self, cam_ids=[0, 2]):
+        """-> one ``[1,3,S,S]`` tensor per requested camera, in ascending camera order (the reference walks its camera list and
+        keeps the requested ones); camera 2 is mirrored left-right when ``len(cam_ids) == 2``"""
+        _check_cams(cam_ids)
+        cams = tuple(c for c in range(4) if c in [int(x) for x in cam_ids])
+        images, _ = self._render(cams)
+        out = [images[k:k + 1] for k in range(len(cams))]
+        if (len(cam_ids) == 2) != (len(cams) == 2) and 2 in cams:          # duplicates in cam_ids: the native call decided by its own count
+            k = cams.index(2)
+            out[k] = torch.flip(out[k], dims=[3])
+        return out
+
+    def get_depth_map(self, cam_ids=[0, 2]):
+        """-> one ``[S,S]`` tensor per entry of ``cam_ids``, in that order; camera 2 is ALWAYS mirrored left-right (the
+        reference's get_depth_map does not look at the number of views)"""
+        cams = tuple(_check_cams(cam_ids))
+        _, depth = self._render(cams)
+        out = [depth[k] for k in range(len(cams))]
+        if len(cams) != 2:
+            out = [torch.fliplr(d) if c == 2 else d for c, d in zip(cams, out)]
+        return out

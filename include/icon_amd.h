@@ -384,7 +384,9 @@ int icon_debug_set_shell_skip(int on);
  * ring size of the shared walks' hand-over queue; "share_lose_push" (0 = none): ticket of the push that is announced but never
  * stored; "share_spin_log2" (0 = 18): the wait bound, 2^n polls - the torture / fault-injection tests of the error path below.
  * "qc_lanes" (0 = 8, the default mapping): 64 makes icon_query_color's rasteriser sweep a face with one whole wavefront,
- * icon_visibility's mapping - tools/time_query_color.py times the two against each other; the result does not depend on it. */
+ * icon_visibility's mapping - tools/time_query_color.py times the two against each other; the result does not depend on it.
+ * "rn_lanes" (0 = the default: chosen from F and the image size): 8 makes icon_render_normal's rasteriser sweep a face's pixel box with eight lanes, 1 with
+ * one thread - tools/time_render.py times the two against each other; the result does not depend on it. */
 int icon_debug_set_option(const char *key, int value);
 /* The searches of coarse lattices and of the adaptive schedule share one packet's BVH walk between the wavefronts of a
  * workgroup through an LDS queue (csrc/geom_device.h nearest_shared).  Every wait in that hand-over is bounded; a wave that
@@ -515,6 +517,24 @@ int icon_query_color_bytes(int64_t V, int64_t F, int image_size, int64_t *bytes)
 int icon_query_color(const float *d_verts, int64_t V, const void *d_faces, int64_t F, int faces_int64,
                      const float *d_image, int H, int W, int image_size, float *d_colors, float *d_vis,
                      void *d_scratch, int64_t scratch_bytes, void *stream);
+
+/* ---- normal maps and depth maps of a mesh (the forward renderer) -------------------------------------
+ * replaces Render.get_rgb_image / get_depth_map (lib/common/render.py:289-325: pytorch3d MeshRasterizer with
+ * blur_radius = log(1/1e-4) * 1e-7 and 30 faces per pixel, vertex-normal textures, softmax blend with gamma = 1e-8) for the
+ * four orthographic cameras of Render.load_meshes: cam 0 looks from +z, 1 from +x, 2 from -z, 3 from -x, +y is up, the
+ * [-1,1] cube fills the image.  The blend is replaced by its limit, the nearest candidate (PARITY UNPINNED).
+ * d_verts [V,3] f32; d_faces [F,3], int64 when faces_int64 != 0, else int32 - read in place; cam_ids: n_views (1..4) HOST
+ * values 0..3; size: 8..2048.  d_images [n_views,3,size,size] f32 out in [-1,1], background 0; d_depth [n_views,size,size]
+ * f32 out (view depth 100 -+ coordinate, background -1) or NULL; d_pix_to_face [n_views,size,size] int32 out (background -1)
+ * or NULL.  With exactly two views the planes of cam 2 are mirrored left-right, as the reference does.  A face that names a
+ * vertex that does not exist is skipped and counted: after the stream has been waited for, the first int32 of the scratch
+ * holds the number of such faces.  d_scratch: device memory of at least icon_render_bytes(V, F, size, n_views) bytes,
+ * 256-byte aligned, owned by the caller.  Enqueued on `stream`: no allocation, no synchronisation, nothing read back;
+ * results are bit-identical from run to run. */
+int icon_render_bytes(int64_t V, int64_t F, int size, int n_views, int64_t *bytes);
+int icon_render_normal(const float *d_verts, int64_t V, const void *d_faces, int64_t F, int faces_int64,
+                       const int *cam_ids, int n_views, int size, float *d_images, float *d_depth, int32_t *d_pix_to_face,
+                       void *d_scratch, int64_t scratch_bytes, void *stream);
 
 #ifdef __cplusplus
 }

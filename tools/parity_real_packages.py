@@ -277,6 +277,26 @@ def sec_visibility(S, their_visibility, name):
            + ("" if nd == 0 else " - class: pixel-centre / top-left fill rule or depth ties of the 4096^2 rasteriser (oracle/icon_oracle.c: orc_visibility)"))
 
 
+def sec_render(S, their_render, name, size=128, cams=(0, 2)):
+    """lib/common/render.py:289-325 (Render.get_rgb_image / get_depth_map) against icon_amd.render.  The native call takes the
+    nearest candidate where the package blends softly: PASS means the conditions that section measures its rule
+    by - pixels only one side covers and pixels beyond 4 x 6.12e-4 (colour) / 4 x 1.83e-5 (depth) each at most 0.5 % of the covered ones."""
+    from icon_amd.render import render_normal_device
+    verts, faces = S.verts[0].float().contiguous(), S.faces[0].long().contiguous()
+    img, dep = render_normal_device(verts, faces, cams, size, return_depth=True)
+    ours_i, ours_d = img.cpu().numpy().astype(np.float64), dep.cpu().numpy().astype(np.float64)
+    their_i, their_d = (np.asarray(a, np.float64) for a in their_render(verts.cpu().numpy(), faces.cpu().numpy(), cams, size))
+    co, ct = ours_d >= 0, their_d >= 0
+    both = co & ct
+    covered = int(co.sum())
+    dc, dd = np.abs(ours_i - their_i).max(1), np.abs(ours_d - their_d)
+    n_cov, n_c, n_d = int((co != ct).sum()), int((both & (dc > 4 * 6.12e-4)).sum()), int((both & (dd > 4 * 1.83e-5)).sum())
+    ok = covered > 0 and max(n_cov, n_c, n_d) <= 0.005 * covered
+    report(name + " Render.get_rgb_image / get_depth_map", "PASS" if ok else "DIFF",
+           f"{size}^2 x {len(cams)} views, {covered} covered pixels: {n_cov} covered by one side only, {n_c} colour / {n_d} depth outliers; largest difference on the "
+           f"common pixels colour {dc[both].max():.2e}, depth {dd[both].max():.2e}" + ("" if ok else " - class: camera convention / blur band / blend"))
+
+
 def sec_voxelize(S, their_voxelize, name):
     """lib/net/voxelize.py:57-59,119-137"""
     from icon_amd import synth
@@ -344,6 +364,10 @@ def main():
         if want("pytorch3d"):
             sec_vertex_normals(subject(), lambda v, f: torch.from_numpy(orc.vertex_normals(v[0].cpu().numpy(), f[0].cpu().numpy())), tag)
             sec_visibility(subject(), lambda xy, z, f: torch.from_numpy(orc.visibility(xy.cpu().numpy(), z.cpu().numpy().reshape(-1), f.cpu().numpy(), 4096)), tag)
+        if want("render"):
+            sys.path.insert(0, os.path.join(ROOT, "tests"))
+            import render_checker                                        # pytorch3d's pipeline restated in float64
+            sec_render(subject(), lambda v, f, cams, size: (lambda r: (r[2], r[1]))(render_checker.render_blend_f64(v, f, cams, size)), tag)
 
         def classic(final):
             v, f = mc_classic.marching_cubes(final.cpu().numpy(), 0.5)
@@ -397,6 +421,7 @@ def main():
                     return np.asarray(best.vertices, np.float32), np.asarray(best.faces, np.int32)
                 sec_clean_mesh(subject(), split_largest, f"trimesh {t.__version__}")
         # ---- pytorch3d --------------------------------------------------------------------------------------------
+        p3 = None
         if want("pytorch3d"):
             def imp():
                 import pytorch3d
@@ -419,6 +444,38 @@ def main():
                     vis[ids.cpu()] = 1.0
                     return vis
                 sec_visibility(subject(), their_vis, name)
+        # the renderer row belongs to the pytorch3d section: where the package is absent its ABSENT line covers this row too
+        # (asked for by name, --only render, the row reports for itself)
+        if want("render") and ("render" in only or p3):
+            def imp():
+                import pytorch3d
+                import pytorch3d.renderer as R
+                from pytorch3d.structures import Meshes
+                return pytorch3d, R, Meshes
+            pr = load("pytorch3d (renderer)", imp)
+            if pr:
+                import torch
+
+                def their_render(v, f, cams, size):                      # render.py:136-168,228-258,289-325 - the settings of Render, written out
+                    R, dev = pr[1], torch.device("cuda:0")
+                    mesh = pr[2](torch.from_numpy(v)[None].to(dev), torch.from_numpy(f)[None].to(dev))
+                    mesh.textures = R.TexturesVertex(verts_features=(mesh.verts_normals_padded() + 1.0) * 0.5)
+                    eyes = [(0, 0, 100.0), (100.0, 0, 0), (0, 0, -100.0), (-100.0, 0, 0)]
+                    images, depths = [], []
+                    for cam in cams:
+                        Rm, T = R.look_at_view_transform(eye=[eyes[cam]], at=((0, 0, 0),), up=((0, 1, 0),))
+                        camera = R.FoVOrthographicCameras(device=dev, R=Rm, T=T, znear=100.0, zfar=-100.0, max_y=100.0, min_y=-100.0, max_x=100.0,
+                                                          min_x=-100.0, scale_xyz=(100.0 * np.ones(3),))
+                        ras = R.MeshRasterizer(cameras=camera, raster_settings=R.RasterizationSettings(image_size=size, blur_radius=np.log(1.0 / 1e-4) * 1e-7,
+                                                                                                        faces_per_pixel=30))
+                        frag = ras(mesh)
+                        rgb = R.blending.softmax_rgb_blend(mesh.sample_textures(frag), frag, R.BlendParams(1e-4, 1e-8, (0.5, 0.5, 0.5)), znear=-256, zfar=256)
+                        im, de = (rgb[0, :, :, :3].permute(2, 0, 1) - 0.5) * 2.0, frag.zbuf[0, :, :, 0]
+                        if cam == 2 and len(cams) == 2:
+                            im, de = torch.flip(im, dims=[2]), torch.fliplr(de)
+                        images.append(im.cpu().numpy()); depths.append(de.cpu().numpy())
+                    return np.stack(images), np.stack(depths)
+                sec_render(subject(), their_render, f"pytorch3d {pr[0].__version__}")
         # ---- voxelize_cuda ----------------------------------------------------------------------------------------
         if want("voxelize_cuda"):
             def imp():
