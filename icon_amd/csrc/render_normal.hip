@@ -18,16 +18,16 @@
 // tests/render_checker.py render_f32 states the same expressions in numpy: face ids, depths and colours are compared for equality.
 //
 // Shape of the work: one stream-ordered call; every buffer lives in the caller's scratch (icon_render_bytes); nothing is
-// allocated, read back or waited for.  The S1 normals of ALL vertices come from the count / scan / fill / ordered-add scheme
-// of query_color.hip - a private copy here (that file computes them only where a vertex is hidden and writes colours; shared
-// through a header its kernels would have to be re-instantiated around a policy parameter, which changes query_color.o).
+// allocated, read back or waited for.  The S1 normals of ALL vertices come from the count / scan / fill / ordered-add kernels
+// of s1_normals_device.h (shared with query_color.hip, which computes them only where a vertex is hidden: S1Ctx::vis is null here);
+// this file keeps the per-vertex kernel of the short lists and the functor that stores a normal into the scratch.
 // One raster launch covers every requested view (blockIdx.y); kRnLanes lanes - or one thread - sweep the pixel centres of a
 // face's box and atomicMin the 64-bit key into the view's S x S z-buffer; a box above 64 pixels per lane is appended to a
 // device-side list that a fixed grid of workgroups consumes.  The resolve pass recomputes the winner's clamped barycentrics
 // with the same function and writes colour, depth and face id, the cam-2 left-right flip of the two-view call in the store address.
 #pragma clang fp contract(off)
 
-#include "common.h"
+#include "s1_normals_device.h"
 
 namespace icon {
 
@@ -38,25 +38,17 @@ namespace {
 constexpr int kRnLanes = 8;          // lanes per face of the rasteriser while faces are large; one thread per face otherwise (rn_launch)
 constexpr int kRnBigPerLane = 64;    // a bounding box of more than this many pixels per lane goes to the deferred list
 constexpr int kRnBigGrid = 1024;     // workgroups (256 lanes, one deferred face at a time each)
-constexpr int kRnShort = 32;         // incidence lists up to this length are summed by one thread
-constexpr int kRnLongGrid = 256;     // wavefronts consuming the long lists
-constexpr int kRnScanItems = 1024;   // vertices per block of the scan (256 threads x 4)
 constexpr float kRnBlur = 9.210340295e-07f;     // float32(log(1 / 1e-4) * 1e-7): squared NDC distance
 constexpr float kRnBlurR = 9.597051539e-04f;    // float32 sqrt of it: the bounding box grows by this
 constexpr float kRnEps = 1e-8f;                 // pytorch3d's kEpsilon
 
 struct RnHdr { int bad_faces, n_big, n_long, pad; };
 
-struct RnCtx {
-    const float *verts; const void *faces;
-    int64_t V, F;
+struct RnCtx : S1Ctx {               // the mesh and the normals' scratch (vis null: every vertex gets a normal), and
     int S, n_views, cams, flip;      // cams: 2 bits per view; flip: the two-view call mirrors cam 2 left-right
     float *images, *depth; int *pix;
     RnHdr *hdr;
-    int *deg, *cur;                  // [V] incidence count / fill cursor
-    int *loc, *part;                 // scan: exclusive prefix inside each kRnScanItems block, exclusive prefix of the block totals
-    int *inc, *tmp;                  // [3F] incidence keys 3 f + corner, grouped by vertex; tmp: the long lists, sorted
-    int *big, *longv;                // deferred (view << 29 | face) [n_views F], long-list vertices [V]
+    int *big;                        // deferred (view << 29 | face) [n_views F]
     float *nrm;                      // [V][3] S1 normals
     unsigned long long *zb;          // [n_views][S][S], image orientation
 };
@@ -83,14 +75,6 @@ __device__ __forceinline__ float rn_seg(float px, float py, float ax, float ay, 
     return ex * ex + ey * ey;
 }
 
-template <class IT>
-__device__ __forceinline__ bool rn_face(const RnCtx &c, int64_t f, int64_t v[3])
-{
-    const IT *fp = static_cast<const IT *>(c.faces) + 3 * f;
-    v[0] = (int64_t)fp[0]; v[1] = (int64_t)fp[1]; v[2] = (int64_t)fp[2];
-    return v[0] >= 0 && v[0] < c.V && v[1] >= 0 && v[1] < c.V && v[2] >= 0 && v[2] < c.V;
-}
-
 struct RnRast {
     float X[3], Y[3], D[3];
     float xlo, xhi, ylo, yhi, den;   // the bounding box grown by kRnBlurR; area + eps
@@ -102,7 +86,7 @@ struct RnRast {
 template <class IT>
 __device__ __forceinline__ bool rn_setup(const RnCtx &c, int cam, int64_t f, RnRast &r)
 {
-    if (!rn_face<IT>(c, f, r.id)) return false;
+    if (!s1_face<IT>(c, f, r.id)) return false;
     const bool side = (cam & 1) != 0, neg = (cam == 0 || cam == 3), front = cam < 2;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
@@ -239,160 +223,27 @@ __global__ __launch_bounds__(256) void k_rn_resolve(RnCtx c)
     if (c.pix) c.pix[at] = face;
 }
 
-// ---- S1 vertex normals of every vertex: incident faces in ascending 3 face + corner order (query_color.hip's scheme) ----
-template <class IT>
-__global__ __launch_bounds__(256) void k_rn_count(RnCtx c)
-{
-    const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (f >= c.F) return;
-    int64_t v[3];
-    if (!rn_face<IT>(c, f, v)) { atomicAdd(&c.hdr->bad_faces, 1); return; }
-#pragma unroll
-    for (int k = 0; k < 3; ++k) atomicAdd(&c.deg[v[k]], 1);
-}
-
-__device__ __forceinline__ int rn_wave_incl_scan(int v)
-{
-    const int lane = threadIdx.x & 63;
-    for (int d = 1; d < 64; d <<= 1) { const int o = __shfl_up(v, d); if (lane >= d) v += o; }
-    return v;
-}
-// exclusive prefix of v over the workgroup (NW wavefronts); total: the workgroup's sum
-template <int NW>
-__device__ __forceinline__ int rn_block_excl_scan(int v, int *s_w, int &total)
-{
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int incl = rn_wave_incl_scan(v);
-    if (lane == 63) s_w[w] = incl;
-    __syncthreads();
-    int before = 0, all = 0;
-    for (int q = 0; q < NW; ++q) { const int t = s_w[q]; before += q < w ? t : 0; all += t; }
-    __syncthreads();
-    total = all;
-    return before + incl - v;
-}
-
-__global__ __launch_bounds__(256) void k_rn_scan_blocks(RnCtx c)
-{
-    __shared__ int s_w[4];
-    const int64_t i0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
-    int d[4], sum = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) { d[k] = i0 + k < c.V ? c.deg[i0 + k] : 0; sum += d[k]; }
-    int total;
-    int run = rn_block_excl_scan<4>(sum, s_w, total);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) { if (i0 + k < c.V) c.loc[i0 + k] = run; run += d[k]; }
-    if (threadIdx.x == 0) c.part[blockIdx.x] = total;
-}
-
-__global__ __launch_bounds__(1024) void k_rn_scan_parts(RnCtx c, int nb)
-{
-    __shared__ int s_w[16];
-    int carry = 0;
-    for (int base = 0; base < nb; base += 1024) {
-        const int i = base + threadIdx.x;
-        const int v = i < nb ? c.part[i] : 0;
-        int total;
-        const int ex = rn_block_excl_scan<16>(v, s_w, total);
-        if (i < nb) c.part[i] = carry + ex;
-        carry += total;
+// a normal into the scratch: n = s / max(|s|, 1e-6)
+struct RnStore {
+    float *nrm;
+    __device__ void operator()(int64_t v, float x, float y, float z) const
+    {
+        s1_normalise(x, y, z);
+        nrm[3 * v] = x; nrm[3 * v + 1] = y; nrm[3 * v + 2] = z;
     }
-}
+};
 
-__device__ __forceinline__ int rn_start(const RnCtx &c, int64_t v) { return c.loc[v] + c.part[v / kRnScanItems]; }
-
-template <class IT>
-__global__ __launch_bounds__(256) void k_rn_fill(RnCtx c)
-{
-    const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (f >= c.F) return;
-    int64_t v[3];
-    if (!rn_face<IT>(c, f, v)) return;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const int64_t at = (int64_t)rn_start(c, v[k]) + atomicAdd(&c.cur[v[k]], 1);
-        if (at >= 0 && at < 3 * c.F) c.inc[at] = (int)(3 * f + k);          // always true after the call's own clear; never trusted
-    }
-}
-
-// (v1 - v0) x (v2 - v0) of the face behind an incidence key (S1)
-template <class IT>
-__device__ __forceinline__ void rn_face_normal(const RnCtx &c, int key, float n[3])
-{
-    int64_t v[3];
-    n[0] = n[1] = n[2] = 0.0f;
-    if (key < 0 || key / 3 >= c.F || !rn_face<IT>(c, key / 3, v)) return;   // listed faces passed the index check
-    const float *a = c.verts + 3 * v[0], *b = c.verts + 3 * v[1], *d = c.verts + 3 * v[2];
-    const float ux = b[0] - a[0], uy = b[1] - a[1], uz = b[2] - a[2];
-    const float vx = d[0] - a[0], vy = d[1] - a[1], vz = d[2] - a[2];
-    n[0] = fmaf(uy, vz, -(uz * vy)); n[1] = fmaf(uz, vx, -(ux * vz)); n[2] = fmaf(ux, vy, -(uy * vx));
-}
-
-__device__ __forceinline__ void rn_store_normal(const RnCtx &c, int64_t v, float x, float y, float z)
-{
-    float len = sqrtf(fmaf(z, z, fmaf(y, y, x * x)));
-    if (len < 1e-6f) len = 1e-6f;
-    c.nrm[3 * v] = x / len; c.nrm[3 * v + 1] = y / len; c.nrm[3 * v + 2] = z / len;
-}
-
-// one thread per vertex: a short incidence list in ascending key order by selection; a long one goes to the second list
+// one thread per vertex: the normal of a short incidence list; a long one goes to k_s1_normals_long's list
 template <class IT>
 __global__ __launch_bounds__(256) void k_rn_normals(RnCtx c)
 {
     const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (v >= c.V) return;
     const int n = c.deg[v];
-    if (n > kRnShort) {                                                    // at most V entries
-        const int at = atomicAdd(&c.hdr->n_long, 1);
-        if ((int64_t)at < c.V) c.longv[at] = (int)v;
-        return;
-    }
-    const int64_t st = rn_start(c, v);
-    if (n < 0 || st < 0 || st + n > 3 * c.F) return;
-    const int *list = c.inc + st;
-    float sx = 0.0f, sy = 0.0f, sz = 0.0f;
-    int last = -1;
-    for (int step = 0; step < n; ++step) {
-        int best = 0x7fffffff;
-        for (int q = 0; q < n; ++q) { const int k = list[q]; if (k > last && k < best) best = k; }
-        float fn[3];
-        rn_face_normal<IT>(c, best, fn);
-        sx += fn[0]; sy += fn[1]; sz += fn[2];
-        last = best;
-    }
-    rn_store_normal(c, v, sx, sy, sz);
-}
-
-// the long lists: one wavefront per vertex - rank-sort the keys into tmp, then add the face normals in that order
-template <class IT>
-__global__ __launch_bounds__(64) void k_rn_normals_long(RnCtx c)
-{
-    const int nl = (int)min((int64_t)c.hdr->n_long, c.V);
-    const int lane = threadIdx.x;
-    for (int e = blockIdx.x; e < nl; e += gridDim.x) {
-        const int64_t v = c.longv[e];
-        if (v < 0 || v >= c.V) continue;
-        const int n = c.deg[v], st = rn_start(c, v);
-        if (n < 0 || st < 0 || (int64_t)st + n > 3 * c.F) continue;
-        const int *list = c.inc + st;
-        for (int i = lane; i < n; i += 64) {
-            const int key = list[i];
-            int rank = 0;
-            for (int q = 0; q < n; ++q) rank += list[q] < key ? 1 : 0;     // keys are distinct
-            c.tmp[st + rank] = key;
-        }
-        __threadfence();                                                   // the wave's own stores, read back by other lanes below
-        float sx = 0.0f, sy = 0.0f, sz = 0.0f;
-        for (int base = 0; base < n; base += 64) {
-            const int i = base + lane;
-            float fn[3] = { 0.0f, 0.0f, 0.0f };
-            if (i < n) rn_face_normal<IT>(c, __hip_atomic_load(&c.tmp[st + i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), fn);
-            const int cnt = min(64, n - base);
-            for (int l = 0; l < cnt; ++l) { sx += __shfl(fn[0], l); sy += __shfl(fn[1], l); sz += __shfl(fn[2], l); }
-        }
-        if (lane == 0) rn_store_normal(c, v, sx, sy, sz);
-    }
+    if (n > kShort) { s1_defer_long(c, v); return; }
+    float s[3];
+    s1_sum_short<IT>(c, v, n, s);
+    RnStore{c.nrm}(v, s[0], s[1], s[2]);
 }
 
 // the call's clears: [0, zero_end) of the scratch to 0, the z-buffers to ~0 - a kernel like the others, so that a captured call
@@ -415,7 +266,7 @@ RnLayout rn_layout(int64_t V, int64_t F, int S, int n_views)
     auto take = [&](size_t bytes) { const size_t at = o; o = (o + bytes + 255) / 256 * 256; return at; };
     L.hdr = take(sizeof(RnHdr)); L.deg = take((size_t)V * 4); L.cur = take((size_t)V * 4);
     L.zero_end = o;                                                        // [0, zero_end): cleared by one memset per call
-    L.loc = take((size_t)V * 4); L.part = take((size_t)((V + kRnScanItems - 1) / kRnScanItems) * 4);
+    L.loc = take((size_t)V * 4); L.part = take((size_t)((V + kScanItems - 1) / kScanItems) * 4);
     L.inc = take((size_t)F * 12); L.tmp = take((size_t)F * 12);
     L.big = take((size_t)F * 4 * n_views); L.longv = take((size_t)V * 4);
     L.nrm = take((size_t)V * 12);
@@ -436,7 +287,7 @@ template <class IT>
 void rn_launch(const RnCtx &c, hipStream_t st)
 {
     const unsigned gF = (unsigned)((c.F + 255) / 256), gV = (unsigned)((c.V + 255) / 256);
-    const int nb = (int)((c.V + kRnScanItems - 1) / kRnScanItems);
+    const int nb = (int)((c.V + kScanItems - 1) / kScanItems);
     // default mapping by the sizes alone (no read-back): eight lanes per face while a face covers many pixels (the SMPL body: 19 pixels
     // of a 512^2 image per face), one thread per face once 8 F exceeds the pixel count (marching-cubes meshes: under 2) - DESIGN.md 4.13
     const int G = g_rn_lanes == 1 ? 1 : (g_rn_lanes == 8 ? 8 : (8 * c.F > (int64_t)c.S * c.S ? 1 : kRnLanes));
@@ -444,12 +295,13 @@ void rn_launch(const RnCtx &c, hipStream_t st)
     if (G == 1) hipLaunchKernelGGL((k_rn_raster<IT, 1>), gR, dim3(256), 0, st, c);
     else hipLaunchKernelGGL((k_rn_raster<IT, 8>), gR, dim3(256), 0, st, c);
     hipLaunchKernelGGL(k_rn_raster_big<IT>, dim3(kRnBigGrid), dim3(256), 0, st, c);
-    hipLaunchKernelGGL(k_rn_count<IT>, dim3(gF), dim3(256), 0, st, c);
-    hipLaunchKernelGGL(k_rn_scan_blocks, dim3((unsigned)nb), dim3(256), 0, st, c);
-    hipLaunchKernelGGL(k_rn_scan_parts, dim3(1), dim3(1024), 0, st, c, nb);
-    hipLaunchKernelGGL(k_rn_fill<IT>, dim3(gF), dim3(256), 0, st, c);
+    const S1Ctx &s1 = c;                                                   // the shared kernels take the base alone
+    hipLaunchKernelGGL(k_s1_count<IT>, dim3(gF), dim3(256), 0, st, s1);
+    hipLaunchKernelGGL(k_s1_scan_blocks, dim3((unsigned)nb), dim3(256), 0, st, s1);
+    hipLaunchKernelGGL(k_s1_scan_parts, dim3(1), dim3(1024), 0, st, s1, nb);
+    hipLaunchKernelGGL(k_s1_fill<IT>, dim3(gF), dim3(256), 0, st, s1);
     hipLaunchKernelGGL(k_rn_normals<IT>, dim3(gV), dim3(256), 0, st, c);
-    hipLaunchKernelGGL(k_rn_normals_long<IT>, dim3(kRnLongGrid), dim3(64), 0, st, c);
+    hipLaunchKernelGGL((k_s1_normals_long<IT, RnStore>), dim3(kLongGrid), dim3(64), 0, st, s1, RnStore{c.nrm});
     hipLaunchKernelGGL(k_rn_resolve<IT>, dim3((unsigned)((c.S * c.S + 255) / 256), (unsigned)c.n_views), dim3(256), 0, st, c);
 }
 
@@ -487,7 +339,8 @@ extern "C" int icon_render_normal(const float *d_verts, int64_t V, const void *d
     RnCtx c{};
     c.verts = d_verts; c.faces = d_faces; c.V = V; c.F = F; c.S = size; c.n_views = n_views; c.cams = cams; c.flip = n_views == 2 ? 1 : 0;
     c.images = d_images; c.depth = d_depth; c.pix = d_pix_to_face;
-    c.hdr = reinterpret_cast<RnHdr *>(s + L.hdr); c.deg = reinterpret_cast<int *>(s + L.deg); c.cur = reinterpret_cast<int *>(s + L.cur);
+    c.hdr = reinterpret_cast<RnHdr *>(s + L.hdr); c.bad_faces = &c.hdr->bad_faces; c.n_long = &c.hdr->n_long;
+    c.deg = reinterpret_cast<int *>(s + L.deg); c.cur = reinterpret_cast<int *>(s + L.cur);
     c.loc = reinterpret_cast<int *>(s + L.loc); c.part = reinterpret_cast<int *>(s + L.part);
     c.inc = reinterpret_cast<int *>(s + L.inc); c.tmp = reinterpret_cast<int *>(s + L.tmp); c.big = reinterpret_cast<int *>(s + L.big);
     c.longv = reinterpret_cast<int *>(s + L.longv); c.nrm = reinterpret_cast<float *>(s + L.nrm);

@@ -128,6 +128,32 @@ def test_gpu_query_color_high_valence_vertex_is_summed_in_order():
     assert np.array_equal(got[1:1501], want[1:1501])
 
 
+@pytest.mark.parametrize("n", [31, 32, 33, 64, 65])
+def test_gpu_query_color_apex_valence_around_the_short_and_long_list_switch(n):
+    """the fan with an apex of valence n (hidden behind the cap at each of these sizes, by the checker): 32 entries are the longest
+    list one thread sums, 33 the shortest a wavefront rank-sorts; 64 fill the wavefront's one round of adding, 65 start a second.
+    Apex and rim equal the S1 normals' colours byte for byte, for int64 and int32 faces; the rest as the checker has it."""
+    from icon_amd.recon import query_color_device
+    v, f = cc.fan(n)
+    assert (f == 0).sum() == n and (f[:n, 0] == 0).all()
+    image = cc.make_image()
+    want, want_vis = cc.checker_query_color(v, f, image)
+    assert not want_vis[:n + 1].any() and want_vis.any()                    # apex and rim hidden, the cap's vertices sampled
+    colors, vis = query_color_device(_dev(v), _dev(f), image.cuda(), return_vis=True)
+    c32 = query_color_device(_dev(v), _dev(f, torch.int32), image.cuda())
+    got = colors.cpu().numpy()
+    assert np.array_equal(vis.cpu().numpy(), want_vis)
+    normal = ((torch.from_numpy(orc.vertex_normals(v, f)) + 1.0) * 0.5 * 255.0).numpy()
+    assert np.array_equal(got[0], normal[0]), (got[0], normal[0])
+    assert np.array_equal(got[1:n + 1], normal[1:n + 1])
+    assert got.tobytes() == c32.cpu().numpy().tobytes()
+    hidden = want_vis == 0
+    assert np.array_equal(got[hidden], want.numpy()[hidden])
+    d = float(np.abs(got[~hidden].astype(np.float64) - want.numpy()[~hidden]).max())
+    print(f"fan({n}): sampled branch max |device - checker| = {d:.3e} (bar {cc.SAMPLED_GPU_BAR:.2e})")
+    assert d <= cc.SAMPLED_GPU_BAR
+
+
 def test_gpu_query_color_raster_mappings_agree():
     """the A/B switch of tools/time_query_color.py: 8 lanes per face (the default) and one wavefront per face give the same bytes (the z-buffer key does not depend
     on who rasterises a face)"""

@@ -52,6 +52,22 @@ def test_gpu_render_equals_the_float32_rule(name):
         _set_lanes(0)
 
 
+@pytest.mark.parametrize("n", [31, 32, 33, 64, 65])
+def test_gpu_render_apex_valence_around_the_short_and_long_list_switch(n):
+    """the fan with an apex of valence n: 32 entries are the longest list one thread sums, 33 the shortest a wavefront rank-sorts;
+    64 fill the wavefront's one round of adding, 65 start a second.  Front and back view (the back view looks at the fan: the
+    apex normal colours its faces) against the float32 rule, for equality"""
+    import color_checker as cc
+    v, f = cc.fan(n)
+    assert (f == 0).sum() == n
+    pix, depth, image = rc.render_f32(v, f, (0, 2), 64)
+    got = _render(v, f, (0, 2), 64)
+    assert (pix[1] >= 0).any() and (pix[1][pix[1] >= 0] < n).any()          # the back view shows fan faces
+    assert np.array_equal(got[0], pix)
+    assert got[1].tobytes() == depth.tobytes()
+    assert got[2].tobytes() == image.tobytes()
+
+
 def test_gpu_render_skips_and_counts_bad_faces():
     """the C entry itself: the face naming vertex V is skipped and counted in the first word of the scratch; the result is the
     icosphere's, rendered without the three extra faces"""

@@ -120,7 +120,7 @@ def main():
                     t = getattr(ev, "device_time_total", None)
                     if t is None:
                         t = getattr(ev, "cuda_time_total", 0.0)
-                    if ("k_qc_" in ev.key or "k_vis_" in ev.key) and ev.count:
+                    if any(p in ev.key for p in ("k_qc_", "k_s1_", "k_vis_")) and ev.count:     # k_s1_: the shared normal kernels (s1_normals_device.h)
                         key = ev.key.replace("(anonymous namespace)::", "").replace("icon::", "").replace("void ", "").split("(")[0]
                         if lanes == 64 or "k_qc_raster" in key:
                             per[key] = t / ev.count

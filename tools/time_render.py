@@ -3,7 +3,7 @@
 meshes of the dense synthetic volumes (257^3, 513^3) at 512^2 x 4 views, for both lane mappings of the rasteriser (eight lanes
 per face / one thread per face).  HIP events around alternating calls after a warm-up; per-kernel times from a torch.profiler
 run of their own.  There is no pytorch3d build for this device to compare with: the figures are records.  query_color_device is
-timed in the same session on the same meshes (its object file does not change with the renderer; the figure shows it).
+timed in the same session on the same meshes (the two share the S1 normal kernels of csrc/s1_normals_device.h).
 
     python tools/time_render.py [--res 257 513] [--reps 30] [--out profiles/render_timing.txt]
 """
@@ -89,7 +89,7 @@ def main():
                     t = getattr(ev, "device_time_total", None)
                     if t is None:
                         t = getattr(ev, "cuda_time_total", 0.0)
-                    if "k_rn_" in ev.key and ev.count:
+                    if ("k_rn_" in ev.key or "k_s1_" in ev.key) and ev.count:         # k_s1_: the shared normal kernels (s1_normals_device.h)
                         key = ev.key.replace("(anonymous namespace)::", "").replace("icon::", "").replace("void ", "").split("(")[0]
                         if lanes == 8 or "k_rn_raster" in key:
                             per[key + (f"  [{lanes} lane(s)]" if "k_rn_raster" in key else "")] = t / ev.count
