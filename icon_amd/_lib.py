@@ -38,6 +38,7 @@ SYMBOLS = [
     "icon_feat_batch_set_volume", "icon_semantic_voxelize_batch",
     "icon_query_color_bytes", "icon_query_color",
     "icon_render_bytes", "icon_render_normal",
+    "icon_silhouette_bytes", "icon_silhouette_forward", "icon_silhouette_backward",
 ]
 
 _lib = None

@@ -3,8 +3,11 @@
 Replaces ``lib.common.render.Render.load_meshes`` / ``get_rgb_image`` / ``get_depth_map`` (a pytorch3d ``MeshRasterizer`` plus
 ``cleanShader``; call sites lib/dataset/TestDataset.py:289-299, apps/ICON.py:387-392, apps/infer.py:423/448/482) by ONE native
 call, ``icon_render_normal`` (csrc/render_normal.hip; the rule is DESIGN.md 4.13).  No pytorch3d involved; there is no CPU path.
-The differentiable uses of the reference's renderer (gradients of the SMPL fit, the soft silhouette), video and point clouds
-are not covered.
+
+``Render.get_silhouette_image`` (the soft silhouette of the SMPL fit loop, apps/infer.py:205) is ``silhouette_device``: a
+``torch.autograd.Function`` over ``icon_silhouette_forward`` / ``icon_silhouette_backward`` (csrc/silhouette.hip; DESIGN.md 4.14,
+parity unpinned like 4.13) - differentiable with respect to the vertices.  The normal and depth maps stay non-differentiable;
+video and point clouds are not covered.
 """
 from __future__ import annotations
 
@@ -95,13 +98,88 @@ def render_normal_device(verts: torch.Tensor, faces: torch.Tensor, cam_ids: Sequ
     return out if len(out) > 1 else images
 
 
+def _sil_args(v, f, cams, size):
+    return (_lib.ptr(v), C.c_int64(v.shape[0]), _lib.ptr(f), C.c_int64(f.shape[0]), C.c_int(1 if f.dtype == torch.int64 else 0),
+            (C.c_int * len(cams))(*cams), C.c_int(len(cams)), C.c_int(size))
+
+
+def _sil_scratch(v, f, cams, size):
+    nbytes = C.c_int64(0)
+    check(_lib.lib().icon_silhouette_bytes(C.c_int64(v.shape[0]), C.c_int64(f.shape[0]), C.c_int(size), C.c_int(len(cams)), C.byref(nbytes)),
+          "icon_silhouette_bytes")
+    return _rn_scratch(v.device, nbytes.value)
+
+
+class _Silhouette(torch.autograd.Function):
+    """verts (float32, contiguous, on the device) -> alpha; the other arguments are not differentiable"""
+
+    @staticmethod
+    def forward(ctx, v, f, cams, size):
+        from .engine import _stream
+        with torch.cuda.device(v.device):
+            scratch = _sil_scratch(v, f, cams, size)
+            alpha = torch.empty((len(cams), size, size), dtype=torch.float32, device=v.device)
+            check(_lib.lib().icon_silhouette_forward(*_sil_args(v, f, cams, size), _lib.ptr(alpha), _lib.ptr(scratch),
+                                                     C.c_int64(scratch.numel()), _stream()), "icon_silhouette_forward")
+        ctx.save_for_backward(v, f, alpha)
+        ctx.cams, ctx.size = cams, size
+        return alpha
+
+    @staticmethod
+    def backward(ctx, grad_alpha):
+        from .engine import _stream
+        v, f, alpha = ctx.saved_tensors
+        cams, size = ctx.cams, ctx.size
+        g = grad_alpha.to(torch.float32).contiguous()
+        with torch.cuda.device(v.device):
+            scratch = _sil_scratch(v, f, cams, size)                          # this thread's and this stream's: autograd has its own
+            grad_verts = torch.empty_like(v)
+            check(_lib.lib().icon_silhouette_backward(*_sil_args(v, f, cams, size), _lib.ptr(alpha), _lib.ptr(g), _lib.ptr(grad_verts),
+                                                      _lib.ptr(scratch), C.c_int64(scratch.numel()), _stream()), "icon_silhouette_backward")
+        return grad_verts, None, None, None
+
+
+def silhouette_device(verts: torch.Tensor, faces: torch.Tensor, cam_ids: Sequence[int] = (0, 2), size: int = 512) -> torch.Tensor:
+    """``verts [V,3]`` (float), ``faces [F,3]`` (int32 or int64, read in place), both on one HIP device -> the soft silhouette
+    ``alpha [n,size,size]`` float32 in [0,1] there (background 0), view k from camera ``cam_ids[k]`` (the cameras and the
+    left-right mirror of camera 2 in a two-view call are ``render_normal_device``'s).  Differentiable with respect to ``verts``
+    (``torch.autograd.Function``: the forward saves ``alpha``, the backward is one native call returning ``grad_verts``; candidate
+    set and back-face culling carry no gradient).  Every candidate of a pixel enters the product - pytorch3d keeps the 50 nearest
+    (DESIGN.md 4.14).  Each direction is ONE native call on the current stream: nothing allocated by it, nothing read back, no
+    floating-point atomics - equal bytes from run to run.  A face that names a missing vertex is skipped."""
+    cams, size = _check_cams(cam_ids), _check_size(size)
+    if not torch.is_tensor(verts) or verts.dim() != 2 or verts.shape[1] != 3 or verts.shape[0] == 0:
+        raise IconAmdError(f"render: verts must be a [V,3] tensor, got {tuple(getattr(verts, 'shape', ()))}")
+    if not verts.dtype.is_floating_point:
+        raise IconAmdError(f"render: verts must be a floating-point tensor, got {verts.dtype}")
+    if not torch.is_tensor(faces) or faces.dim() != 2 or faces.shape[1] != 3 or faces.shape[0] == 0:
+        raise IconAmdError(f"render: faces must be a [F,3] tensor, got {tuple(getattr(faces, 'shape', ()))}")
+    if faces.dtype.is_floating_point or faces.dtype == torch.bool:
+        raise IconAmdError(f"render: faces must be an integer tensor, got {faces.dtype}")
+    _need_device("silhouette_device")
+    if not (verts.is_cuda and faces.is_cuda) or verts.device != faces.device:
+        raise IconAmdError("silhouette_device: verts and faces must live on one HIP device (Render.load_meshes moves host data)")
+    v = verts.to(torch.float32).contiguous()                                 # differentiable: the gradient flows back through the cast
+    f = faces.detach()
+    if f.dtype not in (torch.int32, torch.int64):
+        f = f.to(torch.int64)
+    return _Silhouette.apply(v, f.contiguous(), tuple(cams), size)
+
+
+def _mirror_cam2(cam_ids, cams) -> bool:
+    """does ``get_silhouette_image`` have to mirror camera 2 itself?  The native call mirrors it when IT
+    renders exactly two views; the reference decides by ``len(cam_ids)`` (duplicates included)"""
+    return (len(cam_ids) == 2) != (len(cams) == 2) and 2 in cams
+
+
 class Render:
-    """Drop-in for the forward uses of ``lib.common.render.Render``::
+    """Drop-in for ``lib.common.render.Render``'s normal maps, depth maps and soft silhouettes::
 
         render = Render(size=512, device=torch.device("cuda:0"))
         render.load_meshes(verts, faces)
         T_normal_F, T_normal_B = render.get_rgb_image()          # [1,3,S,S] each, in [-1,1]
         depth_F, depth_B = render.get_depth_map(cam_ids=[0, 2])   # [S,S] each
+        sil_F, sil_B = render.get_silhouette_image()             # [1,S,S] each, differentiable in verts
 
     The maps of one set of cameras are rendered once per ``load_meshes`` (one native call gives images and depths); the
     tensors handed out are views of that result."""
@@ -112,6 +190,7 @@ class Render:
         if self.device.type != "cuda":
             raise IconAmdError(f"Render: device must be a HIP device, got {self.device} (there is no CPU fallback)")
         self.meshes = None
+        self._live = None
         self._cache = {}
 
     def _device(self) -> torch.device:
@@ -120,10 +199,16 @@ class Render:
 
     def load_meshes(self, verts, faces) -> None:
         """``verts [V,3]`` / ``faces [F,3]``: tensors or arrays, on the host or the device (a leading batch axis of 1 is dropped).
-        Lists are taken element by element, as the reference does; element 0 is what the get_* calls render."""
+        Lists are taken element by element, as the reference does; element 0 is what the get_* calls render.  The normal and
+        depth maps are rendered from detached copies, as before; when element 0's vertices are a floating-point device tensor
+        that requires grad, a reference to that tensor is kept next to them for ``get_silhouette_image`` to back-propagate into."""
         dev = self._device()
         if not isinstance(verts, (list, tuple)):
             verts, faces = [verts], [faces]
+        v0 = verts[0] if len(verts) else None
+        self._live = None
+        if torch.is_tensor(v0) and v0.is_cuda and v0.dtype.is_floating_point and v0.requires_grad:
+            self._live = v0[0] if v0.dim() == 3 and v0.shape[0] == 1 else v0
         meshes = []
         for v, f in zip(verts, faces):
             v = torch.as_tensor(np.asarray(v) if not torch.is_tensor(v) else v)
@@ -149,7 +234,8 @@ class Render:
 
     def get_rgb_image(self, cam_ids=[0, 2]):
         """-> one ``[1,3,S,S]`` tensor per requested camera, in ascending camera order (the reference walks its camera list and
-        keeps the requested ones); camera 2 is mirrored left-right when ``len(cam_ids) == 2``"""
+        keeps the requested ones); camera 2 is mirrored left-right when ``len(cam_ids) == 2``.  Not differentiable: rendered from
+        the detached copy of the mesh, whatever ``load_meshes`` was given."""
         _check_cams(cam_ids)
         cams = tuple(c for c in range(4) if c in [int(x) for x in cam_ids])
         images, _ = self._render(cams)
@@ -161,10 +247,29 @@ class Render:
 
     def get_depth_map(self, cam_ids=[0, 2]):
         """-> one ``[S,S]`` tensor per entry of ``cam_ids``, in that order; camera 2 is ALWAYS mirrored left-right (the
-        reference's get_depth_map does not look at the number of views)"""
+        reference's get_depth_map does not look at the number of views).  Not differentiable, like ``get_rgb_image``."""
         cams = tuple(_check_cams(cam_ids))
         _, depth = self._render(cams)
         out = [depth[k] for k in range(len(cams))]
         if len(cams) != 2:
             out = [torch.fliplr(d) if c == 2 else d for c, d in zip(cams, out)]
+        return out
+
+    def get_silhouette_image(self, cam_ids=[0, 2]):
+        """-> one ``[1,S,S]`` soft silhouette per requested camera, in ascending camera order; camera 2 is mirrored left-right
+        (``dims=[2]``) when ``len(cam_ids) == 2`` - the reference's signature and mirroring.  Differentiable: when ``load_meshes``
+        was given a floating-point device tensor that requires grad, ``backward()`` reaches it (``silhouette_device``)."""
+        _check_cams(cam_ids)
+        cams = tuple(c for c in range(4) if c in [int(x) for x in cam_ids])
+        _need_device("Render")
+        if not self.meshes:
+            raise IconAmdError("Render: load_meshes has not been called")
+        v, f = self.meshes[0]
+        if self._live is not None:
+            v = self._live.to(v.device)
+        alpha = silhouette_device(v, f, cams, self.size)
+        out = [alpha[k:k + 1] for k in range(len(cams))]
+        if _mirror_cam2(cam_ids, cams):
+            k = cams.index(2)
+            out[k] = torch.flip(out[k], dims=[2])
         return out

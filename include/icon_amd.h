@@ -536,6 +536,28 @@ int icon_render_normal(const float *d_verts, int64_t V, const void *d_faces, int
                        const int *cam_ids, int n_views, int size, float *d_images, float *d_depth, int32_t *d_pix_to_face,
                        void *d_scratch, int64_t scratch_bytes, void *stream);
 
+/* ---- the soft silhouette of a mesh, forwards and backwards --------------------------------------------
+ * replaces Render.get_silhouette_image (lib/common/render.py:200-213, 376-386: pytorch3d MeshRasterizer with
+ * blur_radius = log(1/1e-4 - 1) * 5e-5, faces_per_pixel = 50, cull_backfaces, SoftSilhouetteShader with sigma = 1e-4) for the
+ * cameras of icon_render_normal, and its gradient with respect to the vertices (the SMPL fit loop, apps/infer.py:163-273).
+ * The rule is DESIGN.md 4.14 (PARITY UNPINNED); ALL candidates of a pixel enter the product, not the 50 nearest.
+ * d_verts [V,3] f32; d_faces [F,3], int64 when faces_int64 != 0, else int32 - read in place; cam_ids: n_views (1..4) HOST
+ * values 0..3; size: 8..2048.  forward: d_alpha [n_views,size,size] f32 out in [0,1], background 0.  backward: d_alpha as the
+ * forward call wrote it, d_grad_alpha [n_views,size,size] f32, d_grad_verts [V,3] f32 out (every entry is written): the
+ * gradient of sum(alpha * grad_alpha), summed over the views; candidate set and culling carry no gradient.  With exactly two
+ * views the plane of cam 2 is mirrored left-right (alpha and grad_alpha alike).  A face that names a vertex that does not exist
+ * is skipped and counted: after the stream has been waited for, the first int32 of the scratch holds the number of such faces.
+ * d_scratch: device memory of at least icon_silhouette_bytes(V, F, size, n_views) bytes, 256-byte aligned, owned by the caller;
+ * the backward call does not need what the forward call left there.  Enqueued on `stream`: no allocation, no synchronisation,
+ * nothing read back; no floating-point atomics: both directions are bit-identical from run to run. */
+int icon_silhouette_bytes(int64_t V, int64_t F, int size, int n_views, int64_t *bytes);
+int icon_silhouette_forward(const float *d_verts, int64_t V, const void *d_faces, int64_t F, int faces_int64,
+                            const int *cam_ids, int n_views, int size, float *d_alpha,
+                            void *d_scratch, int64_t scratch_bytes, void *stream);
+int icon_silhouette_backward(const float *d_verts, int64_t V, const void *d_faces, int64_t F, int faces_int64,
+                             const int *cam_ids, int n_views, int size, const float *d_alpha, const float *d_grad_alpha,
+                             float *d_grad_verts, void *d_scratch, int64_t scratch_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -297,6 +297,30 @@ def sec_render(S, their_render, name, size=128, cams=(0, 2)):
            f"common pixels colour {dc[both].max():.2e}, depth {dd[both].max():.2e}" + ("" if ok else " - class: camera convention / blur band / blend"))
 
 
+def sec_silhouette(S, their_silhouette, name, size=128, cams=(0, 2)):
+    """lib/common/render.py:200-213, 376-386 (Render.get_silhouette_image) against icon_amd.render.silhouette_device: alpha and the
+    gradient of sum(alpha * g) with respect to the vertices, g a fixed smooth field.  The native rule takes every candidate of a
+    pixel, the package the 50 nearest: PASS means alpha within 0.0102 (one pair at the blur radius) on every pixel,
+    within 1e-4 on all but 2 % of the pixels with alpha > 0, and the gradient within 1e-3 of its largest entry."""
+    torch = S.torch
+    from icon_amd.render import silhouette_device
+    verts, faces = S.verts[0].float().contiguous(), S.faces[0].long().contiguous()
+    c = (np.arange(size) + 0.5) / size
+    g = torch.from_numpy(np.stack([np.sin(5.0 * c[None, :] + 3.0 * c[:, None] + k) for k in range(len(cams))]).astype(np.float32)).to(verts.device)
+    v = verts.clone().requires_grad_(True)
+    alpha = silhouette_device(v, faces, cams, size)
+    (alpha * g).sum().backward()
+    their_a, their_g = (np.asarray(a, np.float64) for a in their_silhouette(verts.cpu().numpy(), faces.cpu().numpy(), cams, size, g.cpu().numpy()))
+    da = np.abs(alpha.detach().cpu().numpy() - their_a)
+    dg = float(np.abs(v.grad.cpu().numpy() - their_g).max() / max(np.abs(their_g).max(), 1e-30))
+    covered = int((their_a > 0).sum())
+    n_out = int((da > 1e-4).sum())
+    ok = covered > 0 and da.max() <= 0.0102 and n_out <= 0.02 * covered and dg <= 1e-3
+    report(name + " Render.get_silhouette_image (alpha, grad_verts)", "PASS" if ok else "DIFF",
+           f"{size}^2 x {len(cams)} views, alpha > 0 on {covered} pixels: largest |alpha diff| {da.max():.2e}, {n_out} pixels beyond 1e-4; gradient "
+           f"||g - theirs||inf / ||theirs||inf = {dg:.2e}" + ("" if ok else " - class: camera convention / culling / the 50-faces-per-pixel truncation"))
+
+
 def sec_voxelize(S, their_voxelize, name):
     """lib/net/voxelize.py:57-59,119-137"""
     from icon_amd import synth
@@ -368,6 +392,15 @@ def main():
             sys.path.insert(0, os.path.join(ROOT, "tests"))
             import render_checker                                        # pytorch3d's pipeline restated in float64
             sec_render(subject(), lambda v, f, cams, size: (lambda r: (r[2], r[1]))(render_checker.render_blend_f64(v, f, cams, size)), tag)
+
+        if want("silhouette"):
+            sys.path.insert(0, os.path.join(ROOT, "tests"))
+            import silhouette_oracle                                     # the rule of DESIGN.md 4.14 in float64 torch
+
+            def oracle_sil(v, f, cams, size, g):
+                r = silhouette_oracle.silhouette(v, f, cams, size, grad_alpha=g)
+                return r["alpha"], r["grad_verts"]
+            sec_silhouette(subject(), oracle_sil, tag)
 
         def classic(final):
             v, f = mc_classic.marching_cubes(final.cpu().numpy(), 0.5)
@@ -476,6 +509,35 @@ def main():
                         images.append(im.cpu().numpy()); depths.append(de.cpu().numpy())
                     return np.stack(images), np.stack(depths)
                 sec_render(subject(), their_render, f"pytorch3d {pr[0].__version__}")
+        # the silhouette row: like the renderer row, covered by pytorch3d's ABSENT line unless asked for by name
+        if want("silhouette") and ("silhouette" in only or p3):
+            def imp():
+                import pytorch3d
+                import pytorch3d.renderer as R
+                from pytorch3d.structures import Meshes
+                return pytorch3d, R, Meshes
+            ps = load("pytorch3d (silhouette renderer)", imp)
+            if ps:
+                import torch
+
+                def their_silhouette(v, f, cams, size, g):               # render.py:200-213, 376-386 - the settings of Render, written out
+                    R, dev = ps[1], torch.device("cuda:0")
+                    vt = torch.from_numpy(v).to(dev).requires_grad_(True)
+                    mesh = ps[2](vt[None], torch.from_numpy(f)[None].to(dev))
+                    eyes = [(0, 0, 100.0), (100.0, 0, 0), (0, 0, -100.0), (-100.0, 0, 0)]
+                    planes = []
+                    for cam in cams:
+                        Rm, T = R.look_at_view_transform(eye=[eyes[cam]], at=((0, 0, 0),), up=((0, 1, 0),))
+                        camera = R.FoVOrthographicCameras(device=dev, R=Rm, T=T, znear=100.0, zfar=-100.0, max_y=100.0, min_y=-100.0, max_x=100.0,
+                                                          min_x=-100.0, scale_xyz=(100.0 * np.ones(3),))
+                        settings = R.RasterizationSettings(image_size=size, blur_radius=np.log(1.0 / 1e-4 - 1.0) * 5e-5, faces_per_pixel=50, cull_backfaces=True)
+                        renderer = R.MeshRenderer(rasterizer=R.MeshRasterizer(cameras=camera, raster_settings=settings), shader=R.SoftSilhouetteShader())
+                        a = renderer(mesh)[0, :, :, 3]
+                        planes.append(torch.flip(a, dims=[1]) if cam == 2 and len(cams) == 2 else a)
+                    alpha = torch.stack(planes)
+                    (alpha * torch.from_numpy(g).to(dev)).sum().backward()
+                    return alpha.detach().cpu().numpy(), vt.grad.cpu().numpy()
+                sec_silhouette(subject(), their_silhouette, f"pytorch3d {ps[0].__version__}")
         # ---- voxelize_cuda ----------------------------------------------------------------------------------------
         if want("voxelize_cuda"):
             def imp():
