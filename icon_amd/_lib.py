@@ -39,6 +39,7 @@ SYMBOLS = [
     "icon_query_color_bytes", "icon_query_color",
     "icon_render_bytes", "icon_render_normal",
     "icon_silhouette_bytes", "icon_silhouette_forward", "icon_silhouette_backward",
+    "icon_render_normal_backward_bytes", "icon_render_normal_backward",
 ]
 
 _lib = None

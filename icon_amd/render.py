@@ -6,8 +6,9 @@ call, ``icon_render_normal`` (csrc/render_normal.hip; the rule is DESIGN.md 4.13
 
 ``Render.get_silhouette_image`` (the soft silhouette of the SMPL fit loop, apps/infer.py:205) is ``silhouette_device``: a
 ``torch.autograd.Function`` over ``icon_silhouette_forward`` / ``icon_silhouette_backward`` (csrc/silhouette.hip; DESIGN.md 4.14,
-parity unpinned like 4.13) - differentiable with respect to the vertices.  The normal and depth maps stay non-differentiable;
-video and point clouds are not covered.
+parity unpinned like 4.13) - differentiable with respect to the vertices.  The normal maps are differentiable on request
+(``render_normal_device(differentiable=True)``, ``Render(normal_grad=True)``: ``icon_render_normal_backward``,
+csrc/render_normal_bwd.hip); depth maps and ``pix_to_face`` are not; video and point clouds are not covered.
 """
 from __future__ import annotations
 
@@ -56,33 +57,10 @@ def _check_size(size) -> int:
     return int(size)
 
 
-def render_normal_device(verts: torch.Tensor, faces: torch.Tensor, cam_ids: Sequence[int] = (0, 2), size: int = 512,
-                         return_depth: bool = False, return_faces: bool = False):
-    """``verts [V,3]`` (float), ``faces [F,3]`` (int32 or int64, read in place), both on one HIP device ->
-    ``images [n,3,size,size]`` float32 in [-1,1] there, view k from camera ``cam_ids[k]`` (0: from +z, 1: from +x, 2: from -z,
-    3: from -x; +y is up, the [-1,1] cube fills the image; background 0), then ``depth [n,size,size]`` (view depth, background
-    -1) with ``return_depth`` and ``pix_to_face [n,size,size]`` int32 (background -1) with ``return_faces``.  With exactly two
-    views the planes of camera 2 are mirrored left-right, as the reference's ``get_rgb_image`` does.  ONE native call enqueued
-    on the current stream: nothing is allocated by it, nothing read back, the stream is not waited for - so a face that names a
-    vertex that does not exist cannot raise here; it is skipped.  The scratch is cached per (thread, device, stream)."""
+def _rn_forward(v, f, cams, size, return_depth, return_faces):
+    """the native forward call on a float32, contiguous ``v`` and an int32 / int64, contiguous ``f``"""
     from .engine import _stream
-    cams, size = _check_cams(cam_ids), _check_size(size)
-    if not torch.is_tensor(verts) or verts.dim() != 2 or verts.shape[1] != 3 or verts.shape[0] == 0:
-        raise IconAmdError(f"render: verts must be a [V,3] tensor, got {tuple(getattr(verts, 'shape', ()))}")
-    if not torch.is_tensor(faces) or faces.dim() != 2 or faces.shape[1] != 3 or faces.shape[0] == 0:
-        raise IconAmdError(f"render: faces must be a [F,3] tensor, got {tuple(getattr(faces, 'shape', ()))}")
-    if faces.dtype.is_floating_point or faces.dtype == torch.bool:
-        raise IconAmdError(f"render: faces must be an integer tensor, got {faces.dtype}")
-    _need_device("render_normal_device")
-    if not (verts.is_cuda and faces.is_cuda) or verts.device != faces.device:
-        raise IconAmdError("render_normal_device: verts and faces must live on one HIP device (Render.load_meshes moves host data)")
-    dev = verts.device
-    v = verts.detach().to(torch.float32).contiguous()
-    f = faces.detach()
-    if f.dtype not in (torch.int32, torch.int64):
-        f = f.to(torch.int64)
-    f = f.contiguous()
-    n = len(cams)
+    dev, n = v.device, len(cams)
     L = _lib.lib()
     with torch.cuda.device(dev):
         nbytes = C.c_int64(0)
@@ -94,6 +72,77 @@ def render_normal_device(verts: torch.Tensor, faces: torch.Tensor, cam_ids: Sequ
         check(L.icon_render_normal(_lib.ptr(v), C.c_int64(v.shape[0]), _lib.ptr(f), C.c_int64(f.shape[0]), C.c_int(1 if f.dtype == torch.int64 else 0),
                                    (C.c_int * n)(*cams), C.c_int(n), C.c_int(size), _lib.ptr(images), _lib.ptr(depth), _lib.ptr(pix),
                                    _lib.ptr(scratch), C.c_int64(scratch.numel()), _stream()), "icon_render_normal")
+    return images, depth, pix
+
+
+class _RenderNormal(torch.autograd.Function):
+    """verts (float32, contiguous, on the device) -> images, depth, pix_to_face; only ``images`` is differentiable, and only in
+    ``verts``.  The forward is the unchanged native call with ``return_faces``; the backward is ONE native call,
+    ``icon_render_normal_backward`` (csrc/render_normal_bwd.hip)"""
+
+    @staticmethod
+    def forward(ctx, v, f, cams, size):
+        images, depth, pix = _rn_forward(v, f, cams, size, True, True)
+        ctx.save_for_backward(v, f, pix)
+        ctx.cams, ctx.size = cams, size
+        ctx.mark_non_differentiable(depth, pix)
+        return images, depth, pix
+
+    @staticmethod
+    def backward(ctx, grad_images, _grad_depth, _grad_pix):
+        from .engine import _stream
+        v, f, pix = ctx.saved_tensors
+        cams, size = ctx.cams, ctx.size
+        g = grad_images.to(torch.float32).contiguous()
+        L = _lib.lib()
+        with torch.cuda.device(v.device):
+            nbytes = C.c_int64(0)
+            check(L.icon_render_normal_backward_bytes(C.c_int64(v.shape[0]), C.c_int64(f.shape[0]), C.c_int(size), C.c_int(len(cams)), C.byref(nbytes)),
+                  "icon_render_normal_backward_bytes")
+            scratch = _rn_scratch(v.device, nbytes.value)                     # this thread's and this stream's: autograd has its own
+            grad_verts = torch.empty_like(v)
+            check(L.icon_render_normal_backward(*_sil_args(v, f, cams, size), _lib.ptr(pix), _lib.ptr(g), _lib.ptr(grad_verts),
+                                                _lib.ptr(scratch), C.c_int64(scratch.numel()), _stream()), "icon_render_normal_backward")
+        return grad_verts, None, None, None
+
+
+def render_normal_device(verts: torch.Tensor, faces: torch.Tensor, cam_ids: Sequence[int] = (0, 2), size: int = 512,
+                         return_depth: bool = False, return_faces: bool = False, differentiable: bool = False):
+    """``verts [V,3]`` (float), ``faces [F,3]`` (int32 or int64, read in place), both on one HIP device ->
+    ``images [n,3,size,size]`` float32 in [-1,1] there, view k from camera ``cam_ids[k]`` (0: from +z, 1: from +x, 2: from -z,
+    3: from -x; +y is up, the [-1,1] cube fills the image; background 0), then ``depth [n,size,size]`` (view depth, background
+    -1) with ``return_depth`` and ``pix_to_face [n,size,size]`` int32 (background -1) with ``return_faces``.  With exactly two
+    views the planes of camera 2 are mirrored left-right, as the reference's ``get_rgb_image`` does.  ONE native call enqueued
+    on the current stream: nothing is allocated by it, nothing read back, the stream is not waited for - so a face that names a
+    vertex that does not exist cannot raise here; it is skipped.  The scratch is cached per (thread, device, stream).
+
+    ``differentiable=False`` (the default) renders from a detached copy: nothing returned requires grad.  With ``True`` the
+    same forward call runs inside a ``torch.autograd.Function``: ``images`` is differentiable with respect to ``verts`` (which
+    must be floating-point; the gradient flows back through the float32 cast), its backward is one native call
+    (``icon_render_normal_backward``; the rule is DESIGN.md 4.15: the winner per pixel and the clamp pattern carry no
+    gradient; no floating-point atomics - equal bytes from run to run).  ``depth`` and ``pix_to_face`` stay non-differentiable."""
+    cams, size = _check_cams(cam_ids), _check_size(size)
+    if not torch.is_tensor(verts) or verts.dim() != 2 or verts.shape[1] != 3 or verts.shape[0] == 0:
+        raise IconAmdError(f"render: verts must be a [V,3] tensor, got {tuple(getattr(verts, 'shape', ()))}")
+    if differentiable and not verts.dtype.is_floating_point:
+        raise IconAmdError(f"render: verts must be a floating-point tensor, got {verts.dtype}")
+    if not torch.is_tensor(faces) or faces.dim() != 2 or faces.shape[1] != 3 or faces.shape[0] == 0:
+        raise IconAmdError(f"render: faces must be a [F,3] tensor, got {tuple(getattr(faces, 'shape', ()))}")
+    if faces.dtype.is_floating_point or faces.dtype == torch.bool:
+        raise IconAmdError(f"render: faces must be an integer tensor, got {faces.dtype}")
+    _need_device("render_normal_device")
+    if not (verts.is_cuda and faces.is_cuda) or verts.device != faces.device:
+        raise IconAmdError("render_normal_device: verts and faces must live on one HIP device (Render.load_meshes moves host data)")
+    f = faces.detach()
+    if f.dtype not in (torch.int32, torch.int64):
+        f = f.to(torch.int64)
+    f = f.contiguous()
+    if differentiable:
+        v = verts.to(torch.float32).contiguous()                             # differentiable: the gradient flows back through the cast
+        images, depth, pix = _RenderNormal.apply(v, f, tuple(cams), size)
+    else:
+        v = verts.detach().to(torch.float32).contiguous()
+        images, depth, pix = _rn_forward(v, f, cams, size, return_depth, return_faces)
     out = (images,) + ((depth,) if return_depth else ()) + ((pix,) if return_faces else ())
     return out if len(out) > 1 else images
 
@@ -182,10 +231,14 @@ class Render:
         sil_F, sil_B = render.get_silhouette_image()             # [1,S,S] each, differentiable in verts
 
     The maps of one set of cameras are rendered once per ``load_meshes`` (one native call gives images and depths); the
-    tensors handed out are views of that result."""
+    tensors handed out are views of that result.  ``Render(size, device, normal_grad=True)`` makes ``get_rgb_image``
+    differentiable in the vertices as well (see there)."""
 
-    def __init__(self, size: int = 512, device=None):
+    def __init__(self, size: int = 512, device=None, normal_grad: bool = False):
+        """``normal_grad=True`` makes ``get_rgb_image`` differentiable in the vertices ``load_meshes`` was given (the normal-map
+        terms of the fit loop and the cloth loop, apps/infer.py:200-217 / :448-456); by default it is not, as before."""
         self.size = _check_size(size)
+        self.normal_grad = bool(normal_grad)
         self.device = torch.device(device) if device is not None else torch.device("cuda")
         if self.device.type != "cuda":
             raise IconAmdError(f"Render: device must be a HIP device, got {self.device} (there is no CPU fallback)")
@@ -201,7 +254,8 @@ class Render:
         """``verts [V,3]`` / ``faces [F,3]``: tensors or arrays, on the host or the device (a leading batch axis of 1 is dropped).
         Lists are taken element by element, as the reference does; element 0 is what the get_* calls render.  The normal and
         depth maps are rendered from detached copies, as before; when element 0's vertices are a floating-point device tensor
-        that requires grad, a reference to that tensor is kept next to them for ``get_silhouette_image`` to back-propagate into."""
+        that requires grad, a reference to that tensor is kept next to them for ``get_silhouette_image`` - and, with
+        ``normal_grad=True``, ``get_rgb_image`` - to back-propagate into."""
         dev = self._device()
         if not isinstance(verts, (list, tuple)):
             verts, faces = [verts], [faces]
@@ -234,11 +288,21 @@ class Render:
 
     def get_rgb_image(self, cam_ids=[0, 2]):
         """-> one ``[1,3,S,S]`` tensor per requested camera, in ascending camera order (the reference walks its camera list and
-        keeps the requested ones); camera 2 is mirrored left-right when ``len(cam_ids) == 2``.  Not differentiable: rendered from
-        the detached copy of the mesh, whatever ``load_meshes`` was given."""
+        keeps the requested ones); camera 2 is mirrored left-right when ``len(cam_ids) == 2``.  By default not differentiable:
+        rendered once per ``load_meshes`` from the detached copy of the mesh, whatever ``load_meshes`` was given.  A
+        ``Render(normal_grad=True)`` renders from the live tensor instead - a fresh differentiable call every time, never the
+        cached images - when ``load_meshes`` kept one (a floating-point device tensor that requires grad) and grad mode is on;
+        under ``torch.no_grad()`` or after a detached ``load_meshes`` it takes the cached path like the default."""
         _check_cams(cam_ids)
         cams = tuple(c for c in range(4) if c in [int(x) for x in cam_ids])
-        images, _ = self._render(cams)
+        if self.normal_grad and self._live is not None and torch.is_grad_enabled():
+            _need_device("Render")
+            v, f = self.meshes[0]
+            images, depth = render_normal_device(self._live.to(v.device), f, cams, self.size, return_depth=True, differentiable=True)
+            if cams not in self._cache:                                      # the same bytes as the detached render: get_depth_map needs no second call
+                self._cache[cams] = (images.detach(), depth)
+        else:
+            images, _ = self._render(cams)
         out = [images[k:k + 1] for k in range(len(cams))]
         if (len(cam_ids) == 2) != (len(cams) == 2) and 2 in cams:          # duplicates in cam_ids: the native call decided by its own count
             k = cams.index(2)

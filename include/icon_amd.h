@@ -558,6 +558,30 @@ int icon_silhouette_backward(const float *d_verts, int64_t V, const void *d_face
                              const int *cam_ids, int n_views, int size, const float *d_alpha, const float *d_grad_alpha,
                              float *d_grad_verts, void *d_scratch, int64_t scratch_bytes, void *stream);
 
+/* ---- the gradient of the normal maps with respect to the vertices --------------------------------------
+ * what Render.get_rgb_image back-propagates in the two optimisation loops of apps/infer.py (:200-217 losses["normal"],
+ * :448-456 losses["cloth"]; pytorch3d: TexturesVertex(verts_normals_padded()) interpolated by differentiable barycentrics),
+ * for the images icon_render_normal wrote.  The rule is DESIGN.md 4.15 (PARITY UNPINNED): the winner per pixel, the candidate
+ * set and the clamp pattern of the barycentrics carry no gradient; the gradient flows through the clamped, renormalised
+ * barycentrics of the winner into the NDC corners of its face, and through the S1 vertex normals (the normalisation, the sum
+ * over the incident faces, the cross product) into the world coordinates - the latter summed over the views.  Depth maps and
+ * pix_to_face are not differentiable.
+ * d_verts, d_faces, faces_int64, cam_ids, n_views, size: as given to icon_render_normal.  d_pix_to_face [n_views,size,size]
+ * int32: as that call wrote it, the left-right mirror of cam 2 in a two-view call included; it is only compared with face ids,
+ * never used as an address: ids that name no face select nothing.  d_grad_images [n_views,3,size,size] f32 (mirrored alike);
+ * d_grad_verts [V,3] f32 out (every entry is written; a vertex of no face gets 0): the gradient of sum(images * grad_images).
+ * A face that names a vertex that does not exist is skipped and counted: after the stream has been waited for, the first int32
+ * of the scratch holds the number of such faces.  d_scratch: device memory of at least
+ * icon_render_normal_backward_bytes(V, F, size, n_views) bytes, 256-byte aligned, owned by the caller; the call does not need
+ * what icon_render_normal left in ITS scratch.  Enqueued on `stream`: no allocation, no synchronisation, nothing read back;
+ * no floating-point atomics: bit-identical from run to run and from int32 and int64 faces.  The debug option "rn_lanes"
+ * chooses the mapping of the per-face sweep as it does for icon_render_normal. */
+int icon_render_normal_backward_bytes(int64_t V, int64_t F, int size, int n_views, int64_t *bytes);
+int icon_render_normal_backward(const float *d_verts, int64_t V, const void *d_faces, int64_t F, int faces_int64,
+                                const int *cam_ids, int n_views, int size, const int32_t *d_pix_to_face,
+                                const float *d_grad_images, float *d_grad_verts,
+                                void *d_scratch, int64_t scratch_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

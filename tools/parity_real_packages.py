@@ -321,6 +321,33 @@ def sec_silhouette(S, their_silhouette, name, size=128, cams=(0, 2)):
            f"||g - theirs||inf / ||theirs||inf = {dg:.2e}" + ("" if ok else " - class: camera convention / culling / the 50-faces-per-pixel truncation"))
 
 
+def sec_render_grad(S, their_grad, name, size=128, cams=(0, 2)):
+    """lib/common/render.py:289-325 differentiated (apps/infer.py:200-217, :448-456: the normal-map terms of the two loops) against
+    icon_amd.render.render_normal_device(differentiable=True): the gradient of sum(images * g) with respect to the vertices, g a
+    fixed smooth field, zero on the pixels tests/normal_grad_oracle.py excludes (a barycentric of the winner within 1e-4 of a clamp).
+    The native rule differentiates the winner, the package its soft blend (the two differ on the pixels where two
+    candidates tie in depth, 3.7e-3 of the largest entry on the icosphere at 32^2): PASS means within 1e-2 of the largest entry."""
+    torch = S.torch
+    from icon_amd.render import render_normal_device
+    import normal_grad_oracle
+    verts, faces = S.verts[0].float().contiguous(), S.faces[0].long().contiguous()
+    v = verts.clone().requires_grad_(True)
+    images, pix = render_normal_device(v, faces, cams, size, return_faces=True, differentiable=True)
+    pix = pix.cpu().numpy()
+    c = (np.arange(size) + 0.5) / size
+    g = np.stack([np.sin(5.0 * c[None, :] + 3.0 * c[:, None] + k) for k in range(3 * len(cams))]).reshape(len(cams), 3, size, size)
+    ex = normal_grad_oracle.excluded(verts.cpu().numpy(), faces.cpu().numpy(), pix, cams, size)
+    g = (g * ~ex[:, None]).astype(np.float32)
+    (images * torch.from_numpy(g).to(verts.device)).sum().backward()
+    their_g = np.asarray(their_grad(verts.cpu().numpy(), faces.cpu().numpy(), cams, size, g, pix), np.float64)
+    dg = float(np.abs(v.grad.cpu().numpy() - their_g).max() / max(np.abs(their_g).max(), 1e-30))
+    covered = int((pix >= 0).sum())
+    ok = covered > 0 and dg <= 1e-2
+    report(name + " Render.get_rgb_image (grad_verts)", "PASS" if ok else "DIFF",
+           f"{size}^2 x {len(cams)} views, {covered} covered pixels ({int(ex.sum())} excluded): gradient ||g - theirs||inf / ||theirs||inf = {dg:.2e}"
+           + ("" if ok else " - class: camera convention / depth ties of the soft blend / clamp pattern"))
+
+
 def sec_voxelize(S, their_voxelize, name):
     """lib/net/voxelize.py:57-59,119-137"""
     from icon_amd import synth
@@ -401,6 +428,11 @@ def main():
                 r = silhouette_oracle.silhouette(v, f, cams, size, grad_alpha=g)
                 return r["alpha"], r["grad_verts"]
             sec_silhouette(subject(), oracle_sil, tag)
+
+        if want("render_grad"):
+            sys.path.insert(0, os.path.join(ROOT, "tests"))
+            import normal_grad_oracle                                    # the rule of DESIGN.md 4.15 in float64 torch
+            sec_render_grad(subject(), lambda v, f, cams, size, g, pix: normal_grad_oracle.loss_and_grad(v, f, pix, cams, size, g)[1], tag)
 
         def classic(final):
             v, f = mc_classic.marching_cubes(final.cpu().numpy(), 0.5)
@@ -538,6 +570,38 @@ def main():
                     (alpha * torch.from_numpy(g).to(dev)).sum().backward()
                     return alpha.detach().cpu().numpy(), vt.grad.cpu().numpy()
                 sec_silhouette(subject(), their_silhouette, f"pytorch3d {ps[0].__version__}")
+        # the normal maps' gradient: like the renderer row, covered by pytorch3d's ABSENT line unless asked for by name
+        if want("render_grad") and ("render_grad" in only or p3):
+            def imp():
+                import pytorch3d
+                import pytorch3d.renderer as R
+                from pytorch3d.structures import Meshes
+                return pytorch3d, R, Meshes
+            pg = load("pytorch3d (renderer, gradient)", imp)
+            if pg:
+                import torch
+                sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+                def their_grad(v, f, cams, size, g, pix):                # render.py:136-168,228-258,289-325 with a live verts tensor
+                    R, dev = pg[1], torch.device("cuda:0")
+                    vt = torch.from_numpy(v).to(dev).requires_grad_(True)
+                    mesh = pg[2](vt[None], torch.from_numpy(f)[None].to(dev))
+                    mesh.textures = R.TexturesVertex(verts_features=(mesh.verts_normals_padded() + 1.0) * 0.5)
+                    eyes = [(0, 0, 100.0), (100.0, 0, 0), (0, 0, -100.0), (-100.0, 0, 0)]
+                    images = []
+                    for cam in cams:
+                        Rm, T = R.look_at_view_transform(eye=[eyes[cam]], at=((0, 0, 0),), up=((0, 1, 0),))
+                        camera = R.FoVOrthographicCameras(device=dev, R=Rm, T=T, znear=100.0, zfar=-100.0, max_y=100.0, min_y=-100.0, max_x=100.0,
+                                                          min_x=-100.0, scale_xyz=(100.0 * np.ones(3),))
+                        ras = R.MeshRasterizer(cameras=camera, raster_settings=R.RasterizationSettings(image_size=size, blur_radius=np.log(1.0 / 1e-4) * 1e-7,
+                                                                                                        faces_per_pixel=30))
+                        frag = ras(mesh)
+                        rgb = R.blending.softmax_rgb_blend(mesh.sample_textures(frag), frag, R.BlendParams(1e-4, 1e-8, (0.5, 0.5, 0.5)), znear=-256, zfar=256)
+                        im = (rgb[0, :, :, :3].permute(2, 0, 1) - 0.5) * 2.0
+                        images.append(torch.flip(im, dims=[2]) if cam == 2 and len(cams) == 2 else im)
+                    (torch.stack(images) * torch.from_numpy(g).to(dev)).sum().backward()
+                    return vt.grad.cpu().numpy()
+                sec_render_grad(subject(), their_grad, f"pytorch3d {pg[0].__version__}")
         # ---- voxelize_cuda ----------------------------------------------------------------------------------------
         if want("voxelize_cuda"):
             def imp():
