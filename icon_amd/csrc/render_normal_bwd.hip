@@ -13,8 +13,8 @@
 //      through the cross product to its corners.  World-space, the same for every view: the views add up, and no coordinate is left out.
 //
 // Shape of the work: one stream-ordered call of kernel launches over the caller's scratch; nothing is allocated, read back or
-// waited for; the clears are a kernel of the call's own.  The few expressions of the per-pixel rule are restated here privately, in
-// render_normal.hip's operation order (that file's kernels are the timed ones of 4.13 and stay as they are).
+// waited for; the clears are a kernel of the call's own.  The expressions of the per-pixel rule - projection, ef, den, the clipped box,
+// the clamped barycentrics, the pixel address, the sweeps and the deferred list - are raster_device.h's, the very functions of render_normal.hip.
 //   clear, count / scan / fill (s1_normals_device.h): one incidence list serves the normals and both gathers
 //   N_v: the un-normalised S1 sums into the scratch - the forward's values recomputed, the same bytes
 //   k_rnb_face: per (view, face) sweep the face's clipped pixel box, take the pixels pix_to_face gives to this face, accumulate
@@ -31,24 +31,15 @@
 // an address; pix_to_face is only ever COMPARED with a face id, never used as an address.
 #pragma clang fp contract(off)
 
-#include "s1_normals_device.h"
+#include "raster_device.h"
 
 namespace icon {
 namespace {
 
-constexpr int kRnbLanes = 8;          // render_normal.hip's kRnLanes, kRnBigPerLane, kRnBigGrid, kRnBlurR, kRnEps
-constexpr int kRnbBigPerLane = 64;
-constexpr int kRnbBigGrid = 1024;
-constexpr float kRnbBlurR = 9.597051539e-04f;
-constexpr float kRnbEps = 1e-8f;
 constexpr int kRnbAcc = 16;           // 9: sum b_k g_c; 6: X0 Y0 X1 Y1 X2 Y2 through the ef terms; 1: d / d den
 
-struct RnbHdr { int bad_faces, n_big, n_long, pad; };
-
-struct RnbCtx : S1Ctx {
-    int S, n_views, cams, flip;      // as RnCtx
-    RnbHdr *hdr;
-    int *big;                        // deferred (view << 29 | face) [n_views F]
+struct RnbCtx : RsCtx {
+    int *n_big, *big;                // the deferred list (raster_device.h) [n_views F] and its length in the header
     float *Nv;                       // [V][3] un-normalised S1 sums
     float *gNv;                      // [V][3] d loss / d N_v
     float *gn;                       // [n_views][3 F][3] per corner: sum over the face's pixels of b_k g_c
@@ -59,46 +50,24 @@ struct RnbCtx : S1Ctx {
     float *grad_verts;               // [V][3]
 };
 
-__device__ __forceinline__ float rnb_ef(float px, float py, float ax, float ay, float bx, float by)
-{
-    return (px - ax) * (by - ay) - (py - ay) * (bx - ax);
-}
-__device__ __forceinline__ float rnb_max(float a, float b) { return (a > b) ? a : b; }
-__device__ __forceinline__ float rnb_min(float a, float b) { return (b < a) ? b : a; }
-__device__ __forceinline__ float rnb_centre(int i, int S) { return -1.0f + (float)(2 * i + 1) / (float)S; }
-
 struct RnbFace {
     float X[3], Y[3], den;
-    int i0, j0, w, n;                // pixel box in MIRRORED indices (i = S-1-column, j = S-1-row)
+    RsBox box;
     int64_t id[3];
 };
 
-// face f as camera `cam` sees it (rn_setup: projection, area, den, the clipped box).  false: the forward drew nothing of it
+// face f as camera `cam` sees it: the forward's projection, area, den and clipped box.  false: the forward drew nothing of it
 template <class IT>
 __device__ __forceinline__ bool rnb_setup(const RnbCtx &c, int cam, int64_t f, RnbFace &r)
 {
     if (!s1_face<IT>(c, f, r.id)) return false;
-    const bool side = (cam & 1) != 0, neg = (cam == 0 || cam == 3);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const float *p = c.verts + 3 * r.id[k];
-        const float xa = side ? p[2] : p[0];
-        r.X[k] = neg ? -xa : xa; r.Y[k] = p[1];
-    }
-    const float area = rnb_ef(r.X[2], r.Y[2], r.X[0], r.Y[0], r.X[1], r.Y[1]);
-    if (!(fabsf(area) > kRnbEps)) return false;
-    r.den = area + kRnbEps;
-    const float xlo = rnb_min(r.X[0], rnb_min(r.X[1], r.X[2])) - kRnbBlurR, xhi = rnb_max(r.X[0], rnb_max(r.X[1], r.X[2])) + kRnbBlurR;
-    const float ylo = rnb_min(r.Y[0], rnb_min(r.Y[1], r.Y[2])) - kRnbBlurR, yhi = rnb_max(r.Y[0], rnb_max(r.Y[1], r.Y[2])) + kRnbBlurR;
-    // clamped as floats: what is converted to int lies in [-1, S], whatever the coordinates are (NaN included)
-    const float fS = (float)c.S;
-    const int i0 = (int)floorf(fminf(fmaxf((xlo + 1.0f) * 0.5f * fS, 0.0f), fS));
-    const int i1 = (int)floorf(fminf(fmaxf((xhi + 1.0f) * 0.5f * fS, -1.0f), fS - 1.0f));
-    const int j0 = (int)floorf(fminf(fmaxf((ylo + 1.0f) * 0.5f * fS, 0.0f), fS));
-    const int j1 = (int)floorf(fminf(fmaxf((yhi + 1.0f) * 0.5f * fS, -1.0f), fS - 1.0f));
-    if (i0 > i1 || j0 > j1) return false;
-    r.i0 = i0; r.j0 = j0; r.w = i1 - i0 + 1; r.n = r.w * (j1 - j0 + 1);   // 0 <= i0 <= i1 < S, 0 <= j0 <= j1 < S; n <= S^2 <= 2^22
-    return true;
+    float D[3];                                                            // never read: no depth here
+    rs_project(c, cam, r.id, r.X, r.Y, D);
+    const float area = rs_area(r.X, r.Y);
+    if (!rs_drawn(area)) return false;
+    r.den = area + kRsEps;
+    r.box = rs_box(rs_bounds(r.X, r.Y, kRsNormalBlurR), c.S);
+    return !r.box.empty();
 }
 
 // the S1 normals of the face's corners, as the forward's RnStore left them: N / max(|N|, 1e-6)
@@ -117,21 +86,16 @@ __device__ __forceinline__ void rnb_normals(const RnbCtx &c, const RnbFace &r, f
 __device__ __forceinline__ void rnb_pixel(const RnbCtx &c, const RnbFace &r, const float nrm[9], int view, int cam, int64_t f, int i, int j,
                                           float a[kRnbAcc])
 {
-    const int row = c.S - 1 - j, col = c.S - 1 - i;
-    const int cs = (c.flip && cam == 2) ? c.S - 1 - col : col;               // the cam-2 mirror of the two-view call
-    if ((int64_t)c.pix[((size_t)view * c.S + row) * c.S + cs] != f) return;
-    const size_t plane = (size_t)c.S * c.S;
-    const float *gp = c.gimg + ((size_t)view * 3 * c.S + row) * c.S + cs;
+    const size_t plane = (size_t)c.S * c.S, at = rs_at(c, cam, i, j);
+    if ((int64_t)c.pix[(size_t)view * plane + at] != f) return;
+    const float *gp = c.gimg + (size_t)view * 3 * plane + at;
     const float g0 = gp[0], g1 = gp[plane], g2 = gp[2 * plane];
     if (g0 == 0.0f && g1 == 0.0f && g2 == 0.0f) return;
-    const float px = rnb_centre(i, c.S), py = rnb_centre(j, c.S);
-    const float w0 = rnb_ef(px, py, r.X[1], r.Y[1], r.X[2], r.Y[2]) / r.den;
-    const float w1 = rnb_ef(px, py, r.X[2], r.Y[2], r.X[0], r.Y[0]) / r.den;
-    const float w2 = rnb_ef(px, py, r.X[0], r.Y[0], r.X[1], r.Y[1]) / r.den;
-    const float c0 = rnb_max(rnb_min(w0, 1.0f), 0.0f), c1 = rnb_max(rnb_min(w1, 1.0f), 0.0f), c2 = rnb_max(rnb_min(w2, 1.0f), 0.0f);
-    const float sraw = (c0 + c1) + c2;
-    const float s = rnb_max(sraw, 1e-5f);
-    const float b0 = c0 / s, b1 = c1 / s, b2 = c2 / s;
+    const float px = rs_centre(i, c.S), py = rs_centre(j, c.S);
+    float w[3];
+    rs_weights(r.X, r.Y, r.den, px, py, w);
+    const RsBary q = rs_bary(w);
+    const float w0 = w[0], w1 = w[1], w2 = w[2], b0 = q.b[0], b1 = q.b[1], b2 = q.b[2], s = q.s;
     // path 2: d loss / d n_k = b_k g
     a[0] += b0 * g0; a[1] += b0 * g1; a[2] += b0 * g2;
     a[3] += b1 * g0; a[4] += b1 * g1; a[5] += b1 * g2;
@@ -140,7 +104,7 @@ __device__ __forceinline__ void rnb_pixel(const RnbCtx &c, const RnbFace &r, con
     const float B0 = (g0 * (nrm[0] + 1.0f) + g1 * (nrm[1] + 1.0f)) + g2 * (nrm[2] + 1.0f);
     const float B1 = (g0 * (nrm[3] + 1.0f) + g1 * (nrm[4] + 1.0f)) + g2 * (nrm[5] + 1.0f);
     const float B2 = (g0 * (nrm[6] + 1.0f) + g1 * (nrm[7] + 1.0f)) + g2 * (nrm[8] + 1.0f);
-    const float dot = sraw > 1e-5f ? (B0 * b0 + B1 * b1) + B2 * b2 : 0.0f;    // the max passes gradient only where the sum exceeds 1e-5
+    const float dot = q.sraw > kRsMinSum ? (B0 * b0 + B1 * b1) + B2 * b2 : 0.0f;   // the max passes gradient only where the sum exceeds it
     const float W0 = (w0 > 0.0f && w0 < 1.0f) ? (B0 - dot) / s : 0.0f;        // the clamp only where 0 < w_k < 1
     const float W1 = (w1 > 0.0f && w1 < 1.0f) ? (B1 - dot) / s : 0.0f;
     const float W2 = (w2 > 0.0f && w2 < 1.0f) ? (B2 - dot) / s : 0.0f;
@@ -173,13 +137,6 @@ __device__ __forceinline__ void rnb_write(const RnbCtx &c, const RnbFace &r, boo
     for (int q = 0; q < 6; ++q) oxy[q] = x[q];
 }
 
-// the call's clears: [0, n) words of the scratch (header, incidence counts, fill cursors) - a kernel like the others
-__global__ __launch_bounds__(256) void k_rnb_clear(uint32_t *zero, size_t n)
-{
-    const size_t stride = (size_t)gridDim.x * 256;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) zero[i] = 0u;
-}
-
 // the un-normalised S1 sum into the scratch
 struct RnbStoreN {
     float *Nv;
@@ -206,28 +163,20 @@ __global__ __launch_bounds__(256) void k_rnb_face(RnbCtx c)
 {
     const int64_t f = ((int64_t)blockIdx.x * 256 + threadIdx.x) / G;
     const int sub = threadIdx.x % G;
-    const int view = blockIdx.y, cam = (c.cams >> (2 * view)) & 3;
+    const int view = blockIdx.y, cam = c.cam(view);
     if (f >= c.F) return;                                                  // whole groups of G lanes
     RnbFace r;
     float a[kRnbAcc];
 #pragma unroll
     for (int q = 0; q < kRnbAcc; ++q) a[q] = 0.0f;
     const bool drawn = rnb_setup<IT>(c, cam, f, r);
-    const bool big = drawn && r.n > kRnbBigPerLane * G;
+    const bool big = drawn && r.box.n() > kRsBigPerLane * G;
     if (big) {
-        if (sub == 0) {                                                    // at most n_views F entries; F < 2^29
-            const int at = atomicAdd(&c.hdr->n_big, 1);
-            if ((int64_t)at < c.F * c.n_views) c.big[at] = (view << 29) | (int)f;
-        }
+        if (sub == 0) rs_defer(c, c.n_big, c.big, view, f);
     } else if (drawn) {
         float nrm[9];
         rnb_normals(c, r, nrm);
-        int j = sub / r.w, i = sub - j * r.w;
-        for (int t = sub; t < r.n; t += G) {
-            rnb_pixel(c, r, nrm, view, cam, f, r.i0 + i, r.j0 + j, a);
-            i += G;
-            while (i >= r.w) { i -= r.w; ++j; }
-        }
+        rs_sweep<G>(r.box, sub, [&](int i, int j) { rnb_pixel(c, r, nrm, view, cam, f, i, j, a); });
     }
     if (G > 1) {
 #pragma unroll
@@ -246,22 +195,19 @@ template <class IT>
 __global__ __launch_bounds__(256) void k_rnb_face_big(RnbCtx c)
 {
     __shared__ float s_part[4][kRnbAcc];
-    const int nb = (int)min((int64_t)c.hdr->n_big, c.F * c.n_views);
+    const int nb = rs_deferred_count(c, c.n_big);
     for (int e = blockIdx.x; e < nb; e += gridDim.x) {                     // uniform over the workgroup
-        const int code = c.big[e];
-        const int view = code >> 29, cam = (c.cams >> (2 * view)) & 3;
-        const int64_t f = code & ((1 << 29) - 1);
-        if (view < 0 || view >= c.n_views || f >= c.F) continue;
+        int view;
+        int64_t f;
+        if (!rs_deferred(c, c.big, e, view, f)) continue;
+        const int cam = c.cam(view);
         RnbFace r;
         if (!rnb_setup<IT>(c, cam, f, r)) continue;
         float nrm[9], a[kRnbAcc];
         rnb_normals(c, r, nrm);
 #pragma unroll
         for (int q = 0; q < kRnbAcc; ++q) a[q] = 0.0f;
-        for (int t = threadIdx.x; t < r.n; t += 256) {
-            const int j = t / r.w;
-            rnb_pixel(c, r, nrm, view, cam, f, r.i0 + (t - j * r.w), r.j0 + j, a);
-        }
+        rs_sweep_block(r.box, [&](int i, int j) { rnb_pixel(c, r, nrm, view, cam, f, i, j, a); });
 #pragma unroll
         for (int q = 0; q < kRnbAcc; ++q) {
             float s = a[q];
@@ -317,19 +263,14 @@ struct RnbTermB {
     const float *fc, *gxy; int64_t F; int cams;
     __device__ void operator()(int pass, int key, float o[3]) const
     {
-        o[0] = o[1] = o[2] = 0.0f;
-        if (key < 0 || key / 3 >= F) return;
         if (pass == 0) {
+            o[0] = o[1] = o[2] = 0.0f;
+            if (key < 0 || key / 3 >= F) return;
             const float *g = fc + (size_t)key * 3;
             o[0] = g[0]; o[1] = g[1]; o[2] = g[2];
             return;
         }
-        const int view = pass - 1;
-        const float *g = gxy + ((size_t)view * 3 * F + key) * 2;
-        const int cam = (cams >> (2 * view)) & 3;
-        const float gx = (cam == 0 || cam == 3) ? -g[0] : g[0];            // X = -x, +z, +x, -z for cam 0..3
-        if (cam & 1) o[2] = gx; else o[0] = gx;
-        o[1] = g[1];
+        rs_world_term(gxy, F, cams, pass - 1, key, o);
     }
 };
 struct RnbStoreB {
@@ -379,50 +320,32 @@ __global__ __launch_bounds__(256) void k_rnb_face_pass(RnbCtx c)
     for (int q = 0; q < 9; ++q) out[q] = o[q];
 }
 
-struct RnbLayout { size_t hdr, deg, cur, zero_end, loc, part, inc, tmp, longv, big, Nv, gNv, gn, gxy, fc, total; };
+struct RnbLayout { S1Layout s1; size_t big, Nv, gNv, gn, gxy, fc, total; };
 
 RnbLayout rnb_layout(int64_t V, int64_t F, int n_views)
 {
     RnbLayout L{};
-    size_t o = 0;
-    auto take = [&](size_t bytes) { const size_t at = o; o = (o + bytes + 255) / 256 * 256; return at; };
-    L.hdr = take(sizeof(RnbHdr)); L.deg = take((size_t)V * 4); L.cur = take((size_t)V * 4);
-    L.zero_end = o;                                                        // [0, zero_end): cleared by k_rnb_clear
-    L.loc = take((size_t)V * 4); L.part = take((size_t)((V + kScanItems - 1) / kScanItems) * 4);
-    L.inc = take((size_t)F * 12); L.tmp = take((size_t)F * 12); L.longv = take((size_t)V * 4);
+    S1Take take;
+    L.s1 = s1_layout(take, V, F);
     L.big = take((size_t)F * 4 * n_views);
     L.Nv = take((size_t)V * 12); L.gNv = take((size_t)V * 12);
     L.gn = take((size_t)F * n_views * 36); L.gxy = take((size_t)F * n_views * 24); L.fc = take((size_t)F * 36);
-    L.total = o;
+    L.total = take.o;
     return L;
-}
-
-int rnb_check_sizes(int64_t V, int64_t F, int size, int n_views)
-{
-    ICON_ARG(V > 0 && F > 0 && V < (1ll << 31) && F < (1ll << 29), "icon_render_normal_backward: 0 < V < 2^31, 0 < F < 2^29");
-    ICON_ARG(size >= 8 && size <= 2048, "icon_render_normal_backward: size must be 8..2048");
-    ICON_ARG(n_views >= 1 && n_views <= 4, "icon_render_normal_backward: n_views must be 1..4");
-    return ICON_OK;
 }
 
 template <class IT>
 void rnb_launch(const RnbCtx &c, hipStream_t st)
 {
     const unsigned gF = (unsigned)((c.F + 255) / 256), gV = (unsigned)((c.V + 255) / 256);
-    const int nb = (int)((c.V + kScanItems - 1) / kScanItems);
     const S1Ctx &s1 = c;                                                   // the shared kernels take the base alone
-    hipLaunchKernelGGL(k_s1_count<IT>, dim3(gF), dim3(256), 0, st, s1);
-    hipLaunchKernelGGL(k_s1_scan_blocks, dim3((unsigned)nb), dim3(256), 0, st, s1);
-    hipLaunchKernelGGL(k_s1_scan_parts, dim3(1), dim3(1024), 0, st, s1, nb);
-    hipLaunchKernelGGL(k_s1_fill<IT>, dim3(gF), dim3(256), 0, st, s1);
+    s1_launch_lists<IT>(s1, st);
     hipLaunchKernelGGL(k_rnb_normals<IT>, dim3(gV), dim3(256), 0, st, c);
     hipLaunchKernelGGL((k_s1_normals_long<IT, RnbStoreN>), dim3(kLongGrid), dim3(64), 0, st, s1, RnbStoreN{c.Nv});
-    // the forward's mapping (rn_launch), by the sizes alone or forced by the "rn_lanes" debug option
-    const int G = g_rn_lanes == 1 ? 1 : (g_rn_lanes == 8 ? 8 : (8 * c.F > (int64_t)c.S * c.S ? 1 : kRnbLanes));
-    const dim3 gR((unsigned)((c.F * G + 255) / 256), (unsigned)c.n_views);
-    if (G == 1) hipLaunchKernelGGL((k_rnb_face<IT, 1>), gR, dim3(256), 0, st, c);
+    const dim3 gR((unsigned)((c.F * rs_lanes(c) + 255) / 256), (unsigned)c.n_views);   // the forward's mapping
+    if (rs_lanes(c) == 1) hipLaunchKernelGGL((k_rnb_face<IT, 1>), gR, dim3(256), 0, st, c);
     else hipLaunchKernelGGL((k_rnb_face<IT, 8>), gR, dim3(256), 0, st, c);
-    hipLaunchKernelGGL(k_rnb_face_big<IT>, dim3(kRnbBigGrid), dim3(256), 0, st, c);
+    hipLaunchKernelGGL(k_rnb_face_big<IT>, dim3(kRsBigGrid), dim3(256), 0, st, c);
     const RnbTermA ta{c.gn, c.F};
     const RnbStoreA sa{c.Nv, c.gNv};
     hipLaunchKernelGGL((k_rnb_vertex<RnbTermA, RnbStoreA>), dim3(gV), dim3(256), 0, st, c, c.n_views, ta, sa);
@@ -442,7 +365,7 @@ using namespace icon;
 extern "C" int icon_render_normal_backward_bytes(int64_t V, int64_t F, int size, int n_views, int64_t *bytes)
 {
     ICON_ARG(bytes != nullptr, "icon_render_normal_backward_bytes: null argument");
-    const int rc = rnb_check_sizes(V, F, size, n_views);
+    const int rc = rs_check_sizes("icon_render_normal_backward", V, F, size, n_views);
     if (rc) return rc;
     *bytes = (int64_t)rnb_layout(V, F, n_views).total;
     return ICON_OK;
@@ -454,31 +377,18 @@ extern "C" int icon_render_normal_backward(const float *d_verts, int64_t V, cons
                                            void *d_scratch, int64_t scratch_bytes, void *stream)
 {
     ICON_ARG(d_verts && d_faces && cam_ids && d_pix_to_face && d_grad_images && d_grad_verts && d_scratch, "icon_render_normal_backward: null argument");
-    const int rc = rnb_check_sizes(V, F, size, n_views);
-    if (rc) return rc;
-    int cams = 0;
-    for (int k = 0; k < n_views; ++k) {
-        ICON_ARG(cam_ids[k] >= 0 && cam_ids[k] <= 3, "icon_render_normal_backward: cam_ids must be 0..3");
-        cams |= cam_ids[k] << (2 * k);
-    }
-    ICON_ARG(((uintptr_t)d_scratch & 255) == 0, "icon_render_normal_backward: the scratch must be 256-byte aligned");
     const RnbLayout L = rnb_layout(V, F, n_views);
-    ICON_ARG(scratch_bytes >= (int64_t)L.total, "icon_render_normal_backward: scratch smaller than icon_render_normal_backward_bytes");
+    RnbCtx c{};
+    const int rc = rs_context("icon_render_normal_backward", "icon_render_normal_backward_bytes", d_verts, V, d_faces, F, cam_ids, n_views, size,
+                              d_scratch, scratch_bytes, L.total, c);
+    if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
     char *s = static_cast<char *>(d_scratch);
-    RnbCtx c{};
-    c.verts = d_verts; c.faces = d_faces; c.V = V; c.F = F; c.S = size; c.n_views = n_views; c.cams = cams; c.flip = n_views == 2 ? 1 : 0;
     c.pix = d_pix_to_face; c.gimg = d_grad_images; c.grad_verts = d_grad_verts;
-    c.hdr = reinterpret_cast<RnbHdr *>(s + L.hdr); c.bad_faces = &c.hdr->bad_faces; c.n_long = &c.hdr->n_long;
-    c.deg = reinterpret_cast<int *>(s + L.deg); c.cur = reinterpret_cast<int *>(s + L.cur);
-    c.loc = reinterpret_cast<int *>(s + L.loc); c.part = reinterpret_cast<int *>(s + L.part);
-    c.inc = reinterpret_cast<int *>(s + L.inc); c.tmp = reinterpret_cast<int *>(s + L.tmp); c.longv = reinterpret_cast<int *>(s + L.longv);
-    c.big = reinterpret_cast<int *>(s + L.big);
+    c.n_big = &s1_bind(c, s, L.s1)->n_big; c.big = reinterpret_cast<int *>(s + L.big);
     c.Nv = reinterpret_cast<float *>(s + L.Nv); c.gNv = reinterpret_cast<float *>(s + L.gNv);
     c.gn = reinterpret_cast<float *>(s + L.gn); c.gxy = reinterpret_cast<float *>(s + L.gxy); c.fc = reinterpret_cast<float *>(s + L.fc);
-    const size_t n_zero = L.zero_end / 4;
-    hipLaunchKernelGGL(k_rnb_clear, dim3((unsigned)((n_zero + 255) / 256 < 2048 ? (n_zero + 255) / 256 : 2048)), dim3(256), 0, st,
-                       reinterpret_cast<uint32_t *>(s), n_zero);
+    rs_clear(s, L.s1, nullptr, 0, st);
     if (faces_int64) rnb_launch<int64_t>(c, st); else rnb_launch<int32_t>(c, st);
     ICON_HIP(hipGetLastError());
     return ICON_OK;

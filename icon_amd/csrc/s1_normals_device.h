@@ -1,13 +1,14 @@
 // s1_normals_device.h - the S1 vertex normals (incident faces in ascending 3 face + corner order, float32,
-// v / max(|v|, 1e-6)) as query_color.hip and render_normal.hip compute them, stated once: count / scan / fill a
+// v / max(|v|, 1e-6)) as query_color.hip, render_normal.hip and render_normal_bwd.hip compute them, stated once: count / scan / fill a
 // vertex -> (3 face + corner) incidence list, then one thread per vertex takes the entries in ascending order (selection: the lists
 // hold ~6 entries); a vertex of more than kShort entries goes to a device-side list, where one wavefront rank-sorts its entries
 // and adds them in order.  The order of the additions is fixed by the keys alone: bit-identical from run to run and to the
 // checkers' sequential loops.  Everything lives in the including file's anonymous namespace: each file instantiates the kernels
-// with its own context (S1Ctx is the base of QcCtx / RnCtx), its own per-vertex kernel (s1_sum_short, s1_defer_long) and its own
-// Store functor (k_s1_normals_long).  Every index taken out of the scratch (list lengths, segment starts, keys, list entries) is
-// range-checked before it is used as an address: the checks always pass after the call's own clears and are never relied on -
-// a call replayed from a captured graph once met the previous call's counters.
+// with its own context (S1Ctx is the base of QcCtx and, through raster_device.h's RsCtx, of RnCtx / SilCtx / RnbCtx), its own per-vertex
+// kernel (s1_sum_short, s1_defer_long) and its own Store functor (k_s1_normals_long); the host side lays the pieces out in the caller's
+// scratch (s1_layout), binds them (s1_bind) and launches count / scan / fill (s1_launch_lists).  Every index taken out of the scratch
+// (list lengths, segment starts, keys, list entries) is range-checked before it is used as an address: the checks always pass after the
+// call's own clears and are never relied on - a call replayed from a captured graph once met the previous call's counters.
 #pragma once
 #pragma clang fp contract(off)
 
@@ -30,6 +31,41 @@ struct S1Ctx {
     int *longv;                      // [V] the vertices of more than kShort entries
     const float *vis;                // null: every vertex gets a normal; otherwise only those with vis[v] == 0
 };
+
+// the first words of a call's scratch: the counters its kernels raise (0 after the call's clear).  n_big: the length of the caller's
+// list of deferred faces, where it keeps one (raster_device.h)
+struct S1Hdr { int bad_faces, n_big, n_long, pad; };
+
+// ---- host: the S1 pieces of a call's scratch, 256-byte aligned; [0, zero_end) is what the call's clear sets to 0 ----
+struct S1Take {
+    size_t o = 0;
+    size_t operator()(size_t bytes) { const size_t at = o; o = (o + bytes + 255) / 256 * 256; return at; }
+};
+struct S1Layout { size_t hdr, deg, cur, zero_end, loc, part, inc, tmp, mid, longv; };
+
+// appends the pieces to `take`; mid: `mid_bytes` of the caller's own between tmp and longv (render_normal.hip's deferred list lives there)
+S1Layout s1_layout(S1Take &take, int64_t V, int64_t F, size_t mid_bytes = 0)
+{
+    S1Layout L{};
+    L.hdr = take(sizeof(S1Hdr)); L.deg = take((size_t)V * 4); L.cur = take((size_t)V * 4);
+    L.zero_end = take.o;
+    L.loc = take((size_t)V * 4); L.part = take((size_t)((V + kScanItems - 1) / kScanItems) * 4);
+    L.inc = take((size_t)F * 12); L.tmp = take((size_t)F * 12);
+    L.mid = take(mid_bytes); L.longv = take((size_t)V * 4);
+    return L;
+}
+
+// binds the pieces over the scratch `s` into the context; the header, for the caller's own counters
+S1Hdr *s1_bind(S1Ctx &c, char *s, const S1Layout &L)
+{
+    S1Hdr *hdr = reinterpret_cast<S1Hdr *>(s + L.hdr);
+    c.bad_faces = &hdr->bad_faces; c.n_long = &hdr->n_long;
+    c.deg = reinterpret_cast<int *>(s + L.deg); c.cur = reinterpret_cast<int *>(s + L.cur);
+    c.loc = reinterpret_cast<int *>(s + L.loc); c.part = reinterpret_cast<int *>(s + L.part);
+    c.inc = reinterpret_cast<int *>(s + L.inc); c.tmp = reinterpret_cast<int *>(s + L.tmp);
+    c.longv = reinterpret_cast<int *>(s + L.longv);
+    return hdr;
+}
 
 // the three vertex ids of face f; false: the face names a vertex that does not exist (it is skipped everywhere)
 template <class IT>
@@ -121,6 +157,18 @@ __global__ __launch_bounds__(256) void k_s1_fill(S1Ctx c)
         const int64_t at = (int64_t)s1_start(c, v[k]) + atomicAdd(&c.cur[v[k]], 1);
         if (at >= 0 && at < 3 * c.F) c.inc[at] = (int)(3 * f + k);
     }
+}
+
+// host: count / scan / fill on stream st - the incidence lists every per-vertex kernel below reads
+template <class IT>
+void s1_launch_lists(const S1Ctx &c, hipStream_t st)
+{
+    const unsigned gF = (unsigned)((c.F + 255) / 256);
+    const int nb = (int)((c.V + kScanItems - 1) / kScanItems);
+    hipLaunchKernelGGL(k_s1_count<IT>, dim3(gF), dim3(256), 0, st, c);
+    hipLaunchKernelGGL(k_s1_scan_blocks, dim3((unsigned)nb), dim3(256), 0, st, c);
+    hipLaunchKernelGGL(k_s1_scan_parts, dim3(1), dim3(1024), 0, st, c, nb);
+    hipLaunchKernelGGL(k_s1_fill<IT>, dim3(gF), dim3(256), 0, st, c);
 }
 
 // (v1 - v0) x (v2 - v0) of the face behind an incidence key (S1; the corner order as given); 0 for a key that names no face

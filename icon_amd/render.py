@@ -57,6 +57,32 @@ def _check_size(size) -> int:
     return int(size)
 
 
+def _check_mesh(what: str, verts, faces, need_float: bool) -> torch.Tensor:
+    """the argument checks of ``render_normal_device`` and ``silhouette_device`` (``what``); -> the faces as the native calls read
+    them: detached, int32 or int64, contiguous"""
+    if not torch.is_tensor(verts) or verts.dim() != 2 or verts.shape[1] != 3 or verts.shape[0] == 0:
+        raise IconAmdError(f"render: verts must be a [V,3] tensor, got {tuple(getattr(verts, 'shape', ()))}")
+    if need_float and not verts.dtype.is_floating_point:
+        raise IconAmdError(f"render: verts must be a floating-point tensor, got {verts.dtype}")
+    if not torch.is_tensor(faces) or faces.dim() != 2 or faces.shape[1] != 3 or faces.shape[0] == 0:
+        raise IconAmdError(f"render: faces must be a [F,3] tensor, got {tuple(getattr(faces, 'shape', ()))}")
+    if faces.dtype.is_floating_point or faces.dtype == torch.bool:
+        raise IconAmdError(f"render: faces must be an integer tensor, got {faces.dtype}")
+    _need_device(what)
+    if not (verts.is_cuda and faces.is_cuda) or verts.device != faces.device:
+        raise IconAmdError(f"{what}: verts and faces must live on one HIP device (Render.load_meshes moves host data)")
+    f = faces.detach()
+    if f.dtype not in (torch.int32, torch.int64):
+        f = f.to(torch.int64)
+    return f.contiguous()
+
+
+def _mesh_args(v, f, cams, size):
+    """the leading arguments every native call of this module takes: the mesh, the cameras, the image size"""
+    return (_lib.ptr(v), C.c_int64(v.shape[0]), _lib.ptr(f), C.c_int64(f.shape[0]), C.c_int(1 if f.dtype == torch.int64 else 0),
+            (C.c_int * len(cams))(*cams), C.c_int(len(cams)), C.c_int(size))
+
+
 def _rn_forward(v, f, cams, size, return_depth, return_faces):
     """the native forward call on a float32, contiguous ``v`` and an int32 / int64, contiguous ``f``"""
     from .engine import _stream
@@ -69,8 +95,7 @@ def _rn_forward(v, f, cams, size, return_depth, return_faces):
         images = torch.empty((n, 3, size, size), dtype=torch.float32, device=dev)
         depth = torch.empty((n, size, size), dtype=torch.float32, device=dev) if return_depth else None
         pix = torch.empty((n, size, size), dtype=torch.int32, device=dev) if return_faces else None
-        check(L.icon_render_normal(_lib.ptr(v), C.c_int64(v.shape[0]), _lib.ptr(f), C.c_int64(f.shape[0]), C.c_int(1 if f.dtype == torch.int64 else 0),
-                                   (C.c_int * n)(*cams), C.c_int(n), C.c_int(size), _lib.ptr(images), _lib.ptr(depth), _lib.ptr(pix),
+        check(L.icon_render_normal(*_mesh_args(v, f, cams, size), _lib.ptr(images), _lib.ptr(depth), _lib.ptr(pix),
                                    _lib.ptr(scratch), C.c_int64(scratch.numel()), _stream()), "icon_render_normal")
     return images, depth, pix
 
@@ -101,7 +126,7 @@ class _RenderNormal(torch.autograd.Function):
                   "icon_render_normal_backward_bytes")
             scratch = _rn_scratch(v.device, nbytes.value)                     # this thread's and this stream's: autograd has its own
             grad_verts = torch.empty_like(v)
-            check(L.icon_render_normal_backward(*_sil_args(v, f, cams, size), _lib.ptr(pix), _lib.ptr(g), _lib.ptr(grad_verts),
+            check(L.icon_render_normal_backward(*_mesh_args(v, f, cams, size), _lib.ptr(pix), _lib.ptr(g), _lib.ptr(grad_verts),
                                                 _lib.ptr(scratch), C.c_int64(scratch.numel()), _stream()), "icon_render_normal_backward")
         return grad_verts, None, None, None
 
@@ -122,21 +147,7 @@ def render_normal_device(verts: torch.Tensor, faces: torch.Tensor, cam_ids: Sequ
     (``icon_render_normal_backward``; the rule is DESIGN.md 4.15: the winner per pixel and the clamp pattern carry no
     gradient; no floating-point atomics - equal bytes from run to run).  ``depth`` and ``pix_to_face`` stay non-differentiable."""
     cams, size = _check_cams(cam_ids), _check_size(size)
-    if not torch.is_tensor(verts) or verts.dim() != 2 or verts.shape[1] != 3 or verts.shape[0] == 0:
-        raise IconAmdError(f"render: verts must be a [V,3] tensor, got {tuple(getattr(verts, 'shape', ()))}")
-    if differentiable and not verts.dtype.is_floating_point:
-        raise IconAmdError(f"render: verts must be a floating-point tensor, got {verts.dtype}")
-    if not torch.is_tensor(faces) or faces.dim() != 2 or faces.shape[1] != 3 or faces.shape[0] == 0:
-        raise IconAmdError(f"render: faces must be a [F,3] tensor, got {tuple(getattr(faces, 'shape', ()))}")
-    if faces.dtype.is_floating_point or faces.dtype == torch.bool:
-        raise IconAmdError(f"render: faces must be an integer tensor, got {faces.dtype}")
-    _need_device("render_normal_device")
-    if not (verts.is_cuda and faces.is_cuda) or verts.device != faces.device:
-        raise IconAmdError("render_normal_device: verts and faces must live on one HIP device (Render.load_meshes moves host data)")
-    f = faces.detach()
-    if f.dtype not in (torch.int32, torch.int64):
-        f = f.to(torch.int64)
-    f = f.contiguous()
+    f = _check_mesh("render_normal_device", verts, faces, need_float=differentiable)
     if differentiable:
         v = verts.to(torch.float32).contiguous()                             # differentiable: the gradient flows back through the cast
         images, depth, pix = _RenderNormal.apply(v, f, tuple(cams), size)
@@ -145,11 +156,6 @@ def render_normal_device(verts: torch.Tensor, faces: torch.Tensor, cam_ids: Sequ
         images, depth, pix = _rn_forward(v, f, cams, size, return_depth, return_faces)
     out = (images,) + ((depth,) if return_depth else ()) + ((pix,) if return_faces else ())
     return out if len(out) > 1 else images
-
-
-def _sil_args(v, f, cams, size):
-    return (_lib.ptr(v), C.c_int64(v.shape[0]), _lib.ptr(f), C.c_int64(f.shape[0]), C.c_int(1 if f.dtype == torch.int64 else 0),
-            (C.c_int * len(cams))(*cams), C.c_int(len(cams)), C.c_int(size))
 
 
 def _sil_scratch(v, f, cams, size):
@@ -168,7 +174,7 @@ class _Silhouette(torch.autograd.Function):
         with torch.cuda.device(v.device):
             scratch = _sil_scratch(v, f, cams, size)
             alpha = torch.empty((len(cams), size, size), dtype=torch.float32, device=v.device)
-            check(_lib.lib().icon_silhouette_forward(*_sil_args(v, f, cams, size), _lib.ptr(alpha), _lib.ptr(scratch),
+            check(_lib.lib().icon_silhouette_forward(*_mesh_args(v, f, cams, size), _lib.ptr(alpha), _lib.ptr(scratch),
                                                      C.c_int64(scratch.numel()), _stream()), "icon_silhouette_forward")
         ctx.save_for_backward(v, f, alpha)
         ctx.cams, ctx.size = cams, size
@@ -183,7 +189,7 @@ class _Silhouette(torch.autograd.Function):
         with torch.cuda.device(v.device):
             scratch = _sil_scratch(v, f, cams, size)                          # this thread's and this stream's: autograd has its own
             grad_verts = torch.empty_like(v)
-            check(_lib.lib().icon_silhouette_backward(*_sil_args(v, f, cams, size), _lib.ptr(alpha), _lib.ptr(g), _lib.ptr(grad_verts),
+            check(_lib.lib().icon_silhouette_backward(*_mesh_args(v, f, cams, size), _lib.ptr(alpha), _lib.ptr(g), _lib.ptr(grad_verts),
                                                       _lib.ptr(scratch), C.c_int64(scratch.numel()), _stream()), "icon_silhouette_backward")
         return grad_verts, None, None, None
 
@@ -197,26 +203,13 @@ def silhouette_device(verts: torch.Tensor, faces: torch.Tensor, cam_ids: Sequenc
     (DESIGN.md 4.14).  Each direction is ONE native call on the current stream: nothing allocated by it, nothing read back, no
     floating-point atomics - equal bytes from run to run.  A face that names a missing vertex is skipped."""
     cams, size = _check_cams(cam_ids), _check_size(size)
-    if not torch.is_tensor(verts) or verts.dim() != 2 or verts.shape[1] != 3 or verts.shape[0] == 0:
-        raise IconAmdError(f"render: verts must be a [V,3] tensor, got {tuple(getattr(verts, 'shape', ()))}")
-    if not verts.dtype.is_floating_point:
-        raise IconAmdError(f"render: verts must be a floating-point tensor, got {verts.dtype}")
-    if not torch.is_tensor(faces) or faces.dim() != 2 or faces.shape[1] != 3 or faces.shape[0] == 0:
-        raise IconAmdError(f"render: faces must be a [F,3] tensor, got {tuple(getattr(faces, 'shape', ()))}")
-    if faces.dtype.is_floating_point or faces.dtype == torch.bool:
-        raise IconAmdError(f"render: faces must be an integer tensor, got {faces.dtype}")
-    _need_device("silhouette_device")
-    if not (verts.is_cuda and faces.is_cuda) or verts.device != faces.device:
-        raise IconAmdError("silhouette_device: verts and faces must live on one HIP device (Render.load_meshes moves host data)")
+    f = _check_mesh("silhouette_device", verts, faces, need_float=True)
     v = verts.to(torch.float32).contiguous()                                 # differentiable: the gradient flows back through the cast
-    f = faces.detach()
-    if f.dtype not in (torch.int32, torch.int64):
-        f = f.to(torch.int64)
-    return _Silhouette.apply(v, f.contiguous(), tuple(cams), size)
+    return _Silhouette.apply(v, f, tuple(cams), size)
 
 
 def _mirror_cam2(cam_ids, cams) -> bool:
-    """does ``get_silhouette_image`` have to mirror camera 2 itself?  The native call mirrors it when IT
+    """do ``get_rgb_image`` / ``get_silhouette_image`` have to mirror camera 2 themselves?  The native call mirrors it when IT
     renders exactly two views; the reference decides by ``len(cam_ids)`` (duplicates included)"""
     return (len(cam_ids) == 2) != (len(cams) == 2) and 2 in cams
 
@@ -304,7 +297,7 @@ class Render:
         else:
             images, _ = self._render(cams)
         out = [images[k:k + 1] for k in range(len(cams))]
-        if (len(cam_ids) == 2) != (len(cams) == 2) and 2 in cams:          # duplicates in cam_ids: the native call decided by its own count
+        if _mirror_cam2(cam_ids, cams):                                    # duplicates in cam_ids: the native call decided by its own count
             k = cams.index(2)
             out[k] = torch.flip(out[k], dims=[3])
         return out

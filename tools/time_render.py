@@ -89,7 +89,7 @@ def main():
                     t = getattr(ev, "device_time_total", None)
                     if t is None:
                         t = getattr(ev, "cuda_time_total", 0.0)
-                    if ("k_rn_" in ev.key or "k_s1_" in ev.key) and ev.count:         # k_s1_: the shared normal kernels (s1_normals_device.h)
+                    if any(p in ev.key for p in ("k_rn_", "k_s1_", "k_rs_")) and ev.count:   # k_s1_, k_rs_: the shared kernels (s1_normals_device.h, raster_device.h)
                         key = ev.key.replace("(anonymous namespace)::", "").replace("icon::", "").replace("void ", "").split("(")[0]
                         if lanes == 8 or "k_rn_raster" in key:
                             per[key + (f"  [{lanes} lane(s)]" if "k_rn_raster" in key else "")] = t / ev.count
