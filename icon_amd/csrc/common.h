@@ -85,6 +85,16 @@ struct alignas(32) LeafRec {
 };
 static_assert(sizeof(LeafRec) == 384, "LeafRec must be 384 bytes");
 
+// Oriented bounding boxes of a leaf's two triangle PAIRS (indexed like LeafRec), field-interleaved like it ([field][pair]): one
+// packed-f32 evaluation gives a lower bound of the squared distance from a point to each pair, and the packet walk skips the
+// pairs no lane can still need (geom_device.h: pair_box_bound).  Fields: 0-2 centre, 3-5 / 6-8 / 9-11 the three axes (unit vectors
+// times kPairBoxScale), 12-14 the half extents along them (inflated), 15 unused (0).  Short leaves repeat their last pair's
+// box.  mesh_rules.h: pair_box_setup, DESIGN.md "BVH conservativeness".
+struct alignas(32) PairBox {
+    float f[16][2];
+};
+static_assert(sizeof(PairBox) == 128, "PairBox must be 128 bytes");
+
 constexpr int kLeafMax = 4;        // triangle slots per BVH leaf (short leaves are padded)
 // wavefronts sharing ONE packet's search (geom_device.h: nearest_shared) by the packets of the launch - a launch with fewer
 // packets than the GPU has wave slots lasts as long as its longest walk.  Measured on whole-slab calls, MI355X (search + MLP,
@@ -133,6 +143,7 @@ struct MeshDev {
     const LeafRec *leaves;      // [F] indexed by leaf id = first slot of the leaf
     const MeshDyn *dyn;         // device
     int32_t n_tris;             // triangle slots = F
+    int32_t pbox_off;           // the PairBox section: (const PairBox *)leaves + pbox_off; 0 = the walk tests every pair ("pair_box" off)
     // ray bins over (y, z)
     const int32_t *bin_start;   // [gy*gz + 1]
     const int32_t *bin_slots;   // triangle slots
@@ -393,6 +404,7 @@ int work_share_dbg(icon_work *w, ShareDbg *out);
 int work_check_err(icon_work *w);
 extern int g_qc_lanes;                // query_color.hip: lanes per face of the colour call's rasteriser ("qc_lanes"; 0 = default)
 extern int g_rn_lanes;                // render_normal.hip: lanes per face of the renderer's rasteriser ("rn_lanes"; 0 = default)
+int pair_box_enabled();               // ICON_AMD_PAIR_BOX / icon_debug_set_option("pair_box"): meshes created while it is 0 walk without the cull
 int share_waves_override();           // ICON_AMD_SHARE / icon_debug_set_option("share_waves"): -1 = by launch size
 }  // namespace icon
 

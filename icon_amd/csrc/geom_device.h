@@ -258,9 +258,11 @@ template <bool STATS = false, bool TIES = false>
 __device__ __forceinline__ Nearest nearest_packet(const MeshDev &m, f3 p, bool live, int *wstack /* LDS, kStackDepth ints of this wave */,
                                                   int *n_nodes = nullptr, int *n_tris = nullptr, float thr0 = INFINITY,
                                                   unsigned long long *runner_up = nullptr, int center_lane = 21,
-                                                  bool have_root = false, int root = 0)
+                                                  bool have_root = false, int root = 0, int *n_offered = nullptr, int *n_tested = nullptr)
 {
     Nearest nr; nr.d2 = INFINITY; nr.slot = 0; nr.face = 0x7fffffff;
+    // the leaf pairs' oriented boxes (PairBox), or null: "pair_box" off - every pair of a visited leaf is tested (wave-uniform)
+    const PairBox *pbox = m.pbox_off ? reinterpret_cast<const PairBox *>(m.leaves) + m.pbox_off : nullptr;
     unsigned long long key = 0x7f8000007fffffffull;   // (+inf, INT_MAX)
     unsigned long long key2 = 0x7f8000007fffffffull;
     float thr = live ? thr0 : -INFINITY;
@@ -272,7 +274,24 @@ __device__ __forceinline__ Nearest nearest_packet(const MeshDev &m, f3 p, bool l
             const int leaf = code >> 2, cnt = (code & 3) + 1;
             if (STATS) *n_tris += cnt;
             const int npairs = __builtin_amdgcn_readfirstlane((cnt + 1) >> 1);      // 1 or 2, wave-uniform (scalar loop counter)
-            for (int pr = 0; pr < npairs; ++pr) {
+            // Most pairs of a visited leaf are out of every lane's reach (the leaf's AABB admits a slanted patch from far away:
+            // DESIGN.md 4.1): both pairs' oriented boxes in one packed evaluation, then the distance test only for the pairs
+            // SOME lane still needs.  box bound <= real d^2 of the pair's triangles, so a pair skipped here could neither beat
+            // nor tie any lane's key - the same argument as for a child's box.  Parked lanes (thr = -inf) never vote.
+            int need = (1 << npairs) - 1;                        // bit pr: pair pr is tested; scalar, like the loop over its bits
+            if (pbox) {
+                const f2 bb = pair_box_bound(reinterpret_cast<cf2 *>(as_const(pbox + leaf)), p.x, p.y, p.z);
+                const int any0 = __builtin_amdgcn_ballot_w64(bb.x <= thr) != 0 ? 1 : 0, any1 = __builtin_amdgcn_ballot_w64(bb.y <= thr) != 0 ? 2 : 0;
+                need &= any0 | any1;                             // (ballots are wave-uniform: all scalar)
+            }
+            if (STATS && n_offered) { *n_offered += npairs; *n_tested += __builtin_popcount((unsigned)need); }
+            if (need == 0) {                                     // nothing tested: key and bound are what they were
+                if (sp == 0) break;
+                cur = __builtin_amdgcn_readfirstlane(wstack[--sp]);
+                continue;
+            }
+            for (; need; need &= need - 1) {
+                const int pr = __builtin_ctz((unsigned)need);
                 cf2 *q = reinterpret_cast<cf2 *>(as_const(&m.leaves[leaf].pair[pr]));
                 const f2 d2 = tri_dist2_pair(p, q);
                 const f2 fc = q[22];

@@ -247,6 +247,7 @@ struct HostArrays {
     std::vector<float> vn;
     std::vector<BvhNode> nodes;
     std::vector<LeafRec> leafrec;
+    std::vector<PairBox> pbox;
     std::vector<TriRec> tris;
     std::vector<TriAttr> attr;
     std::vector<int32_t> order, face2slot, bin_start, bin_slots;
@@ -332,6 +333,24 @@ int host_build(const std::vector<float> &verts, const std::vector<int64_t> &face
             for (int fld = 0; fld < 24; ++fld) leafrec[L].pair[t >> 1][fld][t & 1] = src[fld];
         }
     }
+    // the oriented box of every leaf pair (short leaves repeat their last pair's box, a pair of one triangle holds it twice)
+    std::vector<PairBox> &pbox = out.pbox;
+    pbox.resize(F);
+    memset((void *)pbox.data(), 0, sizeof(PairBox) * F);
+    for (int64_t L = 0; L < F; ++L) {
+        const int cnt = hb.leaf_cnt[L];
+        for (int pr = 0; pr < (cnt ? 2 : 0); ++pr) {
+            const int t0 = std::min(2 * pr, (cnt - 1) & ~1);
+            const int64_t p0 = L + t0, p1 = L + std::min(t0 + 1, cnt - 1);
+            float v[6][3], rec[15];
+            for (int k = 0; k < 3; ++k) {
+                v[0][k] = tris[p0].a[k]; v[1][k] = tris[p0].b[k]; v[2][k] = tris[p0].c[k];
+                v[3][k] = tris[p1].a[k]; v[4][k] = tris[p1].b[k]; v[5][k] = tris[p1].c[k];
+            }
+            pair_box_setup(v, rec);
+            for (int fld = 0; fld < 15; ++fld) pbox[L].f[fld][pr] = rec[fld];
+        }
+    }
 
     // (y,z) ray bins: every triangle is listed in all cells its (y,z) bounding box, grown by eps, overlaps.
     // bin_cell_of() is monotone, so a query point inside the grown box lands in one of those cells; eps covers the
@@ -382,6 +401,7 @@ int emit_arena(const HostArrays &h, const MeshLayout &Ly, Put put_fn)
     if ((rc = put_fn(Ly.dyn, dynv.data(), sizeof(MeshDyn))) || (rc = put_fn(Ly.vnormals, h.vn.data(), h.vn.size() * 4)) ||
         (rc = put_fn(Ly.nodes, h.nodes.data(), h.nodes.size() * sizeof(BvhNode))) ||
         (rc = put_fn(Ly.leaves, h.leafrec.data(), h.leafrec.size() * sizeof(LeafRec))) ||
+        (rc = put_fn(Ly.pbox, h.pbox.data(), h.pbox.size() * sizeof(PairBox))) ||
         (rc = put_fn(Ly.tris, h.tris.data(), h.tris.size() * sizeof(TriRec))) || (rc = put_fn(Ly.attr, h.attr.data(), h.attr.size() * sizeof(TriAttr))) ||
         (rc = put_fn(Ly.slot2face, h.order.data(), h.order.size() * 4)) || (rc = put_fn(Ly.face2slot, h.face2slot.data(), h.face2slot.size() * 4)) ||
         (rc = put_fn(Ly.bin_start, h.bin_start.data(), h.bin_start.size() * 4)) || (rc = put_fn(Ly.bin_slots, h.bin_slots.data(), h.bin_slots.size() * 4)))
@@ -553,7 +573,38 @@ extern "C" int icon_debug_host_mesh_build(const float *h_verts, int64_t V, const
     return emit_arena(h, Ly, [&](size_t off, const void *src, size_t bytes) -> int { if (bytes) memcpy(ar + off, src, bytes); return ICON_OK; });
 }
 
+// The pair-box rule on host data (no device needed): for pair i, with the six corners corners[i][6][3] (triangle 0, triangle 1),
+// rec[i][15] = pair_box_setup's record, kind[i] = kPairBox* and bound[i][j] = pair_box_bound - the very function the packet
+// walk evaluates, pairs 2k / 2k + 1 in the two packed components - at point j: pts[j] if shared_pts, else pts[i][j].
+extern "C" int icon_debug_pair_box(const float *corners, int64_t n_pairs, const float *pts, int64_t n_pts, int shared_pts,
+                                   float *rec, int32_t *kind, float *bound)
+{
+    ICON_ARG(corners && pts && rec && kind && bound && n_pairs >= 1 && n_pts >= 1, "icon_debug_pair_box: bad argument");
+    parallel_for((int)((n_pairs + 1) / 2), [&](int k) {
+        PairBox pb;
+        memset((void *)&pb, 0, sizeof(pb));
+        for (int s = 0; s < 2; ++s) {
+            const int64_t i = std::min<int64_t>(2 * (int64_t)k + s, n_pairs - 1);
+            float r[15];
+            kind[i] = pair_box_setup(reinterpret_cast<const float(*)[3]>(corners + 18 * i), r);
+            for (int f = 0; f < 15; ++f) { pb.f[f][s] = r[f]; rec[15 * i + f] = r[f]; }
+        }
+        const pbf2 *q = reinterpret_cast<const pbf2 *>(&pb);
+        for (int s = 0; s < 2; ++s) {
+            const int64_t i = 2 * (int64_t)k + s;
+            if (i >= n_pairs) break;
+            const float *pp = shared_pts ? pts : pts + 3 * n_pts * i;
+            for (int64_t j = 0; j < n_pts; ++j) {
+                const pbf2 b = pair_box_bound(q, pp[3 * j], pp[3 * j + 1], pp[3 * j + 2]);
+                bound[n_pts * i + j] = s ? b.y : b.x;
+            }
+        }
+    });
+    return ICON_OK;
+}
+
 // byte offsets of the arena sections (tests compare the arenas of the host and the device build):
+// (the pair boxes follow the leaves they are indexed like: bytes [leaves + 384 F rounded up to 256, tris) of entry 3's range)
 // out = [dyn, vnormals, nodes, leaves, tris, attr, slot2face, face2slot, bin_start, bin_slots, end of bin_slots, total]
 extern "C" int icon_debug_mesh_layout(int64_t V, int64_t F, int64_t out[12])
 {

@@ -44,7 +44,7 @@ struct BuildCtx {
     int32_t V, F, bound;
     MeshDyn *dyn; BuildHdr *hdr;
     int32_t *valence; uint8_t *leaf_cnt; BTask *tasks; uint32_t *hist; int32_t *cell_count, *cell_cursor;
-    float *vnormals; BvhNode *nodes; LeafRec *leaves; TriRec *tris; TriAttr *attr; int32_t *slot2face, *face2slot;
+    float *vnormals; BvhNode *nodes; LeafRec *leaves; PairBox *pbox; TriRec *tris; TriAttr *attr; int32_t *slot2face, *face2slot;
     int32_t *bin_start, *bin_slots;
     float *tbox, *cen; int32_t *order[2]; int32_t *adj; int32_t *chunkcnt; int32_t *subq; struct STask *sublist; uint32_t *bounds_part;
     int32_t nck; int64_t cells_cap, entries_cap;
@@ -713,6 +713,24 @@ __global__ __launch_bounds__(256) void k_tri_records(BuildCtx c)
     const int tend = (myt == cnt - 1) ? kLeafMax : myt + 1;    // short leaves repeat their last triangle
     for (int t = myt; t < tend; ++t)
         for (int fld = 0; fld < 24; ++fld) lr.pair[t >> 1][fld][t & 1] = src[fld];
+    // the oriented box of the pair this slot opens (its partner: the next slot of the leaf, or the triangle itself); the last
+    // pair of a short leaf is repeated
+    if ((myt & 1) == 0) {
+        float pv[6][3], rec[15];
+        for (int q = 0; q < 3; ++q) for (int k = 0; k < 3; ++k) { pv[q][k] = v[q][k]; pv[3 + q][k] = v[q][k]; }
+        if (myt + 1 < cnt) {
+            int id1[3]; float v1[3][3]; int bf1 = 0, bv1 = 0;
+            load_face(c, c.slot2face[p + 1], id1, v1, &bf1, &bv1);
+            for (int q = 0; q < 3; ++q) for (int k = 0; k < 3; ++k) pv[3 + q][k] = v1[q][k];
+        }
+        pair_box_setup(pv, rec);
+        PairBox &pb = c.pbox[leaf];
+        const int pend = (myt + 2 >= cnt) ? 2 : (myt >> 1) + 1;
+        for (int pr = myt >> 1; pr < pend; ++pr) {
+            for (int fld = 0; fld < 15; ++fld) pb.f[fld][pr] = rec[fld];
+            pb.f[15][pr] = 0.0f;
+        }
+    }
     // ray-bin cells covered by the (y,z) box of the triangle, grown by eps
     const BinGrid g = grid_of(c);
     int cy0, cy1, cz0, cz1;
@@ -889,6 +907,7 @@ void mesh_bind_arena(icon_mesh *m, const MeshLayout &L)
     d.leaves = reinterpret_cast<const LeafRec *>(b + L.leaves);
     d.dyn = m->d_dyn;
     d.n_tris = (int32_t)m->F;
+    d.pbox_off = pair_box_enabled() ? (int32_t)((L.pbox - L.leaves) / sizeof(PairBox)) : 0;
     d.bin_start = reinterpret_cast<const int32_t *>(b + L.bin_start);
     d.bin_slots = reinterpret_cast<const int32_t *>(b + L.bin_slots);
 }
@@ -906,7 +925,7 @@ int mesh_build_device(icon_mesh *m, const float *d_verts, const int64_t *d_faces
     c.tasks = reinterpret_cast<BTask *>(b + L.tasks); c.hist = reinterpret_cast<uint32_t *>(b + L.hist);
     c.cell_count = reinterpret_cast<int32_t *>(b + L.cell_count); c.cell_cursor = reinterpret_cast<int32_t *>(b + L.cell_cursor);
     c.vnormals = reinterpret_cast<float *>(b + L.vnormals); c.nodes = reinterpret_cast<BvhNode *>(b + L.nodes);
-    c.leaves = reinterpret_cast<LeafRec *>(b + L.leaves); c.tris = reinterpret_cast<TriRec *>(b + L.tris);
+    c.leaves = reinterpret_cast<LeafRec *>(b + L.leaves); c.pbox = reinterpret_cast<PairBox *>(b + L.pbox); c.tris = reinterpret_cast<TriRec *>(b + L.tris);
     c.attr = reinterpret_cast<TriAttr *>(b + L.attr); c.slot2face = reinterpret_cast<int32_t *>(b + L.slot2face);
     c.face2slot = reinterpret_cast<int32_t *>(b + L.face2slot); c.bin_start = reinterpret_cast<int32_t *>(b + L.bin_start);
     c.bin_slots = reinterpret_cast<int32_t *>(b + L.bin_slots); c.tbox = reinterpret_cast<float *>(b + L.tbox);

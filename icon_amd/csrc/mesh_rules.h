@@ -88,6 +88,140 @@ __host__ __device__ inline void tri_setup(const float *a, const float *b, const 
     t.face = face; t.pad = 0;
 }
 
+// ---- oriented box of a leaf pair (PairBox, common.h) ----------------------------------------------------------------------
+// A lower bound of the squared distance from a point to two triangles that the packet walk evaluates before the distance test
+// itself.  Frame: n = the normalised sum of the two area-weighted normals, u1 = the pair's longest edge with its n component
+// removed, u2 = n x u1 - tight along the normal, where an axis-aligned box of a slanted patch is not.  ANY orthonormal frame
+// gives a valid bound, so every doubtful case (zero area, collinear slivers, duplicates, opposed normals, a frame whose Gram
+// matrix is off by more than kPairBoxGram) takes the identity frame: the pair's AABB.  A pair with a non-finite corner, or
+// whose box overflows float32, gets infinite extents and is never culled.
+// The contract (DESIGN.md "BVH conservativeness"): the float32 value of pair_box_bound never exceeds the real squared distance
+// from the point to either triangle.  What pays for the rounding: the stored axes are the unit vectors TIMES kPairBoxScale (the
+// sum of squares comes out 2e-4 low - the frame's non-orthonormality, the sum's own rounding, and the rounding of the
+// projections of a point that is far from the box relative to its size), and the half extents are inflated by kPairBoxEps
+// times their sum (the rounding of the projections of a point nearer than that, and of the extents themselves).
+constexpr float kPairBoxScale = 0.9999f;
+constexpr float kPairBoxGram = 4e-6f;
+constexpr float kPairBoxEps = 4e-6f;
+constexpr float kPairBoxFloor = 1e-15f;
+enum { kPairBoxOriented = 0, kPairBoxAabb = 1, kPairBoxNever = 2 };
+
+__host__ __device__ inline bool pb_finite(float v)
+{
+    uint32_t u; __builtin_memcpy(&u, &v, 4);
+    return (u & 0x7f800000u) != 0x7f800000u;
+}
+__host__ __device__ inline void pb_cross(const float *a, const float *b, float *r)
+{
+    r[0] = fmaf(a[1], b[2], -(a[2] * b[1])); r[1] = fmaf(a[2], b[0], -(a[0] * b[2])); r[2] = fmaf(a[0], b[1], -(a[1] * b[0]));
+}
+// v: the six corners (triangle 0: v[0..2], triangle 1: v[3..5]; a pair of one triangle passes it twice).
+// out[15]: centre, the three scaled axes, the inflated half extents (PairBox fields 0..14).  Returns kPairBox*.
+__host__ __device__ inline int pair_box_setup(const float v[6][3], float out[15])
+{
+    bool fin = true;
+    for (int i = 0; i < 6; ++i) for (int k = 0; k < 3; ++k) fin = fin && pb_finite(v[i][k]);
+    float ax[3][3] = {{1.f, 0.f, 0.f}, {0.f, 1.f, 0.f}, {0.f, 0.f, 1.f}};
+    int kind = kPairBoxAabb;
+    if (fin) {
+        // the frame
+        float e[6][3], l2[6];
+        for (int t = 0; t < 2; ++t)
+            for (int k = 0; k < 3; ++k) {
+                e[3 * t][k] = v[3 * t + 1][k] - v[3 * t][k]; e[3 * t + 1][k] = v[3 * t + 2][k] - v[3 * t][k];
+                e[3 * t + 2][k] = v[3 * t + 2][k] - v[3 * t + 1][k];
+            }
+        int best = 0;
+        for (int i = 0; i < 6; ++i) { l2[i] = dot3r(e[i], e[i]); if (l2[i] > l2[best]) best = i; }
+        const float L2 = l2[best];
+        float n0[3], n1[3], n[3];
+        pb_cross(e[0], e[1], n0); pb_cross(e[3], e[4], n1);
+        for (int k = 0; k < 3; ++k) n[k] = n0[k] + n1[k];
+        const float nn = dot3r(n, n);
+        if (nn > 1e-10f * (L2 * L2)) {
+            const float ln = sqrtf(nn);
+            float a0[3], u[3], a1[3], a2[3];
+            for (int k = 0; k < 3; ++k) a0[k] = n[k] / ln;
+            const float en = dot3r(e[best], a0);
+            for (int k = 0; k < 3; ++k) u[k] = fmaf(-en, a0[k], e[best][k]);
+            const float uu = dot3r(u, u);
+            if (uu > 1e-10f * L2) {
+                const float lu = sqrtf(uu);
+                for (int k = 0; k < 3; ++k) a1[k] = u[k] / lu;
+                pb_cross(a0, a1, a2);
+                const float g[6] = {dot3r(a0, a0) - 1.0f, dot3r(a1, a1) - 1.0f, dot3r(a2, a2) - 1.0f, dot3r(a0, a1), dot3r(a0, a2), dot3r(a1, a2)};
+                bool ok = true;
+                for (int i = 0; i < 6; ++i) ok = ok && (fabsf(g[i]) <= kPairBoxGram);      // (a NaN fails)
+                if (ok) {
+                    for (int k = 0; k < 3; ++k) { ax[0][k] = a0[k]; ax[1][k] = a1[k]; ax[2][k] = a2[k]; }
+                    kind = kPairBoxOriented;
+                }
+            }
+        }
+    }
+    for (int attempt = 0; attempt < 2 && fin; ++attempt) {
+        // centre: the middle of the corners' AABB, moved to the middle of their extent along every axis
+        float c[3];
+        for (int k = 0; k < 3; ++k) {
+            float lo = v[0][k], hi = v[0][k];
+            for (int i = 1; i < 6; ++i) { lo = fminf(lo, v[i][k]); hi = fmaxf(hi, v[i][k]); }
+            c[k] = canon(0.5f * (lo + hi));
+        }
+        float mid[3];
+        for (int a = 0; a < 3; ++a) {
+            float lo = 0.f, hi = 0.f;
+            for (int i = 0; i < 6; ++i) {
+                const float d[3] = {v[i][0] - c[0], v[i][1] - c[1], v[i][2] - c[2]};
+                const float t = dot3r(ax[a], d);
+                lo = i ? fminf(lo, t) : t; hi = i ? fmaxf(hi, t) : t;
+            }
+            mid[a] = 0.5f * (lo + hi);
+        }
+        for (int k = 0; k < 3; ++k) c[k] = canon(fmaf(mid[2], ax[2][k], fmaf(mid[1], ax[1][k], fmaf(mid[0], ax[0][k], c[k]))));
+        // the stored axes and the extents of the corners along THEM, about the stored centre
+        float h[3];
+        for (int a = 0; a < 3; ++a) {
+            for (int k = 0; k < 3; ++k) out[3 + 3 * a + k] = canon(ax[a][k] * kPairBoxScale);
+            float m = 0.f;
+            for (int i = 0; i < 6; ++i) {
+                const float d[3] = {v[i][0] - c[0], v[i][1] - c[1], v[i][2] - c[2]};
+                m = fmaxf(m, fabsf(dot3r(out + 3 + 3 * a, d)));
+            }
+            h[a] = m;
+        }
+        const float pad = fmaf(kPairBoxEps, (h[0] + h[1]) + h[2], kPairBoxFloor);
+        bool ok = true;
+        for (int k = 0; k < 3; ++k) { out[k] = c[k]; out[12 + k] = h[k] + pad; ok = ok && pb_finite(c[k]) && pb_finite(out[12 + k]); }
+        if (ok) return kind;
+        if (kind == kPairBoxAabb) break;
+        kind = kPairBoxAabb;                                         // (the oriented frame overflowed: once more with the identity)
+        for (int a = 0; a < 3; ++a) for (int k = 0; k < 3; ++k) ax[a][k] = (a == k) ? 1.f : 0.f;
+    }
+    for (int k = 0; k < 3; ++k) { out[k] = 0.f; out[12 + k] = __builtin_inff(); }
+    for (int a = 0; a < 3; ++a) for (int k = 0; k < 3; ++k) out[3 + 3 * a + k] = (a == k) ? kPairBoxScale : 0.f;
+    return kPairBoxNever;
+}
+
+// Both pair boxes of a leaf at once (packed f32: the operand shape of v_pk_add / v_pk_mul / v_pk_fma): q = the 16 two-float
+// fields of a PairBox, (px, py, pz) the point.  Component i = lower bound of the squared distance to the triangles of pair i:
+// the squared distance to the box in its own frame.  No square root; NaN projections (a NaN point) give 0 = "not culled".
+typedef float pbf2 __attribute__((ext_vector_type(2)));
+template <class Ptr>
+__host__ __device__ inline pbf2 pair_box_bound(Ptr q, float px, float py, float pz)
+{
+    pbf2 bx, by, bz; bx.x = px; bx.y = px; by.x = py; by.y = py; bz.x = pz; bz.y = pz;
+    const pbf2 dx = bx - q[0], dy = by - q[1], dz = bz - q[2];
+    const pbf2 t0 = __builtin_elementwise_fma(q[5], dz, __builtin_elementwise_fma(q[4], dy, q[3] * dx));
+    const pbf2 t1 = __builtin_elementwise_fma(q[8], dz, __builtin_elementwise_fma(q[7], dy, q[6] * dx));
+    const pbf2 t2 = __builtin_elementwise_fma(q[11], dz, __builtin_elementwise_fma(q[10], dy, q[9] * dx));
+    const pbf2 h0 = q[12], h1 = q[13], h2 = q[14];
+    pbf2 e0, e1, e2;
+    e0.x = fmaxf(fabsf(t0.x) - h0.x, 0.0f); e0.y = fmaxf(fabsf(t0.y) - h0.y, 0.0f);
+    e1.x = fmaxf(fabsf(t1.x) - h1.x, 0.0f); e1.y = fmaxf(fabsf(t1.y) - h1.y, 0.0f);
+    e2.x = fmaxf(fabsf(t2.x) - h2.x, 0.0f); e2.y = fmaxf(fabsf(t2.y) - h2.y, 0.0f);
+    return __builtin_elementwise_fma(e2, e2, __builtin_elementwise_fma(e1, e1, e0 * e0));
+}
+
 // ---- arena layout (one device allocation per mesh) ------------------------------------------------------------
 constexpr int kTopLevels = 7;          // BVH levels 0..6 are split by multi-workgroup kernels (k_bvh_bin / k_bvh_part)
 constexpr int kSubMax = 256;           // subtrees of at most this many triangles are finished by ONE workgroup in LDS (k_bvh_sub)
@@ -112,7 +246,7 @@ struct BuildHdr {                      // zeroed before every build
 
 struct MeshLayout {
     size_t dyn, hdr, valence, leaf_cnt, tasks, hist, cell_count, cell_cursor, zero_end;   // [dyn, zero_end) is zeroed per build
-    size_t vnormals, nodes, leaves, tris, attr, slot2face, face2slot, bin_start, bin_slots;
+    size_t vnormals, nodes, leaves, pbox, tris, attr, slot2face, face2slot, bin_start, bin_slots;
     size_t tbox, cen, order0, order1, adj, chunkcnt, subq, sublist, bounds_part, total;
     int64_t nck;                       // chunk records per top level
 };
@@ -136,6 +270,7 @@ inline MeshLayout mesh_layout(int64_t V, int64_t F)
     L.vnormals = take(sizeof(float) * 3 * V);
     L.nodes = take(sizeof(BvhNode) * F);
     L.leaves = take(sizeof(LeafRec) * F);
+    L.pbox = take(sizeof(PairBox) * F);                        // behind the leaves it is indexed like (icon_debug_mesh_layout: part of entry 3's range)
     L.tris = take(sizeof(TriRec) * F);
     L.attr = take(sizeof(TriAttr) * F);
     L.slot2face = take(sizeof(int32_t) * F);

@@ -192,6 +192,25 @@ __global__ __launch_bounds__(kBlock) void k_traversal_stats(MeshDev m, LatticeMa
     if ((threadIdx.x & 63) == 0) atomicMax(&out[4], (unsigned long long)(nn + nt));      // the longest walk: what a latency-bound launch waits for
 }
 
+// diagnostics: what the pair boxes do to the lattice walk - per packet, the nodes visited, the leaf pairs offered to the
+// distance test and the pairs tested (icon_debug_pair_stats; tools/pair_box_model.py predicts the last two on the CPU)
+__global__ __launch_bounds__(kBlock) void k_pair_stats(MeshDev m, LatticeMap L, unsigned long long *out /* [4] */)
+{
+    __shared__ int lds[(kBlock / 64) * kStackDepth];
+    L = lattice_trim(L, m);
+    if ((int)blockIdx.x >= L.tx * L.ty * L.tz) return;
+    int ix, iy, iz, cx, cy, cz;
+    const bool live = lattice_point(L, ix, iy, iz);
+    lattice_clamp(L, ix, iy, iz, cx, cy, cz);
+    const f3 p = lattice_world(L.res, cx, cy, cz + L.z0);
+    int nn = 0, nt = 0, no = 0, ns = 0;
+    nearest_packet<true>(m, p, live, lds + (threadIdx.x >> 6) * kStackDepth, &nn, &nt, INFINITY, nullptr, packet_center_lane(L), false, 0, &no, &ns);
+    if ((threadIdx.x & 63) == 0) {
+        atomicAdd(&out[0], 1ull); atomicAdd(&out[1], (unsigned long long)nn);
+        atomicAdd(&out[2], (unsigned long long)no); atomicAdd(&out[3], (unsigned long long)ns);
+    }
+}
+
 // one thread per (y, z) row of the slab: triangles whose (y,z) projection covers the row
 __global__ __launch_bounds__(kBlock) void k_row_crossings(MeshDev m, LatticeMap L, int32_t *row_count, int32_t *row_slots, LatticeFast *lf)
 {
@@ -822,6 +841,12 @@ namespace icon {
 // ---- shared walks: error record and test switches ------------------------------------------------------------------------
 int g_share_ring = 0, g_share_lose = 0, g_share_spin_log2 = 0;     // icon_debug_set_option; all zero in production
 int g_lattice_fast = -1;                                          // -1: read ICON_AMD_LATTICE_FAST once (default on)
+int g_pair_box = -1;                                               // -1: read ICON_AMD_PAIR_BOX once (default on); 0 / 1: icon_debug_set_option
+int pair_box_enabled()
+{
+    if (g_pair_box < 0) g_pair_box = getenv("ICON_AMD_PAIR_BOX") ? (atoi(getenv("ICON_AMD_PAIR_BOX")) != 0) : 1;
+    return g_pair_box;
+}
 int g_share_waves = -2;                                           // -2: read ICON_AMD_SHARE once; -1: by launch size; 1 / 4 / 8 / 16: forced
 int share_waves_override()
 {
@@ -1453,6 +1478,26 @@ extern "C" int icon_debug_traversal_stats(const icon_mesh_t *mesh, int res, int 
     return ICON_OK;
 }
 
+// out = [packets, nodes visited, leaf pairs offered to the distance test, leaf pairs tested], summed over the packets of the
+// planes [z0, z1) of the res^3 lattice, for the walk this mesh runs ("pair_box" as it was when the mesh was created)
+extern "C" int icon_debug_pair_stats(const icon_mesh_t *mesh, int res, int z0, int z1, uint64_t out[4])
+{
+    ICON_ARG(mesh && out, "icon_debug_pair_stats: null argument");
+    LatticeMap L;
+    int rc = lattice_map(res, z0, z1, mesh, 0.05f, true, &L);
+    if (rc) return rc;
+    unsigned long long *d = nullptr;
+    ICON_HIP(hipMalloc((void **)&d, 4 * sizeof(unsigned long long)));
+    ICON_HIP(hipMemset(d, 0, 4 * sizeof(unsigned long long)));
+    hipLaunchKernelGGL(k_pair_stats, dim3((unsigned)(L.tx * L.ty * L.tz)), dim3(kBlock), 0, 0, mesh->dev, L, d);
+    unsigned long long h[4];
+    hipError_t e = hipMemcpy(h, d, sizeof(h), hipMemcpyDeviceToHost);
+    (void)hipFree(d);
+    if (e != hipSuccess) return fail(ICON_ERR_HIP, std::string("pair stats: ") + hipGetErrorString(e));
+    for (int k = 0; k < 4; ++k) out[k] = h[k];
+    return ICON_OK;
+}
+
 extern "C" int icon_grid_eval_slab(const icon_mesh_t *mesh, const icon_feat_t *feat, const icon_mlp_t *mlp,
                                    int prior_type, float sdf_clip, int cmap_mode,
                                    int res, int z0, int z1, float *d_occ,
@@ -1475,7 +1520,8 @@ extern "C" int icon_work_status(icon_work_t *work)
     return work_check_err(work);
 }
 
-// test / A-B switches by name (process-wide): "lattice_fast" 0 / 1; "share_waves" wavefronts per shared walk (-1 = by launch size;
+// test / A-B switches by name (process-wide): "pair_box" 0 / 1 - the packet walk culls leaf pairs by their oriented boxes (meshes
+// and mesh batches created AFTERWARDS; 0: they run the walk without the cull); "lattice_fast" 0 / 1; "share_waves" wavefronts per shared walk (-1 = by launch size;
 // 4: the adaptive schedule's searches only); "share_ring" forced ring size of the shared walks (0 = 64),
 // "share_lose_push" the ticket of the push that is announced but never stored (0 = none), "share_spin_log2" wait bound 2^n polls
 // (0 = 2^18).  Production leaves all of them alone.
@@ -1485,6 +1531,7 @@ extern "C" int icon_debug_set_option(const char *key, int value)
     const std::string k(key);
     if (k == "lattice_fast") g_lattice_fast = value ? 1 : 0;
     else if (k == "share_waves") { ICON_ARG(value == -1 || value == 1 || value == 4 || value == 8 || value == 16, "share_waves: -1 (by launch size), 1, 4, 8 or 16"); g_share_waves = value; }
+    else if (k == "pair_box") g_pair_box = value ? 1 : 0;
     else if (k == "share_ring") { ICON_ARG(value == 0 || (value >= 2 && value <= 64 && (value & (value - 1)) == 0), "share_ring: 0 or a power of two in 2..64"); g_share_ring = value; }
     else if (k == "share_lose_push") { ICON_ARG(value >= 0, "share_lose_push: a ticket >= 1, or 0"); g_share_lose = value; }
     else if (k == "share_spin_log2") { ICON_ARG(value >= 0 && value < 30, "share_spin_log2: 0..29"); g_share_spin_log2 = value; }

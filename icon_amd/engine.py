@@ -137,6 +137,16 @@ class MeshHandle(_Handle):
         return dict(waves=arr[0], nodes=arr[1], tris=arr[2], nodes_per_wave=arr[1] / max(arr[0], 1),
                     tris_per_wave=arr[2] / max(arr[0], 1), longest_walk=arr[3])
 
+    def pair_stats(self, res: int, z0: int = 0, z1: Optional[int] = None) -> dict:
+        """the lattice walk's leaf work per 4^3 packet: nodes visited, leaf pairs offered to the distance test, pairs tested
+        (fewer than offered when the mesh was created with the "pair_box" option on: the oriented-box cull)"""
+        arr = (C.c_uint64 * 4)()
+        check(_lib.lib().icon_debug_pair_stats(self.h, C.c_int(res), C.c_int(z0), C.c_int(res if z1 is None else z1), arr),
+              "icon_debug_pair_stats")
+        n = max(arr[0], 1)
+        return dict(packets=arr[0], nodes=arr[1], pairs_offered=arr[2], pairs_tested=arr[3], nodes_per_packet=arr[1] / n,
+                    pairs_offered_per_packet=arr[2] / n, pairs_tested_per_packet=arr[3] / n)
+
     def sdf_query(self, points: torch.Tensor, search: str = "bvh"):
         """cal_sdf_batch (lib/dataset/mesh_util.py:357-396) for points [N,3] ->
         dict(sdf [N], norm [N,3], cmap [N,3], vis [N], face [N] i64, inside [N] bool)"""

@@ -416,6 +416,11 @@ int icon_work_set_tie_rule(icon_work_t *work, int rule, int ulps);
  * tested, both summed over wavefronts (every visit serves all lanes of the wavefront), out[3] = nodes + triangles of the
  * LONGEST walk (what a latency-bound launch - fewer packets than wave slots - waits for). */
 int icon_debug_traversal_stats(const icon_mesh_t *mesh, int res, int z0, int z1, uint64_t out[4]);
+/* the lattice walk's leaf work: out = [packets, nodes visited, leaf pairs offered to the distance test, leaf pairs tested] */
+int icon_debug_pair_stats(const icon_mesh_t *mesh, int res, int z0, int z1, uint64_t out[4]);
+/* host only: the oriented-box rule of the leaf pairs (record, kind 0 oriented / 1 AABB / 2 never culled, lower bounds of d^2) */
+int icon_debug_pair_box(const float *corners, int64_t n_pairs, const float *pts, int64_t n_pts, int shared_pts,
+                        float *rec, int32_t *kind, float *bound);
 
 /* Seg3dLossless._forward_faster's None rule (lib/common/seg3d_lossless.py:173-177: the call returns None when nothing exceeds
  * 0.5 on the COARSEST lattice) for a dense device volume d_occ [res,res,res]: the coarsest lattice is the sub-lattice of strides

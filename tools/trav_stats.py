@@ -6,6 +6,9 @@ a = synth.make_assets("body"); T=lambda x: torch.from_numpy(x).cuda()
 mesh = MeshHandle(T(a.smpl_verts), T(a.smpl_faces), T(a.smpl_cmap), T(a.smpl_vis))
 for res in (33, 65, 129, 257):
     print(res, mesh.traversal_stats(res))
+    ps = mesh.pair_stats(res)     # the oriented-box cull of the leaf pairs (ICON_AMD_PAIR_BOX=0: off); tools/pair_box_model.py predicts it
+    print(res, f"nodes / packet {ps['nodes_per_packet']:.1f}, leaf pairs offered / packet {ps['pairs_offered_per_packet']:.1f}, "
+               f"pairs tested / packet {ps['pairs_tested_per_packet']:.1f}")
 import time
 for n in (36000, 100000, 1000000):
     pts = (torch.rand((n, 3), device="cuda") * 2 - 1)
