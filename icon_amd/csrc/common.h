@@ -40,7 +40,10 @@ int fail(int code, const std::string &msg);
 struct alignas(64) BvhNode {
     float lo[3][2], hi[3][2];   // [axis][child]: the two children's bounds interleaved (packed-f32 operands)
     int32_t child0, child1;
-    int32_t pad[2];
+    // the same two references as the packet walk follows them when the mesh walks on node boxes (mesh_rules.h: node box records): an
+    // inner child that is an oriented parent carries kNodeBoxFlag - the walk then reads that child's PairBox-shaped record instead of
+    // its BvhNode.  Same 64-byte line as the boxes: an AABB visit costs no extra load.  Every other reader uses child0 / child1.
+    int32_t nb_child[2];
 };
 static_assert(sizeof(BvhNode) == 64, "BvhNode must be 64 bytes");
 
@@ -90,6 +93,8 @@ static_assert(sizeof(LeafRec) == 384, "LeafRec must be 384 bytes");
 // pairs no lane can still need (geom_device.h: pair_box_bound).  Fields: 0-2 centre, 3-5 / 6-8 / 9-11 the three axes (unit vectors
 // times kPairBoxScale), 12-14 the half extents along them (inflated), 15 unused (0).  Short leaves repeat their last pair's
 // box.  mesh_rules.h: pair_box_setup, DESIGN.md "BVH conservativeness".
+// The node boxes (mesh_rules.h: node_box_make) use the same layout, indexed by node id: the two components are the two CHILDREN of an
+// oriented parent, field 15 holds their references (bit patterns).
 struct alignas(32) PairBox {
     float f[16][2];
 };
@@ -144,6 +149,7 @@ struct MeshDev {
     const MeshDyn *dyn;         // device
     int32_t n_tris;             // triangle slots = F
     int32_t pbox_off;           // the PairBox section: (const PairBox *)leaves + pbox_off; 0 = the walk tests every pair ("pair_box" off)
+    int32_t nbox_off;           // the node-box section (PairBox records by node id), same addressing; 0 = the walk uses AABBs only ("node_box" off)
     // ray bins over (y, z)
     const int32_t *bin_start;   // [gy*gz + 1]
     const int32_t *bin_slots;   // triangle slots
@@ -404,6 +410,7 @@ int work_share_dbg(icon_work *w, ShareDbg *out);
 int work_check_err(icon_work *w);
 extern int g_qc_lanes;                // query_color.hip: lanes per face of the colour call's rasteriser ("qc_lanes"; 0 = default)
 extern int g_rn_lanes;                // render_normal.hip: lanes per face of the renderer's rasteriser ("rn_lanes"; 0 = default)
+int node_box_enabled();               // ICON_AMD_NODE_BOX / icon_debug_set_option("node_box"): likewise for the oriented boxes of the bottom inner nodes
 int pair_box_enabled();               // ICON_AMD_PAIR_BOX / icon_debug_set_option("pair_box"): meshes created while it is 0 walk without the cull
 int share_waves_override();           // ICON_AMD_SHARE / icon_debug_set_option("share_waves"): -1 = by launch size
 }  // namespace icon

@@ -258,7 +258,8 @@ template <bool STATS = false, bool TIES = false>
 __device__ __forceinline__ Nearest nearest_packet(const MeshDev &m, f3 p, bool live, int *wstack /* LDS, kStackDepth ints of this wave */,
                                                   int *n_nodes = nullptr, int *n_tris = nullptr, float thr0 = INFINITY,
                                                   unsigned long long *runner_up = nullptr, int center_lane = 21,
-                                                  bool have_root = false, int root = 0, int *n_offered = nullptr, int *n_tested = nullptr)
+                                                  bool have_root = false, int root = 0, int *n_offered = nullptr, int *n_tested = nullptr,
+                                                  int *n_leaves = nullptr, int *n_obox = nullptr)
 {
     Nearest nr; nr.d2 = INFINITY; nr.slot = 0; nr.face = 0x7fffffff;
     // the leaf pairs' oriented boxes (PairBox), or null: "pair_box" off - every pair of a visited leaf is tested (wave-uniform)
@@ -268,11 +269,19 @@ __device__ __forceinline__ Nearest nearest_packet(const MeshDev &m, f3 p, bool l
     float thr = live ? thr0 : -INFINITY;
     int sp = 0;
     int cur = have_root ? root : mesh_root(m);        // (wave-uniform choice; the caller that holds the root in a register passes it)
+    // the node boxes (PairBox records by node id), or null: "node_box" off - AABBs all the way down.  A reference >= 0 with
+    // kNodeBoxFlag names an oriented parent: a node whose children both hold <= kNodeBoxMaxTris triangles and are tested by one
+    // oriented box each (mesh_rules.h).  The flag travels with the reference - in the parent's record (an AABB parent: the spare
+    // words of its BvhNode, same cache line; an oriented parent: field 15 of its box record) and on the stack; only the root's is
+    // worked out here, from its split point.  All of it wave-uniform.
+    const PairBox *nbox = m.nbox_off ? reinterpret_cast<const PairBox *>(m.leaves) + m.nbox_off : nullptr;
+    if (nbox) cur = node_ref_flagged(cur, 0, m.n_tris);
     while (true) {
         if (cur < 0) {
             const int code = ~cur;
             const int leaf = code >> 2, cnt = (code & 3) + 1;
             if (STATS) *n_tris += cnt;
+            if (STATS && n_leaves) ++*n_leaves;
             const int npairs = __builtin_amdgcn_readfirstlane((cnt + 1) >> 1);      // 1 or 2, wave-uniform (scalar loop counter)
             // Most pairs of a visited leaf are out of every lane's reach (the leaf's AABB admits a slanted patch from far away:
             // DESIGN.md 4.1): both pairs' oriented boxes in one packed evaluation, then the distance test only for the pairs
@@ -317,10 +326,21 @@ __device__ __forceinline__ Nearest nearest_packet(const MeshDev &m, f3 p, bool l
             cur = __builtin_amdgcn_readfirstlane(wstack[--sp]);
         } else {
             if (STATS) ++*n_nodes;
-            cf2 *q = reinterpret_cast<cf2 *>(as_const(m.nodes + cur));   // lo.x lo.y lo.z hi.x hi.y hi.z (children 0,1), ids
-            const f2 dd = box_dist2_pair(q, p);
+            // both children's lower bounds in one packed evaluation: box distances of an AABB parent, pair_box_bound of an oriented
+            // parent's record - either way <= the real d^2 of every triangle below the child, which is all the vote relies on
+            f2 dd, ids;
+            if (cur & kNodeBoxFlag) {
+                if (STATS && n_obox) ++*n_obox;
+                cf2 *q = reinterpret_cast<cf2 *>(as_const(nbox + (cur & ~kNodeBoxFlag)));
+                dd = pair_box_bound(q, p.x, p.y, p.z);
+                ids = q[15];
+            } else {
+                cf2 *q = reinterpret_cast<cf2 *>(as_const(m.nodes + cur));   // lo.x lo.y lo.z hi.x hi.y hi.z (children 0,1), ids, walk ids
+                dd = box_dist2_pair(q, p);
+                const f2 plain = q[6], walk = q[7];                          // (one 64-byte scalar load either way)
+                ids = nbox ? walk : plain;
+            }
             const float d0 = dd.x, d1 = dd.y;
-            const f2 ids = q[6];
             const int c0 = __float_as_int(ids.x), c1 = __float_as_int(ids.y);
             const bool v0 = __any(d0 <= thr), v1 = __any(d1 <= thr);
             if (v0 && v1) {

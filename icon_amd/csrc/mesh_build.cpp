@@ -247,7 +247,7 @@ struct HostArrays {
     std::vector<float> vn;
     std::vector<BvhNode> nodes;
     std::vector<LeafRec> leafrec;
-    std::vector<PairBox> pbox;
+    std::vector<PairBox> pbox, nbox;
     std::vector<TriRec> tris;
     std::vector<TriAttr> attr;
     std::vector<int32_t> order, face2slot, bin_start, bin_slots;
@@ -351,6 +351,15 @@ int host_build(const std::vector<float> &verts, const std::vector<int64_t> &face
             for (int fld = 0; fld < 15; ++fld) pbox[L].f[fld][pr] = rec[fld];
         }
     }
+    // the node boxes: every inner node's walk references, and the record of every oriented parent (node id = its split point - 1:
+    // the slot behind it starts a leaf)
+    std::vector<PairBox> &nbox = out.nbox;
+    nbox.resize(F);
+    memset((void *)nbox.data(), 0, sizeof(PairBox) * F);
+    for (int64_t id = 0; id + 1 < F; ++id) {
+        if (!hb.leaf_cnt[id + 1]) continue;
+        ICON_ARG(node_box_make(hb.nodes.data(), tris.data(), (int)F, (int)id, hb.nodes[id].nb_child, nbox[id]) != 0, "icon_mesh_create: malformed tree (node boxes)");
+    }
 
     // (y,z) ray bins: every triangle is listed in all cells its (y,z) bounding box, grown by eps, overlaps.
     // bin_cell_of() is monotone, so a query point inside the grown box lands in one of those cells; eps covers the
@@ -402,6 +411,7 @@ int emit_arena(const HostArrays &h, const MeshLayout &Ly, Put put_fn)
         (rc = put_fn(Ly.nodes, h.nodes.data(), h.nodes.size() * sizeof(BvhNode))) ||
         (rc = put_fn(Ly.leaves, h.leafrec.data(), h.leafrec.size() * sizeof(LeafRec))) ||
         (rc = put_fn(Ly.pbox, h.pbox.data(), h.pbox.size() * sizeof(PairBox))) ||
+        (rc = put_fn(Ly.nbox, h.nbox.data(), h.nbox.size() * sizeof(PairBox))) ||
         (rc = put_fn(Ly.tris, h.tris.data(), h.tris.size() * sizeof(TriRec))) || (rc = put_fn(Ly.attr, h.attr.data(), h.attr.size() * sizeof(TriAttr))) ||
         (rc = put_fn(Ly.slot2face, h.order.data(), h.order.size() * 4)) || (rc = put_fn(Ly.face2slot, h.face2slot.data(), h.face2slot.size() * 4)) ||
         (rc = put_fn(Ly.bin_start, h.bin_start.data(), h.bin_start.size() * 4)) || (rc = put_fn(Ly.bin_slots, h.bin_slots.data(), h.bin_slots.size() * 4)))
@@ -603,8 +613,34 @@ extern "C" int icon_debug_pair_box(const float *corners, int64_t n_pairs, const 
     return ICON_OK;
 }
 
+// The node-box rule on host data: rec[15] = range_box_setup's record of the n_tris triangles tris[i][3][3] (one slot range), *kind =
+// kPairBox*.  And pair_box_bound - the function the packet walk evaluates - on PairBox-shaped records as an arena holds them:
+// recs[i][16][2], bound[i][c][j] = component c of record i at point j (pts[j] if shared_pts, else pts[i][j]).
+extern "C" int icon_debug_range_box(const float *tris, int64_t n_tris, float *rec, int32_t *kind)
+{
+    ICON_ARG(tris && rec && kind && n_tris >= 1 && n_tris <= (1 << 20), "icon_debug_range_box: bad argument");
+    *kind = range_box_setup(tris, 9, (int)n_tris, rec);
+    return ICON_OK;
+}
+extern "C" int icon_debug_box_bound(const float *recs, int64_t n_recs, const float *pts, int64_t n_pts, int shared_pts, float *bound)
+{
+    ICON_ARG(recs && pts && bound && n_recs >= 1 && n_recs <= (1 << 24) && n_pts >= 1, "icon_debug_box_bound: bad argument");
+    parallel_for((int)n_recs, [&](int i) {
+        PairBox pb;
+        memcpy((void *)&pb, recs + 32 * (size_t)i, sizeof(pb));
+        const pbf2 *q = reinterpret_cast<const pbf2 *>(&pb);
+        const float *pp = shared_pts ? pts : pts + 3 * n_pts * (size_t)i;
+        for (int64_t j = 0; j < n_pts; ++j) {
+            const pbf2 b = pair_box_bound(q, pp[3 * j], pp[3 * j + 1], pp[3 * j + 2]);
+            bound[(2 * (size_t)i) * n_pts + j] = b.x; bound[(2 * (size_t)i + 1) * n_pts + j] = b.y;
+        }
+    });
+    return ICON_OK;
+}
+
 // byte offsets of the arena sections (tests compare the arenas of the host and the device build):
-// (the pair boxes follow the leaves they are indexed like: bytes [leaves + 384 F rounded up to 256, tris) of entry 3's range)
+// (the pair boxes follow the leaves they are indexed like, the node boxes - indexed by node id - follow them: bytes
+//  [leaves + 384 F rounded up to 256, tris) of entry 3's range hold 128 F bytes of each, each rounded up to 256)
 // out = [dyn, vnormals, nodes, leaves, tris, attr, slot2face, face2slot, bin_start, bin_slots, end of bin_slots, total]
 extern "C" int icon_debug_mesh_layout(int64_t V, int64_t F, int64_t out[12])
 {

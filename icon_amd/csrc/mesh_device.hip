@@ -44,7 +44,7 @@ struct BuildCtx {
     int32_t V, F, bound;
     MeshDyn *dyn; BuildHdr *hdr;
     int32_t *valence; uint8_t *leaf_cnt; BTask *tasks; uint32_t *hist; int32_t *cell_count, *cell_cursor;
-    float *vnormals; BvhNode *nodes; LeafRec *leaves; PairBox *pbox; TriRec *tris; TriAttr *attr; int32_t *slot2face, *face2slot;
+    float *vnormals; BvhNode *nodes; LeafRec *leaves; PairBox *pbox, *nbox; TriRec *tris; TriAttr *attr; int32_t *slot2face, *face2slot;
     int32_t *bin_start, *bin_slots;
     float *tbox, *cen; int32_t *order[2]; int32_t *adj; int32_t *chunkcnt; int32_t *subq; struct STask *sublist; uint32_t *bounds_part;
     int32_t nck; int64_t cells_cap, entries_cap;
@@ -739,6 +739,18 @@ __global__ __launch_bounds__(256) void k_tri_records(BuildCtx c)
         for (int cy = cy0; cy <= cy1; ++cy) atomicAdd(&c.cell_count[(size_t)cz * g.gy + cy], 1);
 }
 
+// the node boxes (mesh_rules.h: node_box_make): one thread per inner node - node id = split point - 1, and the slot behind a split
+// point starts a leaf - once the tree and the slot-ordered triangle records exist.  At most 32 triangles per thread, read in slot
+// order; nothing here is summed across threads, so the records equal the host builder's bit for bit.
+__global__ __launch_bounds__(256) void k_node_box(BuildCtx c)
+{
+    const int id = blockIdx.x * 256 + threadIdx.x;
+    if (id + 1 >= c.F || c.leaf_cnt[id + 1] == 0) return;
+    int nb[2];
+    if (!node_box_make(c.nodes, c.tris, c.F, id, nb, c.nbox[id])) { atomicOr(&c.dyn->status, kMeshInternal); return; }
+    c.nodes[id].nb_child[0] = nb[0]; c.nodes[id].nb_child[1] = nb[1];
+}
+
 // exclusive scan of the cell counts by one workgroup: tiles of 4,096 cells (four per thread, coalesced), a running carry
 __global__ __launch_bounds__(1024) void k_scan_cells(BuildCtx c)
 {
@@ -908,6 +920,7 @@ void mesh_bind_arena(icon_mesh *m, const MeshLayout &L)
     d.dyn = m->d_dyn;
     d.n_tris = (int32_t)m->F;
     d.pbox_off = pair_box_enabled() ? (int32_t)((L.pbox - L.leaves) / sizeof(PairBox)) : 0;
+    d.nbox_off = node_box_enabled() ? (int32_t)((L.nbox - L.leaves) / sizeof(PairBox)) : 0;
     d.bin_start = reinterpret_cast<const int32_t *>(b + L.bin_start);
     d.bin_slots = reinterpret_cast<const int32_t *>(b + L.bin_slots);
 }
@@ -925,7 +938,7 @@ int mesh_build_device(icon_mesh *m, const float *d_verts, const int64_t *d_faces
     c.tasks = reinterpret_cast<BTask *>(b + L.tasks); c.hist = reinterpret_cast<uint32_t *>(b + L.hist);
     c.cell_count = reinterpret_cast<int32_t *>(b + L.cell_count); c.cell_cursor = reinterpret_cast<int32_t *>(b + L.cell_cursor);
     c.vnormals = reinterpret_cast<float *>(b + L.vnormals); c.nodes = reinterpret_cast<BvhNode *>(b + L.nodes);
-    c.leaves = reinterpret_cast<LeafRec *>(b + L.leaves); c.pbox = reinterpret_cast<PairBox *>(b + L.pbox); c.tris = reinterpret_cast<TriRec *>(b + L.tris);
+    c.leaves = reinterpret_cast<LeafRec *>(b + L.leaves); c.pbox = reinterpret_cast<PairBox *>(b + L.pbox); c.nbox = reinterpret_cast<PairBox *>(b + L.nbox); c.tris = reinterpret_cast<TriRec *>(b + L.tris);
     c.attr = reinterpret_cast<TriAttr *>(b + L.attr); c.slot2face = reinterpret_cast<int32_t *>(b + L.slot2face);
     c.face2slot = reinterpret_cast<int32_t *>(b + L.face2slot); c.bin_start = reinterpret_cast<int32_t *>(b + L.bin_start);
     c.bin_slots = reinterpret_cast<int32_t *>(b + L.bin_slots); c.tbox = reinterpret_cast<float *>(b + L.tbox);
@@ -958,6 +971,8 @@ int mesh_build_device(icon_mesh *m, const float *d_verts, const int64_t *d_faces
     debug_sync("k_bvh_sub", st);
     hipLaunchKernelGGL(k_tri_records, dim3(nbF), dim3(256), 0, st, c);
     debug_sync("k_tri_records", st);
+    if (m->F > 1) hipLaunchKernelGGL(k_node_box, dim3((unsigned)((m->F + 254) / 256)), dim3(256), 0, st, c);
+    debug_sync("k_node_box", st);
     hipLaunchKernelGGL(k_scan_cells, dim3(1), dim3(1024), 0, st, c);
     hipLaunchKernelGGL(k_bin_fill, dim3((unsigned)((m->F * 8 + 255) / 256)), dim3(256), 0, st, c);
     hipLaunchKernelGGL(k_bin_sort, dim3((unsigned)((c.cells_cap + 255) / 256)), dim3(256), 0, st, c);

@@ -202,6 +202,146 @@ __host__ __device__ inline int pair_box_setup(const float v[6][3], float out[15]
     return kPairBoxNever;
 }
 
+// ---- oriented box of a slot range (the node boxes: PairBox records indexed by node id) ----------------------------------------------------------
+// pair_box_setup's rule for the n >= 1 triangles of a slot range instead of the two of a pair: a parent whose two children both hold
+// at most kNodeBoxMaxTris triangles (an "oriented parent"; a child may be a leaf or an inner node) tests its children by one such
+// box each instead of their AABBs - from distance D the AABB of a slanted patch of thickness t admits everything within
+// sqrt(2 D t), at every small subtree just as at a leaf.  tri: corner k of triangle i at tri[i * stride + 3 * k ..]
+// (TriRec: stride 12).  Sums and searches run in slot order, then corner / edge order (ab, ac, bc), and take the FIRST maximum.
+// Same frame (n = normalised sum of the area normals, u1 = the longest edge less its n part, u2 = n x u1), same fall-backs, same
+// scale and inflation as the pair box: the argument for the contract does not depend on the number of corners.
+constexpr int kNodeBoxMaxTris = 16;
+constexpr int kNodeBoxFlag = 1 << 30;      // set in a child reference >= 0: that inner node is an oriented parent (node ids are < 2^23)
+__host__ __device__ inline int range_box_setup(const float *tri, int stride, int n, float out[15])
+{
+    bool fin = true;
+    for (int i = 0; i < n; ++i) for (int k = 0; k < 9; ++k) fin = fin && pb_finite(tri[(size_t)i * stride + k]);
+    float ax[3][3] = {{1.f, 0.f, 0.f}, {0.f, 1.f, 0.f}, {0.f, 0.f, 1.f}};
+    int kind = kPairBoxAabb;
+    if (fin) {
+        // the frame
+        float eb[3] = {0.f, 0.f, 0.f}, nsum[3] = {0.f, 0.f, 0.f}, L2 = 0.f;
+        for (int i = 0; i < n; ++i) {
+            const float *a = tri + (size_t)i * stride, *b = a + 3, *c = a + 6;
+            float e[3][3];
+            for (int k = 0; k < 3; ++k) { e[0][k] = b[k] - a[k]; e[1][k] = c[k] - a[k]; e[2][k] = c[k] - b[k]; }
+            for (int j = 0; j < 3; ++j) {
+                const float l2 = dot3r(e[j], e[j]);
+                if ((i == 0 && j == 0) || l2 > L2) { L2 = l2; for (int k = 0; k < 3; ++k) eb[k] = e[j][k]; }
+            }
+            float nt[3];
+            pb_cross(e[0], e[1], nt);
+            for (int k = 0; k < 3; ++k) nsum[k] = i ? nsum[k] + nt[k] : nt[k];
+        }
+        const float nn = dot3r(nsum, nsum);
+        if (nn > 1e-10f * (L2 * L2)) {
+            const float ln = sqrtf(nn);
+            float a0[3], u[3], a1[3], a2[3];
+            for (int k = 0; k < 3; ++k) a0[k] = nsum[k] / ln;
+            const float en = dot3r(eb, a0);
+            for (int k = 0; k < 3; ++k) u[k] = fmaf(-en, a0[k], eb[k]);
+            const float uu = dot3r(u, u);
+            if (uu > 1e-10f * L2) {
+                const float lu = sqrtf(uu);
+                for (int k = 0; k < 3; ++k) a1[k] = u[k] / lu;
+                pb_cross(a0, a1, a2);
+                const float g[6] = {dot3r(a0, a0) - 1.0f, dot3r(a1, a1) - 1.0f, dot3r(a2, a2) - 1.0f, dot3r(a0, a1), dot3r(a0, a2), dot3r(a1, a2)};
+                bool ok = true;
+                for (int i = 0; i < 6; ++i) ok = ok && (fabsf(g[i]) <= kPairBoxGram);      // (a NaN fails)
+                if (ok) {
+                    for (int k = 0; k < 3; ++k) { ax[0][k] = a0[k]; ax[1][k] = a1[k]; ax[2][k] = a2[k]; }
+                    kind = kPairBoxOriented;
+                }
+            }
+        }
+    }
+    const int nc = 3 * n;
+    for (int attempt = 0; attempt < 2 && fin; ++attempt) {
+        // centre: the middle of the corners' AABB, moved to the middle of their extent along every axis
+        float c[3];
+        for (int k = 0; k < 3; ++k) {
+            float lo = tri[k], hi = tri[k];
+            for (int i = 1; i < nc; ++i) { const float v = tri[(size_t)(i / 3) * stride + 3 * (i % 3) + k]; lo = fminf(lo, v); hi = fmaxf(hi, v); }
+            c[k] = canon(0.5f * (lo + hi));
+        }
+        float mid[3];
+        for (int a = 0; a < 3; ++a) {
+            float lo = 0.f, hi = 0.f;
+            for (int i = 0; i < nc; ++i) {
+                const float *v = tri + (size_t)(i / 3) * stride + 3 * (i % 3);
+                const float d[3] = {v[0] - c[0], v[1] - c[1], v[2] - c[2]};
+                const float t = dot3r(ax[a], d);
+                lo = i ? fminf(lo, t) : t; hi = i ? fmaxf(hi, t) : t;
+            }
+            mid[a] = 0.5f * (lo + hi);
+        }
+        for (int k = 0; k < 3; ++k) c[k] = canon(fmaf(mid[2], ax[2][k], fmaf(mid[1], ax[1][k], fmaf(mid[0], ax[0][k], c[k]))));
+        // the stored axes and the extents of the corners along THEM, about the stored centre
+        float h[3];
+        for (int a = 0; a < 3; ++a) {
+            for (int k = 0; k < 3; ++k) out[3 + 3 * a + k] = canon(ax[a][k] * kPairBoxScale);
+            float m = 0.f;
+            for (int i = 0; i < nc; ++i) {
+                const float *v = tri + (size_t)(i / 3) * stride + 3 * (i % 3);
+                const float d[3] = {v[0] - c[0], v[1] - c[1], v[2] - c[2]};
+                m = fmaxf(m, fabsf(dot3r(out + 3 + 3 * a, d)));
+            }
+            h[a] = m;
+        }
+        const float pad = fmaf(kPairBoxEps, (h[0] + h[1]) + h[2], kPairBoxFloor);
+        bool ok = true;
+        for (int k = 0; k < 3; ++k) { out[k] = c[k]; out[12 + k] = h[k] + pad; ok = ok && pb_finite(c[k]) && pb_finite(out[12 + k]); }
+        if (ok) return kind;
+        if (kind == kPairBoxAabb) break;
+        kind = kPairBoxAabb;                                         // (the oriented frame overflowed: once more with the identity)
+        for (int a = 0; a < 3; ++a) for (int k = 0; k < 3; ++k) ax[a][k] = (a == k) ? 1.f : 0.f;
+    }
+    for (int k = 0; k < 3; ++k) { out[k] = 0.f; out[12 + k] = __builtin_inff(); }
+    for (int a = 0; a < 3; ++a) for (int k = 0; k < 3; ++k) out[3 + 3 * a + k] = (a == k) ? kPairBoxScale : 0.f;
+    return kPairBoxNever;
+}
+
+// The node-box record of inner node `id` (its split point is slot id + 1), or false: not an oriented parent.  Shared by both builders
+// so that they cannot disagree: nodes / tris = the finished tree and the slot-ordered triangle records, F = the slot count.
+//   rec: fields 0..14 = the two children's boxes, field-interleaved like a PairBox ([field][child]); field 15 = the two child
+//        references as the walk follows them (bit patterns): a leaf code, or an inner node's id | kNodeBoxFlag - an inner child of
+//        an oriented parent holds at most kNodeBoxMaxTris triangles, so it is an oriented parent itself.
+//   The children's slot ranges are [b0, id + 1) and [id + 1, e1): b0 / e1 are found down the left / right spine of the children.
+__host__ __device__ inline bool node_child_range(const BvhNode *nodes, int F, int child, int side, int bound, int &edge)
+{
+    int c = child;
+    for (int it = 0; it <= bound && c >= 0; ++it) { if (c >= F) return false; c = side ? nodes[c].child1 : nodes[c].child0; }
+    if (c >= 0) return false;
+    const int code = ~c, leaf = code >> 2, cnt = (code & 3) + 1;
+    edge = side ? leaf + cnt : leaf;
+    return leaf >= 0 && leaf + cnt <= F;
+}
+__host__ __device__ inline int node_ref_flagged(int ref, int begin, int end)
+{
+    // ref >= 0 owns [begin, end) and splits it at ref + 1
+    if (ref < 0) return ref;
+    return (ref + 1 - begin <= kNodeBoxMaxTris && end - (ref + 1) <= kNodeBoxMaxTris) ? (ref | kNodeBoxFlag) : ref;
+}
+
+// what both builders do for inner node `id` once the tree and the slot-ordered triangle records exist: nb = its two child references
+// as the node-box walk follows them (BvhNode::nb_child), and, for an oriented parent, its record.  Returns 0: the tree is malformed
+// (a bug), 1: an AABB parent (rec untouched), 2: an oriented parent.  At most 2 * kNodeBoxMaxTris triangles are read, in slot order.
+__host__ __device__ inline int node_box_make(const BvhNode *nodes, const TriRec *tris, int F, int id, int nb[2], PairBox &rec)
+{
+    const int c0 = nodes[id].child0, c1 = nodes[id].child1, mid = id + 1;
+    int b0 = 0, e1 = 0;
+    if (!node_child_range(nodes, F, c0, 0, kStackDepth, b0) || !node_child_range(nodes, F, c1, 1, kStackDepth, e1) || !(b0 < mid && mid < e1)) return 0;
+    nb[0] = node_ref_flagged(c0, b0, mid); nb[1] = node_ref_flagged(c1, mid, e1);
+    if (mid - b0 > kNodeBoxMaxTris || e1 - mid > kNodeBoxMaxTris) return 1;
+    for (int s = 0; s < 2; ++s) {
+        float r[15];
+        range_box_setup(reinterpret_cast<const float *>(tris + (s ? mid : b0)), (int)(sizeof(TriRec) / 4), s ? e1 - mid : mid - b0, r);
+        for (int fld = 0; fld < 15; ++fld) rec.f[fld][s] = r[fld];
+        __builtin_memcpy(&rec.f[15][s], &nb[s], 4);
+    }
+    return 2;
+}
+
 // Both pair boxes of a leaf at once (packed f32: the operand shape of v_pk_add / v_pk_mul / v_pk_fma): q = the 16 two-float
 // fields of a PairBox, (px, py, pz) the point.  Component i = lower bound of the squared distance to the triangles of pair i:
 // the squared distance to the box in its own frame.  No square root; NaN projections (a NaN point) give 0 = "not culled".
@@ -246,7 +386,7 @@ struct BuildHdr {                      // zeroed before every build
 
 struct MeshLayout {
     size_t dyn, hdr, valence, leaf_cnt, tasks, hist, cell_count, cell_cursor, zero_end;   // [dyn, zero_end) is zeroed per build
-    size_t vnormals, nodes, leaves, pbox, tris, attr, slot2face, face2slot, bin_start, bin_slots;
+    size_t vnormals, nodes, leaves, pbox, nbox, tris, attr, slot2face, face2slot, bin_start, bin_slots;
     size_t tbox, cen, order0, order1, adj, chunkcnt, subq, sublist, bounds_part, total;
     int64_t nck;                       // chunk records per top level
 };
@@ -271,6 +411,7 @@ inline MeshLayout mesh_layout(int64_t V, int64_t F)
     L.nodes = take(sizeof(BvhNode) * F);
     L.leaves = take(sizeof(LeafRec) * F);
     L.pbox = take(sizeof(PairBox) * F);                        // behind the leaves it is indexed like (icon_debug_mesh_layout: part of entry 3's range)
+    L.nbox = take(sizeof(PairBox) * F);                        // the node boxes, indexed by node id (part of entry 3's range as well)
     L.tris = take(sizeof(TriRec) * F);
     L.attr = take(sizeof(TriAttr) * F);
     L.slot2face = take(sizeof(int32_t) * F);

@@ -194,7 +194,7 @@ __global__ __launch_bounds__(kBlock) void k_traversal_stats(MeshDev m, LatticeMa
 
 // diagnostics: what the pair boxes do to the lattice walk - per packet, the nodes visited, the leaf pairs offered to the
 // distance test and the pairs tested (icon_debug_pair_stats; tools/pair_box_model.py predicts the last two on the CPU)
-__global__ __launch_bounds__(kBlock) void k_pair_stats(MeshDev m, LatticeMap L, unsigned long long *out /* [4] */)
+__global__ __launch_bounds__(kBlock) void k_pair_stats(MeshDev m, LatticeMap L, unsigned long long *out /* [6] */)
 {
     __shared__ int lds[(kBlock / 64) * kStackDepth];
     L = lattice_trim(L, m);
@@ -203,11 +203,12 @@ __global__ __launch_bounds__(kBlock) void k_pair_stats(MeshDev m, LatticeMap L, 
     const bool live = lattice_point(L, ix, iy, iz);
     lattice_clamp(L, ix, iy, iz, cx, cy, cz);
     const f3 p = lattice_world(L.res, cx, cy, cz + L.z0);
-    int nn = 0, nt = 0, no = 0, ns = 0;
-    nearest_packet<true>(m, p, live, lds + (threadIdx.x >> 6) * kStackDepth, &nn, &nt, INFINITY, nullptr, packet_center_lane(L), false, 0, &no, &ns);
+    int nn = 0, nt = 0, no = 0, ns = 0, nl = 0, nb = 0;
+    nearest_packet<true>(m, p, live, lds + (threadIdx.x >> 6) * kStackDepth, &nn, &nt, INFINITY, nullptr, packet_center_lane(L), false, 0, &no, &ns, &nl, &nb);
     if ((threadIdx.x & 63) == 0) {
         atomicAdd(&out[0], 1ull); atomicAdd(&out[1], (unsigned long long)nn);
         atomicAdd(&out[2], (unsigned long long)no); atomicAdd(&out[3], (unsigned long long)ns);
+        atomicAdd(&out[4], (unsigned long long)nl); atomicAdd(&out[5], (unsigned long long)nb);
     }
 }
 
@@ -842,6 +843,12 @@ namespace icon {
 int g_share_ring = 0, g_share_lose = 0, g_share_spin_log2 = 0;     // icon_debug_set_option; all zero in production
 int g_lattice_fast = -1;                                          // -1: read ICON_AMD_LATTICE_FAST once (default on)
 int g_pair_box = -1;                                               // -1: read ICON_AMD_PAIR_BOX once (default on); 0 / 1: icon_debug_set_option
+int g_node_box = -1;                                               // likewise ICON_AMD_NODE_BOX / "node_box"
+int node_box_enabled()
+{
+    if (g_node_box < 0) g_node_box = getenv("ICON_AMD_NODE_BOX") ? (atoi(getenv("ICON_AMD_NODE_BOX")) != 0) : 1;
+    return g_node_box;
+}
 int pair_box_enabled()
 {
     if (g_pair_box < 0) g_pair_box = getenv("ICON_AMD_PAIR_BOX") ? (atoi(getenv("ICON_AMD_PAIR_BOX")) != 0) : 1;
@@ -1480,21 +1487,39 @@ extern "C" int icon_debug_traversal_stats(const icon_mesh_t *mesh, int res, int 
 
 // out = [packets, nodes visited, leaf pairs offered to the distance test, leaf pairs tested], summed over the packets of the
 // planes [z0, z1) of the res^3 lattice, for the walk this mesh runs ("pair_box" as it was when the mesh was created)
-extern "C" int icon_debug_pair_stats(const icon_mesh_t *mesh, int res, int z0, int z1, uint64_t out[4])
+static int walk_stats(const icon_mesh_t *mesh, int res, int z0, int z1, unsigned long long h[6])
 {
-    ICON_ARG(mesh && out, "icon_debug_pair_stats: null argument");
     LatticeMap L;
     int rc = lattice_map(res, z0, z1, mesh, 0.05f, true, &L);
     if (rc) return rc;
     unsigned long long *d = nullptr;
-    ICON_HIP(hipMalloc((void **)&d, 4 * sizeof(unsigned long long)));
-    ICON_HIP(hipMemset(d, 0, 4 * sizeof(unsigned long long)));
+    ICON_HIP(hipMalloc((void **)&d, 6 * sizeof(unsigned long long)));
+    ICON_HIP(hipMemset(d, 0, 6 * sizeof(unsigned long long)));
     hipLaunchKernelGGL(k_pair_stats, dim3((unsigned)(L.tx * L.ty * L.tz)), dim3(kBlock), 0, 0, mesh->dev, L, d);
-    unsigned long long h[4];
-    hipError_t e = hipMemcpy(h, d, sizeof(h), hipMemcpyDeviceToHost);
+    hipError_t e = hipMemcpy(h, d, 6 * sizeof(unsigned long long), hipMemcpyDeviceToHost);
     (void)hipFree(d);
-    if (e != hipSuccess) return fail(ICON_ERR_HIP, std::string("pair stats: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return fail(ICON_ERR_HIP, std::string("walk stats: ") + hipGetErrorString(e));
+    return ICON_OK;
+}
+extern "C" int icon_debug_pair_stats(const icon_mesh_t *mesh, int res, int z0, int z1, uint64_t out[4])
+{
+    ICON_ARG(mesh && out, "icon_debug_pair_stats: null argument");
+    unsigned long long h[6];
+    int rc = walk_stats(mesh, res, z0, z1, h);
+    if (rc) return rc;
     for (int k = 0; k < 4; ++k) out[k] = h[k];
+    return ICON_OK;
+}
+// a superset of icon_debug_pair_stats (kept for its callers' out[4]), same kernel:
+// out = [packets, inner nodes visited (AABB and oriented parents together), leaf pairs offered, leaf pairs tested, leaves visited,
+// oriented parents visited] for the walk this mesh runs ("pair_box" / "node_box" as they were when the mesh was created)
+extern "C" int icon_debug_walk_stats(const icon_mesh_t *mesh, int res, int z0, int z1, uint64_t out[6])
+{
+    ICON_ARG(mesh && out, "icon_debug_walk_stats: null argument");
+    unsigned long long h[6];
+    int rc = walk_stats(mesh, res, z0, z1, h);
+    if (rc) return rc;
+    for (int k = 0; k < 6; ++k) out[k] = h[k];
     return ICON_OK;
 }
 
@@ -1521,7 +1546,8 @@ extern "C" int icon_work_status(icon_work_t *work)
 }
 
 // test / A-B switches by name (process-wide): "pair_box" 0 / 1 - the packet walk culls leaf pairs by their oriented boxes (meshes
-// and mesh batches created AFTERWARDS; 0: they run the walk without the cull); "lattice_fast" 0 / 1; "share_waves" wavefronts per shared walk (-1 = by launch size;
+// and mesh batches created AFTERWARDS; 0: they run the walk without the cull); "node_box" 0 / 1 - the packet walk tests the children of the bottom
+// inner nodes by oriented boxes (likewise: meshes created afterwards; 0: AABBs only); "lattice_fast" 0 / 1; "share_waves" wavefronts per shared walk (-1 = by launch size;
 // 4: the adaptive schedule's searches only); "share_ring" forced ring size of the shared walks (0 = 64),
 // "share_lose_push" the ticket of the push that is announced but never stored (0 = none), "share_spin_log2" wait bound 2^n polls
 // (0 = 2^18).  Production leaves all of them alone.
@@ -1532,6 +1558,7 @@ extern "C" int icon_debug_set_option(const char *key, int value)
     if (k == "lattice_fast") g_lattice_fast = value ? 1 : 0;
     else if (k == "share_waves") { ICON_ARG(value == -1 || value == 1 || value == 4 || value == 8 || value == 16, "share_waves: -1 (by launch size), 1, 4, 8 or 16"); g_share_waves = value; }
     else if (k == "pair_box") g_pair_box = value ? 1 : 0;
+    else if (k == "node_box") g_node_box = value ? 1 : 0;
     else if (k == "share_ring") { ICON_ARG(value == 0 || (value >= 2 && value <= 64 && (value & (value - 1)) == 0), "share_ring: 0 or a power of two in 2..64"); g_share_ring = value; }
     else if (k == "share_lose_push") { ICON_ARG(value >= 0, "share_lose_push: a ticket >= 1, or 0"); g_share_lose = value; }
     else if (k == "share_spin_log2") { ICON_ARG(value >= 0 && value < 30, "share_spin_log2: 0..29"); g_share_spin_log2 = value; }

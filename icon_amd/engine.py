@@ -147,6 +147,13 @@ class MeshHandle(_Handle):
         return dict(packets=arr[0], nodes=arr[1], pairs_offered=arr[2], pairs_tested=arr[3], nodes_per_packet=arr[1] / n,
                     pairs_offered_per_packet=arr[2] / n, pairs_tested_per_packet=arr[3] / n)
 
+    def walk_stats(self, res: int, z0: int = 0, z1: Optional[int] = None) -> dict:
+        """a superset of pair_stats (the same kernel and walk, its raw counts): plus the leaves visited and the oriented parents among the nodes (0 with the "node_box" option off)"""
+        arr = (C.c_uint64 * 6)()
+        check(_lib.lib().icon_debug_walk_stats(self.h, C.c_int(res), C.c_int(z0), C.c_int(res if z1 is None else z1), arr),
+              "icon_debug_walk_stats")
+        return dict(packets=arr[0], nodes=arr[1], pairs_offered=arr[2], pairs_tested=arr[3], leaves=arr[4], oriented_nodes=arr[5])
+
     def sdf_query(self, points: torch.Tensor, search: str = "bvh"):
         """cal_sdf_batch (lib/dataset/mesh_util.py:357-396) for points [N,3] ->
         dict(sdf [N], norm [N,3], cmap [N,3], vis [N], face [N] i64, inside [N] bool)"""

@@ -418,9 +418,16 @@ int icon_work_set_tie_rule(icon_work_t *work, int rule, int ulps);
 int icon_debug_traversal_stats(const icon_mesh_t *mesh, int res, int z0, int z1, uint64_t out[4]);
 /* the lattice walk's leaf work: out = [packets, nodes visited, leaf pairs offered to the distance test, leaf pairs tested] */
 int icon_debug_pair_stats(const icon_mesh_t *mesh, int res, int z0, int z1, uint64_t out[4]);
+/* a superset of icon_debug_pair_stats (same kernel, same walk; out[0..3] are its four values): out = [packets, inner nodes visited (AABB and oriented parents together), leaf pairs offered,
+ * leaf pairs tested, leaves visited, oriented parents visited (0 for a mesh created with the "node_box" option off)] */
+int icon_debug_walk_stats(const icon_mesh_t *mesh, int res, int z0, int z1, uint64_t out[6]);
 /* host only: the oriented-box rule of the leaf pairs (record, kind 0 oriented / 1 AABB / 2 never culled, lower bounds of d^2) */
 int icon_debug_pair_box(const float *corners, int64_t n_pairs, const float *pts, int64_t n_pts, int shared_pts,
                         float *rec, int32_t *kind, float *bound);
+/* host only: the oriented-box rule of a slot range (the node boxes): rec[15], kind of the n_tris triangles tris[i][3][3]; and the
+ * walk's bound on PairBox-shaped records recs[i][16][2]: bound[i][c][j] = component c at point j (pts[j], or pts[i][j]) */
+int icon_debug_range_box(const float *tris, int64_t n_tris, float *rec, int32_t *kind);
+int icon_debug_box_bound(const float *recs, int64_t n_recs, const float *pts, int64_t n_pts, int shared_pts, float *bound);
 
 /* Seg3dLossless._forward_faster's None rule (lib/common/seg3d_lossless.py:173-177: the call returns None when nothing exceeds
  * 0.5 on the COARSEST lattice) for a dense device volume d_occ [res,res,res]: the coarsest lattice is the sub-lattice of strides
