@@ -150,6 +150,7 @@ struct MeshDev {
     int32_t n_tris;             // triangle slots = F
     int32_t pbox_off;           // the PairBox section: (const PairBox *)leaves + pbox_off; 0 = the walk tests every pair ("pair_box" off)
     int32_t nbox_off;           // the node-box section (PairBox records by node id), same addressing; 0 = the walk uses AABBs only ("node_box" off)
+    int32_t box_clamp;          // 1: the lattice launches evaluate the oriented boxes by pair_box_bound_half ("box_clamp" on); read by the host only
     // ray bins over (y, z)
     const int32_t *bin_start;   // [gy*gz + 1]
     const int32_t *bin_slots;   // triangle slots
@@ -411,6 +412,7 @@ int work_check_err(icon_work *w);
 extern int g_qc_lanes;                // query_color.hip: lanes per face of the colour call's rasteriser ("qc_lanes"; 0 = default)
 extern int g_rn_lanes;                // render_normal.hip: lanes per face of the renderer's rasteriser ("rn_lanes"; 0 = default)
 int node_box_enabled();               // ICON_AMD_NODE_BOX / icon_debug_set_option("node_box"): likewise for the oriented boxes of the bottom inner nodes
+int box_clamp_enabled();              // ICON_AMD_BOX_CLAMP / icon_debug_set_option("box_clamp"): meshes created while it is 0 keep pair_box_bound everywhere
 int pair_box_enabled();               // ICON_AMD_PAIR_BOX / icon_debug_set_option("pair_box"): meshes created while it is 0 walk without the cull
 int share_waves_override();           // ICON_AMD_SHARE / icon_debug_set_option("share_waves"): -1 = by launch size
 }  // namespace icon

@@ -254,7 +254,15 @@ __device__ __forceinline__ float prune_threshold(float best)
 // carries the key of its original and is therefore never its own runner-up).  Every face whose d^2 lies within
 // the pruning bound of the final winner is visited (the bound only ever shrinks towards its final value), so the
 // runner-up is exact whenever it is within ~8e-5 relative of the winner - far beyond the 255 ulps reported.
-template <bool STATS = false, bool TIES = false>
+// CLAMP ("box_clamp"): the oriented boxes - parents and leaf pairs - are evaluated in half units with the excess limited to
+// [0, 1] by the subtraction's clamp bit (mesh_rules.h: pair_box_bound_half) and voted against thr / 4: the same decisions, or
+// fewer culls where an excess passes 2.0 - bit-identical results either way.
+// The loop is written for its listing (profiles/walk_diet_isa.txt): child references are integers from the scalar load in both
+// kinds of inner visit, the key and the threshold are updated in place, both pair ballots become bits on the scalar unit, and
+// there is ONE pop, at the loop's tail.
+typedef int i2 __attribute__((ext_vector_type(2)));
+typedef __attribute__((address_space(4))) const i2 ci2;
+template <bool STATS = false, bool TIES = false, bool CLAMP = false>
 __device__ __forceinline__ Nearest nearest_packet(const MeshDev &m, f3 p, bool live, int *wstack /* LDS, kStackDepth ints of this wave */,
                                                   int *n_nodes = nullptr, int *n_tris = nullptr, float thr0 = INFINITY,
                                                   unsigned long long *runner_up = nullptr, int center_lane = 21,
@@ -267,6 +275,8 @@ __device__ __forceinline__ Nearest nearest_packet(const MeshDev &m, f3 p, bool l
     unsigned long long key = 0x7f8000007fffffffull;   // (+inf, INT_MAX)
     unsigned long long key2 = 0x7f8000007fffffffull;
     float thr = live ? thr0 : -INFINITY;
+    float thq = thr * 0.25f;                          // CLAMP: the bound the half-unit boxes vote against (an exact multiply)
+    const f3 ph = mk3(p.x * 0.5f, p.y * 0.5f, p.z * 0.5f);
     int sp = 0;
     int cur = have_root ? root : mesh_root(m);        // (wave-uniform choice; the caller that holds the root in a register passes it)
     // the node boxes (PairBox records by node id), or null: "node_box" off - AABBs all the way down.  A reference >= 0 with
@@ -277,6 +287,7 @@ __device__ __forceinline__ Nearest nearest_packet(const MeshDev &m, f3 p, bool l
     const PairBox *nbox = m.nbox_off ? reinterpret_cast<const PairBox *>(m.leaves) + m.nbox_off : nullptr;
     if (nbox) cur = node_ref_flagged(cur, 0, m.n_tris);
     while (true) {
+        bool pop;                                                // wave-uniform: this visit entered no child
         if (cur < 0) {
             const int code = ~cur;
             const int leaf = code >> 2, cnt = (code & 3) + 1;
@@ -287,75 +298,84 @@ __device__ __forceinline__ Nearest nearest_packet(const MeshDev &m, f3 p, bool l
             // DESIGN.md 4.1): both pairs' oriented boxes in one packed evaluation, then the distance test only for the pairs
             // SOME lane still needs.  box bound <= real d^2 of the pair's triangles, so a pair skipped here could neither beat
             // nor tie any lane's key - the same argument as for a child's box.  Parked lanes (thr = -inf) never vote.
-            int need = (1 << npairs) - 1;                        // bit pr: pair pr is tested; scalar, like the loop over its bits
+            int need = (2 << npairs) - 2;                        // bit pr + 1: pair pr is tested; scalar, like the loop over its bits
             if (pbox) {
-                const f2 bb = pair_box_bound(reinterpret_cast<cf2 *>(as_const(pbox + leaf)), p.x, p.y, p.z);
-                const int any0 = __builtin_amdgcn_ballot_w64(bb.x <= thr) != 0 ? 1 : 0, any1 = __builtin_amdgcn_ballot_w64(bb.y <= thr) != 0 ? 2 : 0;
-                need &= any0 | any1;                             // (ballots are wave-uniform: all scalar)
+                cf2 *q = reinterpret_cast<cf2 *>(as_const(pbox + leaf));
+                const f2 bb = CLAMP ? pair_box_bound_half(q, ph.x, ph.y, ph.z) : pair_box_bound(q, p.x, p.y, p.z);
+                const float lim = CLAMP ? thq : thr;
+                // (ballots are wave-uniform; each becomes a bit by a scalar select of constants - which is why the bits start at 1:
+                //  a bare 0 / 1 is materialised per lane and read back)
+                const int any0 = __builtin_amdgcn_ballot_w64(bb.x <= lim) != 0 ? 2 : 0, any1 = __builtin_amdgcn_ballot_w64(bb.y <= lim) != 0 ? 4 : 0;
+                need &= any0 | any1;
             }
             if (STATS && n_offered) { *n_offered += npairs; *n_tested += __builtin_popcount((unsigned)need); }
-            if (need == 0) {                                     // nothing tested: key and bound are what they were
-                if (sp == 0) break;
-                cur = __builtin_amdgcn_readfirstlane(wstack[--sp]);
-                continue;
+            if (need) {                                          // (nothing tested: key and bound are what they were)
+                do {
+                    const int pr = __builtin_ctz((unsigned)need) - 1;
+                    cf2 *q = reinterpret_cast<cf2 *>(as_const(&m.leaves[leaf].pair[pr]));
+                    const f2 d2 = tri_dist2_pair(p, q);
+                    const f2 fc = q[22];
+                    // S3 as ONE unsigned 64-bit minimum: key = (bits of d^2) << 32 | face.  d^2 >= +0, so
+                    // its bit pattern orders like the value; equal d^2 -> lower face id wins; NaN (bits
+                    // above +inf) never wins; a padding copy has the same key as its original.
+                    const unsigned long long k0 = ((unsigned long long)(unsigned)__float_as_int(d2.x) << 32) | (unsigned)__float_as_int(fc.x);
+                    const unsigned long long k1 = ((unsigned long long)(unsigned)__float_as_int(d2.y) << 32) | (unsigned)__float_as_int(fc.y);
+                    // (the winner's slot is looked up from its face id at the end: nothing else to carry per test; a parked
+                    //  lane computes on a clamped copy of a real point and may update its key freely - it never votes
+                    //  (thr = -inf) and its result is not stored - so the update needs no `live` mask)
+                    if (TIES) {
+                        if (k0 < key) { key2 = key; key = k0; } else if (k0 != key && k0 < key2) key2 = k0;
+                        if (k1 < key) { key2 = key; key = k1; } else if (k1 != key && k1 < key2) key2 = k1;
+                    } else {
+                        key = (k0 < key) ? k0 : key;
+                        key = (k1 < key) ? k1 : key;
+                    }
+                    need &= need - 1;
+                } while (need);
+                thr = live ? prune_threshold(__int_as_float((int)(key >> 32))) : thr;   // one fma + select: cheaper than finding out whether the key moved
+                if (CLAMP) thq = thr * 0.25f;
             }
-            for (; need; need &= need - 1) {
-                const int pr = __builtin_ctz((unsigned)need);
-                cf2 *q = reinterpret_cast<cf2 *>(as_const(&m.leaves[leaf].pair[pr]));
-                const f2 d2 = tri_dist2_pair(p, q);
-                const f2 fc = q[22];
-                // S3 as ONE unsigned 64-bit minimum: key = (bits of d^2) << 32 | face.  d^2 >= +0, so
-                // its bit pattern orders like the value; equal d^2 -> lower face id wins; NaN (bits
-                // above +inf) never wins; a padding copy has the same key as its original.
-                const unsigned long long k0 = ((unsigned long long)(unsigned)__float_as_int(d2.x) << 32) | (unsigned)__float_as_int(fc.x);
-                const unsigned long long k1 = ((unsigned long long)(unsigned)__float_as_int(d2.y) << 32) | (unsigned)__float_as_int(fc.y);
-                // (the winner's slot is looked up from its face id at the end: nothing else to carry per test; a parked
-                //  lane computes on a clamped copy of a real point and may update its key freely - it never votes
-                //  (thr = -inf) and its result is not stored - so the update needs no `live` mask)
-                if (TIES) {
-                    if (k0 < key) { key2 = key; key = k0; } else if (k0 != key && k0 < key2) key2 = k0;
-                    if (k1 < key) { key2 = key; key = k1; } else if (k1 != key && k1 < key2) key2 = k1;
-                } else {
-                    key = (k0 < key) ? k0 : key;
-                    key = (k1 < key) ? k1 : key;
-                }
-            }
-            nr.d2 = __int_as_float((int)(key >> 32));
-            thr = live ? prune_threshold(nr.d2) : thr;           // one fma + select: cheaper than finding out whether the key moved
-            if (sp == 0) break;
-            cur = __builtin_amdgcn_readfirstlane(wstack[--sp]);
+            pop = true;
         } else {
             if (STATS) ++*n_nodes;
-            // both children's lower bounds in one packed evaluation: box distances of an AABB parent, pair_box_bound of an oriented
-            // parent's record - either way <= the real d^2 of every triangle below the child, which is all the vote relies on
-            f2 dd, ids;
+            // both children's lower bounds in one packed evaluation: box distances of an AABB parent, the oriented-box bound of an
+            // oriented parent's record - either way <= the real d^2 of every triangle below the child, which is all the vote relies on
+            i2 ids;                                              // the child references: integers from the record's own scalar load, both ways
+            unsigned long long b0, b1;                           // the votes
+            f2 dd;                                               // (in half units at an oriented parent under CLAMP: one visit, one unit)
             if (cur & kNodeBoxFlag) {
                 if (STATS && n_obox) ++*n_obox;
-                cf2 *q = reinterpret_cast<cf2 *>(as_const(nbox + (cur & ~kNodeBoxFlag)));
-                dd = pair_box_bound(q, p.x, p.y, p.z);
-                ids = q[15];
+                const PairBox *rec = nbox + (cur & ~kNodeBoxFlag);
+                cf2 *q = reinterpret_cast<cf2 *>(as_const(rec));
+                dd = CLAMP ? pair_box_bound_half(q, ph.x, ph.y, ph.z) : pair_box_bound(q, p.x, p.y, p.z);
+                const float lim = CLAMP ? thq : thr;
+                ids = reinterpret_cast<ci2 *>(as_const(rec))[15];
+                b0 = __builtin_amdgcn_ballot_w64(dd.x <= lim); b1 = __builtin_amdgcn_ballot_w64(dd.y <= lim);
             } else {
                 cf2 *q = reinterpret_cast<cf2 *>(as_const(m.nodes + cur));   // lo.x lo.y lo.z hi.x hi.y hi.z (children 0,1), ids, walk ids
                 dd = box_dist2_pair(q, p);
-                const f2 plain = q[6], walk = q[7];                          // (one 64-byte scalar load either way)
+                ci2 *qi = reinterpret_cast<ci2 *>(as_const(m.nodes + cur));
+                const i2 plain = qi[6], walk = qi[7];                        // (one 64-byte scalar load either way)
                 ids = nbox ? walk : plain;
+                b0 = __builtin_amdgcn_ballot_w64(dd.x <= thr); b1 = __builtin_amdgcn_ballot_w64(dd.y <= thr);
             }
-            const float d0 = dd.x, d1 = dd.y;
-            const int c0 = __float_as_int(ids.x), c1 = __float_as_int(ids.y);
-            const bool v0 = __any(d0 <= thr), v1 = __any(d1 <= thr);
+            const int c0 = ids.x, c1 = ids.y;
+            const bool v0 = b0 != 0, v1 = b1 != 0;
+            pop = false;
             if (v0 && v1) {
                 // order by the block's centre lane; non-negative floats order like their bit patterns
-                const int e0 = __builtin_amdgcn_readlane(__float_as_int(d0), center_lane);
-                const int e1 = __builtin_amdgcn_readlane(__float_as_int(d1), center_lane);
+                const int e0 = __builtin_amdgcn_readlane(__float_as_int(dd.x), center_lane);
+                const int e1 = __builtin_amdgcn_readlane(__float_as_int(dd.y), center_lane);
                 const bool first0 = e0 <= e1;
                 wstack[sp++] = first0 ? c1 : c0;
                 cur = first0 ? c0 : c1;
             } else if (v0) cur = c0;
             else if (v1) cur = c1;
-            else {
-                if (sp == 0) break;
-                cur = __builtin_amdgcn_readfirstlane(wstack[--sp]);
-            }
+            else pop = true;
+        }
+        if (pop) {
+            if (sp == 0) break;
+            cur = __builtin_amdgcn_readfirstlane(wstack[--sp]);
         }
     }
     nr.d2 = __int_as_float((int)(key >> 32)); nr.face = (int)(key & 0xffffffffu);

@@ -638,6 +638,24 @@ extern "C" int icon_debug_box_bound(const float *recs, int64_t n_recs, const flo
     return ICON_OK;
 }
 
+// pair_box_bound_half - the "box_clamp" evaluation of the same records, as the lattice walk calls it (the point halved per lane
+// first) - in icon_debug_box_bound's layout: bound[i][c][j] is a QUARTER of the squared distance, or less.
+extern "C" int icon_debug_box_bound_half(const float *recs, int64_t n_recs, const float *pts, int64_t n_pts, int shared_pts, float *bound)
+{
+    ICON_ARG(recs && pts && bound && n_recs >= 1 && n_recs <= (1 << 24) && n_pts >= 1, "icon_debug_box_bound_half: bad argument");
+    parallel_for((int)n_recs, [&](int i) {
+        PairBox pb;
+        memcpy((void *)&pb, recs + 32 * (size_t)i, sizeof(pb));
+        const pbf2 *q = reinterpret_cast<const pbf2 *>(&pb);
+        const float *pp = shared_pts ? pts : pts + 3 * n_pts * (size_t)i;
+        for (int64_t j = 0; j < n_pts; ++j) {
+            const pbf2 b = pair_box_bound_half(q, pp[3 * j] * 0.5f, pp[3 * j + 1] * 0.5f, pp[3 * j + 2] * 0.5f);
+            bound[(2 * (size_t)i) * n_pts + j] = b.x; bound[(2 * (size_t)i + 1) * n_pts + j] = b.y;
+        }
+    });
+    return ICON_OK;
+}
+
 // byte offsets of the arena sections (tests compare the arenas of the host and the device build):
 // (the pair boxes follow the leaves they are indexed like, the node boxes - indexed by node id - follow them: bytes
 //  [leaves + 384 F rounded up to 256, tris) of entry 3's range hold 128 F bytes of each, each rounded up to 256)

@@ -362,6 +362,33 @@ __host__ __device__ inline pbf2 pair_box_bound(Ptr q, float px, float py, float 
     return __builtin_elementwise_fma(e2, e2, __builtin_elementwise_fma(e1, e1, e0 * e0));
 }
 
+// The same records evaluated in HALF units ("box_clamp"): (hx, hy, hz) = the point times 0.5 (exact; the caller holds it per lane),
+// every length comes out halved, the result is pair_box_bound / 4.  Halving commutes with every rounding above the subnormal range,
+// so while no axis excess passes 2.0 the value is pair_box_bound's divided by 4, bit for bit; an excess beyond 2.0 stops at 1.0 in
+// half units and the value is SMALLER than a quarter of pair_box_bound's - the vote `bound' <= thr / 4` culls what `bound <= thr`
+// culls, or less (DESIGN.md "BVH conservativeness").  What it is for: both limits of min(max(., 0), 1) are the clamp bit of the
+// subtraction that produces the excess (one v_fma_f32 |t'|, h, -0.5 clamp per component instead of v_sub_f32 + v_max_f32).
+// NaN projections give 0 like pair_box_bound's: fmaxf(NaN, 0) = 0, and the clamp bit turns NaN into 0 as well.
+__host__ __device__ inline float pair_box_excess_half(float t, float h)
+{
+    return fminf(fmaxf(fmaf(h, -0.5f, fabsf(t)), 0.0f), 1.0f);
+}
+template <class Ptr>
+__host__ __device__ inline pbf2 pair_box_bound_half(Ptr q, float hx, float hy, float hz)
+{
+    pbf2 bx, by, bz, mh; bx.x = hx; bx.y = hx; by.x = hy; by.y = hy; bz.x = hz; bz.y = hz; mh.x = -0.5f; mh.y = -0.5f;
+    const pbf2 dx = __builtin_elementwise_fma(q[0], mh, bx), dy = __builtin_elementwise_fma(q[1], mh, by), dz = __builtin_elementwise_fma(q[2], mh, bz);
+    const pbf2 t0 = __builtin_elementwise_fma(q[5], dz, __builtin_elementwise_fma(q[4], dy, q[3] * dx));
+    const pbf2 t1 = __builtin_elementwise_fma(q[8], dz, __builtin_elementwise_fma(q[7], dy, q[6] * dx));
+    const pbf2 t2 = __builtin_elementwise_fma(q[11], dz, __builtin_elementwise_fma(q[10], dy, q[9] * dx));
+    const pbf2 h0 = q[12], h1 = q[13], h2 = q[14];
+    pbf2 e0, e1, e2;
+    e0.x = pair_box_excess_half(t0.x, h0.x); e0.y = pair_box_excess_half(t0.y, h0.y);
+    e1.x = pair_box_excess_half(t1.x, h1.x); e1.y = pair_box_excess_half(t1.y, h1.y);
+    e2.x = pair_box_excess_half(t2.x, h2.x); e2.y = pair_box_excess_half(t2.y, h2.y);
+    return __builtin_elementwise_fma(e2, e2, __builtin_elementwise_fma(e1, e1, e0 * e0));
+}
+
 // ---- arena layout (one device allocation per mesh) ------------------------------------------------------------
 constexpr int kTopLevels = 7;          // BVH levels 0..6 are split by multi-workgroup kernels (k_bvh_bin / k_bvh_part)
 constexpr int kSubMax = 256;           // subtrees of at most this many triangles are finished by ONE workgroup in LDS (k_bvh_sub)

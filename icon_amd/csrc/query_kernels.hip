@@ -73,10 +73,12 @@ __global__ __launch_bounds__(kCoopWaves * 64) void k_sdf_query_coop(MeshDev m, c
 // ALT (diagnostics, icon_work_set_tie_rule): the alternative tie rule - highest face index among the faces within
 // `tie_ulps` float32 ulps of the minimum d^2 (nearest_packet_alt) - for measuring how much of the output hangs on
 // the unpinned tie behaviour of the kaolin leaf (lib/dataset/mesh_util.py:374-390).
-template <bool LATTICE, bool ALT = false>
-__global__ __launch_bounds__(kBlock) void k_nearest(MeshDev m, Calib cal, LatticeMap L, const float *__restrict__ pts, int64_t N,
-                                                    NearRef near, const int32_t *__restrict__ perm,
-                                                    float sdf_clip, int tie_ulps, const LatticeFast *lf)
+// CLAMP: the half-unit, clamped evaluation of the oriented boxes (nearest_packet; "box_clamp").  k_nearest<lattice> itself runs it;
+// k_nearest_plain is the same lattice launch on pair_box_bound, for meshes created with the option off (A/B, tests).
+template <bool LATTICE, bool ALT, bool CLAMP>
+__device__ __forceinline__ void nearest_launch(const MeshDev &m, const Calib &cal, LatticeMap L, const float *__restrict__ pts, int64_t N,
+                                               const NearRef &near, const int32_t *__restrict__ perm,
+                                               float sdf_clip, int tie_ulps, const LatticeFast *lf)
 {
     __shared__ int lds[(kBlock / 64) * kStackDepth];
     int64_t i; bool live; f3 p;
@@ -107,12 +109,25 @@ __global__ __launch_bounds__(kBlock) void k_nearest(MeshDev m, Calib cal, Lattic
         p = project(resolve_calib(cal), mk3(pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]));
         root = mesh_root(m);
     }
-    Nearest nr = nearest_packet(m, p, live, lds + (threadIdx.x >> 6) * kStackDepth, nullptr, nullptr, INFINITY, nullptr,
-                                LATTICE ? packet_center_lane(L) : 21, true, root);
+    Nearest nr = nearest_packet<false, false, CLAMP>(m, p, live, lds + (threadIdx.x >> 6) * kStackDepth, nullptr, nullptr, INFINITY, nullptr,
+                                                     LATTICE ? packet_center_lane(L) : 21, true, root);
     if (ALT) nr = nearest_packet_alt(m, p, live, lds + (threadIdx.x >> 6) * kStackDepth, (uint32_t)__float_as_int(nr.d2), (uint32_t)tie_ulps);
     // (staging the 16 x 4 x 4 block through LDS so that 16 threads store one 64-byte run removes the partial-line
     //  writes but the block-wide barrier costs 0.14 ms; not kept)
     if (live) store_near(near, i, nr, sdf_clip);
+}
+template <bool LATTICE, bool ALT = false>
+__global__ __launch_bounds__(kBlock) void k_nearest(MeshDev m, Calib cal, LatticeMap L, const float *__restrict__ pts, int64_t N,
+                                                    NearRef near, const int32_t *__restrict__ perm,
+                                                    float sdf_clip, int tie_ulps, const LatticeFast *lf)
+{
+    nearest_launch<LATTICE, ALT, LATTICE && !ALT>(m, cal, L, pts, N, near, perm, sdf_clip, tie_ulps, lf);
+}
+__global__ __launch_bounds__(kBlock) void k_nearest_plain(MeshDev m, Calib cal, LatticeMap L, const float *__restrict__ pts, int64_t N,
+                                                          NearRef near, const int32_t *__restrict__ perm,
+                                                          float sdf_clip, int tie_ulps, const LatticeFast *lf)
+{
+    nearest_launch<true, false, false>(m, cal, L, pts, N, near, perm, sdf_clip, tie_ulps, lf);
 }
 
 // Lattices of few packets (33^3 .. 65^3 slabs: the first level of the reference's schedule): one PACKET per workgroup, its walk
@@ -194,6 +209,7 @@ __global__ __launch_bounds__(kBlock) void k_traversal_stats(MeshDev m, LatticeMa
 
 // diagnostics: what the pair boxes do to the lattice walk - per packet, the nodes visited, the leaf pairs offered to the
 // distance test and the pairs tested (icon_debug_pair_stats; tools/pair_box_model.py predicts the last two on the CPU)
+template <bool CLAMP>
 __global__ __launch_bounds__(kBlock) void k_pair_stats(MeshDev m, LatticeMap L, unsigned long long *out /* [6] */)
 {
     __shared__ int lds[(kBlock / 64) * kStackDepth];
@@ -204,7 +220,7 @@ __global__ __launch_bounds__(kBlock) void k_pair_stats(MeshDev m, LatticeMap L, 
     lattice_clamp(L, ix, iy, iz, cx, cy, cz);
     const f3 p = lattice_world(L.res, cx, cy, cz + L.z0);
     int nn = 0, nt = 0, no = 0, ns = 0, nl = 0, nb = 0;
-    nearest_packet<true>(m, p, live, lds + (threadIdx.x >> 6) * kStackDepth, &nn, &nt, INFINITY, nullptr, packet_center_lane(L), false, 0, &no, &ns, &nl, &nb);
+    nearest_packet<true, false, CLAMP>(m, p, live, lds + (threadIdx.x >> 6) * kStackDepth, &nn, &nt, INFINITY, nullptr, packet_center_lane(L), false, 0, &no, &ns, &nl, &nb);
     if ((threadIdx.x & 63) == 0) {
         atomicAdd(&out[0], 1ull); atomicAdd(&out[1], (unsigned long long)nn);
         atomicAdd(&out[2], (unsigned long long)no); atomicAdd(&out[3], (unsigned long long)ns);
@@ -849,6 +865,12 @@ int node_box_enabled()
     if (g_node_box < 0) g_node_box = getenv("ICON_AMD_NODE_BOX") ? (atoi(getenv("ICON_AMD_NODE_BOX")) != 0) : 1;
     return g_node_box;
 }
+int g_box_clamp = -1;                                              // likewise ICON_AMD_BOX_CLAMP / "box_clamp"
+int box_clamp_enabled()
+{
+    if (g_box_clamp < 0) g_box_clamp = getenv("ICON_AMD_BOX_CLAMP") ? (atoi(getenv("ICON_AMD_BOX_CLAMP")) != 0) : 1;
+    return g_box_clamp;
+}
 int pair_box_enabled()
 {
     if (g_pair_box < 0) g_pair_box = getenv("ICON_AMD_PAIR_BOX") ? (atoi(getenv("ICON_AMD_PAIR_BOX")) != 0) : 1;
@@ -1025,6 +1047,7 @@ int launch_nearest(const icon_mesh_t *mesh, const Calib &cal, const LatticeMap &
         if (nw == 16) hipLaunchKernelGGL(k_nearest_shared<16>, dim3((unsigned)nb * 4), dim3(16 * 64), 0, st, mesh->dev, L, near, sdf_clip, dbg);
         else if (nw == 8) hipLaunchKernelGGL(k_nearest_shared<8>, dim3((unsigned)nb * 4), dim3(8 * 64), 0, st, mesh->dev, L, near, sdf_clip, dbg);
         else if (alt) hipLaunchKernelGGL((k_nearest<LATTICE, true>), dim3((unsigned)nb), dim3(kBlock), 0, st, mesh->dev, cal, L, d_points, N, near, perm, sdf_clip, work->tie_ulps, lf);
+        else if (LATTICE && !mesh->dev.box_clamp) hipLaunchKernelGGL(k_nearest_plain, dim3((unsigned)nb), dim3(kBlock), 0, st, mesh->dev, cal, L, d_points, N, near, perm, sdf_clip, 0, lf);
         else hipLaunchKernelGGL((k_nearest<LATTICE, false>), dim3((unsigned)nb), dim3(kBlock), 0, st, mesh->dev, cal, L, d_points, N, near, perm, sdf_clip, 0, lf);
         if (work->prof) { (void)hipEventRecord(work->ev[5], st); work->ev_search = true; }
     }
@@ -1495,7 +1518,8 @@ static int walk_stats(const icon_mesh_t *mesh, int res, int z0, int z1, unsigned
     unsigned long long *d = nullptr;
     ICON_HIP(hipMalloc((void **)&d, 6 * sizeof(unsigned long long)));
     ICON_HIP(hipMemset(d, 0, 6 * sizeof(unsigned long long)));
-    hipLaunchKernelGGL(k_pair_stats, dim3((unsigned)(L.tx * L.ty * L.tz)), dim3(kBlock), 0, 0, mesh->dev, L, d);
+    if (mesh->dev.box_clamp) hipLaunchKernelGGL(k_pair_stats<true>, dim3((unsigned)(L.tx * L.ty * L.tz)), dim3(kBlock), 0, 0, mesh->dev, L, d);
+    else hipLaunchKernelGGL(k_pair_stats<false>, dim3((unsigned)(L.tx * L.ty * L.tz)), dim3(kBlock), 0, 0, mesh->dev, L, d);
     hipError_t e = hipMemcpy(h, d, 6 * sizeof(unsigned long long), hipMemcpyDeviceToHost);
     (void)hipFree(d);
     if (e != hipSuccess) return fail(ICON_ERR_HIP, std::string("walk stats: ") + hipGetErrorString(e));
@@ -1547,7 +1571,8 @@ extern "C" int icon_work_status(icon_work_t *work)
 
 // test / A-B switches by name (process-wide): "pair_box" 0 / 1 - the packet walk culls leaf pairs by their oriented boxes (meshes
 // and mesh batches created AFTERWARDS; 0: they run the walk without the cull); "node_box" 0 / 1 - the packet walk tests the children of the bottom
-// inner nodes by oriented boxes (likewise: meshes created afterwards; 0: AABBs only); "lattice_fast" 0 / 1; "share_waves" wavefronts per shared walk (-1 = by launch size;
+// inner nodes by oriented boxes (likewise: meshes created afterwards; 0: AABBs only); "box_clamp" 0 / 1 - the lattice launches of k_nearest evaluate the
+// oriented boxes in half units with the excess clamped (mesh_rules.h: pair_box_bound_half; likewise: meshes created afterwards); "lattice_fast" 0 / 1; "share_waves" wavefronts per shared walk (-1 = by launch size;
 // 4: the adaptive schedule's searches only); "share_ring" forced ring size of the shared walks (0 = 64),
 // "share_lose_push" the ticket of the push that is announced but never stored (0 = none), "share_spin_log2" wait bound 2^n polls
 // (0 = 2^18).  Production leaves all of them alone.
@@ -1559,6 +1584,7 @@ extern "C" int icon_debug_set_option(const char *key, int value)
     else if (k == "share_waves") { ICON_ARG(value == -1 || value == 1 || value == 4 || value == 8 || value == 16, "share_waves: -1 (by launch size), 1, 4, 8 or 16"); g_share_waves = value; }
     else if (k == "pair_box") g_pair_box = value ? 1 : 0;
     else if (k == "node_box") g_node_box = value ? 1 : 0;
+    else if (k == "box_clamp") g_box_clamp = value ? 1 : 0;
     else if (k == "share_ring") { ICON_ARG(value == 0 || (value >= 2 && value <= 64 && (value & (value - 1)) == 0), "share_ring: 0 or a power of two in 2..64"); g_share_ring = value; }
     else if (k == "share_lose_push") { ICON_ARG(value >= 0, "share_lose_push: a ticket >= 1, or 0"); g_share_lose = value; }
     else if (k == "share_spin_log2") { ICON_ARG(value >= 0 && value < 30, "share_spin_log2: 0..29"); g_share_spin_log2 = value; }

@@ -70,6 +70,14 @@ class _Handle:
             pass
 
 
+def set_debug_option(key: str, value: int) -> None:
+    """A/B switches of the native library by name (icon_debug_set_option; process-wide, production leaves them alone):
+    "pair_box", "node_box" and "box_clamp" are read when a mesh is created - a MeshHandle made afterwards runs the walk
+    with the oriented boxes of the leaf pairs / of the bottom inner nodes off or on, and evaluates them by pair_box_bound
+    (0) or by the half-unit clamped form pair_box_bound_half (1, the default) in the lattice launches."""
+    check(_lib.lib().icon_debug_set_option(key.encode(), C.c_int(int(value))), "icon_debug_set_option")
+
+
 class MeshHandle(_Handle):
     """Per-image SMPL body (icon_mesh_create_arena): the tensors of ``smpl_feat_dict``
     (lib/net/HGPIFuNet.py:236-240), batch size 1.  Built by kernels on the current stream into a block of the caching

@@ -428,6 +428,9 @@ int icon_debug_pair_box(const float *corners, int64_t n_pairs, const float *pts,
  * walk's bound on PairBox-shaped records recs[i][16][2]: bound[i][c][j] = component c at point j (pts[j], or pts[i][j]) */
 int icon_debug_range_box(const float *tris, int64_t n_tris, float *rec, int32_t *kind);
 int icon_debug_box_bound(const float *recs, int64_t n_recs, const float *pts, int64_t n_pts, int shared_pts, float *bound);
+/* host only: the same records by the "box_clamp" evaluation (half units, excess clamped to [0, 1]): a quarter of icon_debug_box_bound's
+ * value bit for bit while no axis excess passes 2.0, less beyond; same layout */
+int icon_debug_box_bound_half(const float *recs, int64_t n_recs, const float *pts, int64_t n_pts, int shared_pts, float *bound);
 
 /* Seg3dLossless._forward_faster's None rule (lib/common/seg3d_lossless.py:173-177: the call returns None when nothing exceeds
  * 0.5 on the COARSEST lattice) for a dense device volume d_occ [res,res,res]: the coarsest lattice is the sub-lattice of strides

@@ -10,9 +10,10 @@ node boxes: asserted.
     python tools/node_box_model.py --mesh body --res 257 --packets 250 --seed 1
     python tools/node_box_model.py --mesh body --res 65 --packets 0 --thresholds 16     # every packet: the GPU's counters
 
-Estimated VALU instructions per packet = 25 per AABB node visit + 32 per oriented node visit (the 22 of pair_box_bound, the
-votes, the ordering) + 30 per leaf visit (the packed pair-box evaluation) + 50 per pair tested + 70 of set-up; dependent load
-rounds = node visits + leaf visits.  The GPU's counters for the same walk: tools/trav_stats.py (MeshHandle.walk_stats).
+Estimated VALU instructions per packet, counted in the compiled loop of k_nearest<lattice> with "box_clamp" on
+(profiles/walk_diet_isa.txt) = 20 per AABB node visit (15 box + 2 votes, ~3 of push / pop per visit) + 26 per oriented node visit
+(21 of pair_box_bound_half + 2 votes, the same ~3) + 24 per leaf visit (21 + 2, the bound update of a tested leaf) + 61 per pair
+tested (51 distance + 10 key update) + 70 of set-up; dependent load rounds = node visits + leaf visits.  The GPU's counters for the same walk: tools/trav_stats.py (MeshHandle.walk_stats).
 """
 import argparse
 import os
@@ -219,7 +220,7 @@ def model(tree, res, blocks, variants):
 
 
 def estimate(r):
-    return 25 * r["aabb"] + 32 * r["obox"] + 30 * r["leaves"] + 50 * r["tested"] + 70
+    return 20 * r["aabb"] + 26 * r["obox"] + 24 * r["leaves"] + 61 * r["tested"] + 70
 
 
 def main():
