@@ -597,6 +597,44 @@ int icon_render_normal_backward(const float *d_verts, int64_t V, const void *d_f
                                 const float *d_grad_images, float *d_grad_verts,
                                 void *d_scratch, int64_t scratch_bytes, void *stream);
 
+/* ---- the cloth refinement step without the renderer, forwards and backwards ------------------------------
+ * what one iteration of the cloth loop of apps/infer.py:405-476 computes besides its normal maps: the LocalAffine deformation
+ * y = A x + b with the stiffness and rigidity means (lib/net/local_affine.py) and the mesh shape priors of
+ * update_mesh_shape_prior_losses (lib/dataset/mesh_util.py:168-176: mesh_edge_loss, pytorch3d's mesh_normal_consistency and
+ * mesh_laplacian_smoothing(method="uniform")).  The rule is DESIGN.md 4.16 (PARITY UNPINNED); every expression is evaluated in
+ * float64 from the float32 inputs and rounded once.
+ * Topology (icon_amd/cloth.py: ClothTopology builds it once per mesh): d_edges [E,2]; the neighbour lists d_nbr_off [V+1] /
+ * d_nbr [2E] (row v: the other end of every edge at v, multiplicity kept); d_pairs [P,4] = (v0, v1, a, c), the face pairs over
+ * an edge (v0, v1) with their third vertices; d_inc_off [V+1] / d_inc [4P] (row v: pair * 4 + slot for every slot of d_pairs
+ * that holds v).  All of them int64 when index_int64 != 0, else int32 - read in place; an entry that names nothing is skipped.
+ * B meshes share the lists: d_x [B,V,3], d_A [B,V,3,3], d_b [B,V,3,1], d_y [B,V,3] f32.  The scalars (d_stiffness, d_rigid,
+ * d_edge, d_nc, d_laplacian) and their incoming gradients are DEVICE pointers to one f32 each; E = 0 gives stiffness 0 and
+ * edge 0, P = 0 gives nc 0.  local_affine_backward: d_grad_A / d_grad_b of sum(y grad_y) + stiffness grad_stiffness + rigid
+ * grad_rigid; x gets no gradient.  mesh_priors: d_verts [V,3] of ONE mesh; `terms` is a mask of ICON_PRIOR_*: a term left out
+ * is not computed, its output is 0 and its incoming gradient is not read; d_grad_verts [V,3] out, every entry written.
+ * d_scratch: device memory of at least icon_local_affine_bytes(B, V, E) / icon_mesh_priors_bytes(V, E, P) bytes, 256-byte
+ * aligned, owned by the caller; a backward call does not need what the forward call left there, and
+ * icon_local_affine_backward - a single gather - takes none.  Enqueued on `stream` (two
+ * launches per call, one for icon_local_affine_backward, whatever the sizes): no allocation, no synchronisation, nothing read
+ * back; no floating-point atomics: bit-identical from run to run and from int32 and int64 indices. */
+enum { ICON_PRIOR_EDGE = 1, ICON_PRIOR_NC = 2, ICON_PRIOR_LAPLACIAN = 4 };
+int icon_local_affine_bytes(int64_t B, int64_t V, int64_t E, int64_t *bytes);
+int icon_local_affine_forward(const float *d_x, const float *d_A, const float *d_b, int64_t B, int64_t V,
+                              const void *d_edges, int64_t E, int index_int64, float *d_y, float *d_stiffness,
+                              float *d_rigid, void *d_scratch, int64_t scratch_bytes, void *stream);
+int icon_local_affine_backward(const float *d_x, const float *d_A, const float *d_b, int64_t B, int64_t V,
+                               const void *d_nbr_off, const void *d_nbr, int64_t E, int index_int64,
+                               const float *d_grad_y, const float *d_grad_stiffness, const float *d_grad_rigid,
+                               float *d_grad_A, float *d_grad_b, void *stream);
+int icon_mesh_priors_bytes(int64_t V, int64_t E, int64_t P, int64_t *bytes);
+int icon_mesh_priors_forward(const float *d_verts, int64_t V, const void *d_edges, const void *d_nbr_off, const void *d_nbr, int64_t E,
+                             const void *d_pairs, int64_t P, int index_int64, float target_length, int terms,
+                             float *d_edge, float *d_nc, float *d_laplacian, void *d_scratch, int64_t scratch_bytes, void *stream);
+int icon_mesh_priors_backward(const float *d_verts, int64_t V, const void *d_edges, const void *d_nbr_off, const void *d_nbr, int64_t E,
+                              const void *d_pairs, const void *d_inc_off, const void *d_inc, int64_t P, int index_int64,
+                              float target_length, int terms, const float *d_grad_edge, const float *d_grad_nc,
+                              const float *d_grad_laplacian, float *d_grad_verts, void *d_scratch, int64_t scratch_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
