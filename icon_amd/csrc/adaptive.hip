@@ -367,7 +367,7 @@ __global__ __launch_bounds__(NW == 1 ? 256 : NW * 64) void k_ad_nearest(MeshDev 
         const bool live = used && ix < r && iy < r && iz < r && C[xyz(r, cx, cy, cz)] != 0;
         const f3 p = lattice_world(r, cx, cy, cz);
         Nearest nr;
-        if (NW == 1) nr = nearest_packet(m, p, live, lds + wave * kStackDepth, nullptr, nullptr, INFINITY, nullptr, P == 4 ? 21 : 0);
+        if (NW == 1) nr = nearest_packet(m, p, live, lds + wave * kStackDepth, {mesh_root(m), P == 4 ? 21 : 0});
         else nr = nearest_shared<NW>(m, p, live, lds + wave * kStackDepth, smem, P == 4 ? 21 : 0, dbg);
         if (live && (NW == 1 || wave == 0)) store_near(near, ((int64_t)cz * r + cy) * r + cx, nr, sdf_clip);
     }
@@ -568,7 +568,7 @@ static int adaptive_eval_impl(const icon_mesh_t *mesh, const icon_feat_t *feat, 
             int n_cu = 0;
             if ((rc = device_cu_count(&n_cu))) return rc;
             // the number of blocks is known on the device only: a grid that fills the wave slots, every workgroup loops
-            const int share_env = share_waves_override();        // diagnostics: 1 = one wave per block
+            const int share_env = option(kOptShareWaves);        // diagnostics: 1 = one wave per block
             // wavefronts per shared walk by level: the candidates of a level grow ~4x with the resolution, the walks get shorter -
             // measured per level of the [33 .. 513] schedule (us, NW = 16 / 8 / 4 / 1): 65^3 75 / 97 / 160 / 462, 129^3 183 / 123 /
             // 142 / 311, 257^3 381 / 221 / 150 / 196 (tools/share_probe.sh): few long walks want many waves each, many walks few

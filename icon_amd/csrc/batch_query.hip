@@ -60,7 +60,7 @@ __global__ __launch_bounds__(kBlock) void k_nearest_batch(BatchDev bd, const flo
     const int64_t i = perm[(int64_t)b * bd.n + (live ? r : bd.n - 1)];
     const MeshDev m = batch_mesh_uniform(bd, b);
     const f3 p = project(batch_calib_uniform(bd, b), mk3(pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]));
-    const Nearest nr = nearest_packet(m, p, live, lds + (threadIdx.x >> 6) * kStackDepth);
+    const Nearest nr = nearest_packet(m, p, live, lds + (threadIdx.x >> 6) * kStackDepth, {mesh_root(m)});
     if (live) store_near(near, i, nr, sdf_clip);
 }
 

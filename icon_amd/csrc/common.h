@@ -411,10 +411,10 @@ int work_share_dbg(icon_work *w, ShareDbg *out);
 int work_check_err(icon_work *w);
 extern int g_qc_lanes;                // query_color.hip: lanes per face of the colour call's rasteriser ("qc_lanes"; 0 = default)
 extern int g_rn_lanes;                // render_normal.hip: lanes per face of the renderer's rasteriser ("rn_lanes"; 0 = default)
-int node_box_enabled();               // ICON_AMD_NODE_BOX / icon_debug_set_option("node_box"): likewise for the oriented boxes of the bottom inner nodes
-int box_clamp_enabled();              // ICON_AMD_BOX_CLAMP / icon_debug_set_option("box_clamp"): meshes created while it is 0 keep pair_box_bound everywhere
-int pair_box_enabled();               // ICON_AMD_PAIR_BOX / icon_debug_set_option("pair_box"): meshes created while it is 0 walk without the cull
-int share_waves_override();           // ICON_AMD_SHARE / icon_debug_set_option("share_waves"): -1 = by launch size
+// the process-wide test / A-B switches (query_kernels.hip: the table with their keys, environment variables and defaults)
+enum Opt { kOptPairBox, kOptNodeBox, kOptBoxClamp, kOptLatticeFast, kOptUnfused, kOptShellSkip, kOptShareWaves, kOptShareRing, kOptShareLose,
+           kOptShareSpinLog2, kOptCount };
+int option(Opt o);
 }  // namespace icon
 
 struct icon_work {

@@ -242,6 +242,39 @@ __device__ __forceinline__ float prune_threshold(float best)
     return fmaf(best, 1.000083f, 2.1e-7f);
 }
 
+typedef int i2 __attribute__((ext_vector_type(2)));
+typedef __attribute__((address_space(4))) const i2 ci2;
+
+// The two visits every packet walk shares (nearest_packet, nearest_shared, nearest_packet_alt); what a walk does with the keys
+// and the votes is its own.
+// Leaf: the keys of the two triangles of one TriPre pair.  S3 as ONE unsigned 64-bit minimum: key = (bits of d^2) << 32 | face.
+// d^2 >= +0, so its bit pattern orders like the value; equal d^2 -> lower face id wins; NaN (bits above +inf) never wins; a
+// padding copy has the same key as its original.
+struct PairKeys { unsigned long long k0, k1; };
+__device__ __forceinline__ PairKeys leaf_pair_keys(const MeshDev &m, int leaf, int pr, f3 p)
+{
+    cf2 *q = reinterpret_cast<cf2 *>(as_const(&m.leaves[leaf].pair[pr]));
+    const f2 d2 = tri_dist2_pair(p, q);
+    const f2 fc = q[22];
+    PairKeys k;
+    k.k0 = ((unsigned long long)(unsigned)__float_as_int(d2.x) << 32) | (unsigned)__float_as_int(fc.x);
+    k.k1 = ((unsigned long long)(unsigned)__float_as_int(d2.y) << 32) | (unsigned)__float_as_int(fc.y);
+    return k;
+}
+// AABB inner node: both children's box distances and the node's child references, integers from the record's own scalar load
+// (one 64-byte load): lo.x lo.y lo.z hi.x hi.y hi.z (children 0,1), ids, walk ids.  `walk`: the references that carry
+// kNodeBoxFlag (wave-uniform; nearest_packet with node boxes only).
+struct AabbVisit { f2 dd; i2 ids; };
+__device__ __forceinline__ AabbVisit aabb_visit(const MeshDev &m, int node, f3 p, bool walk = false)
+{
+    AabbVisit v;
+    v.dd = box_dist2_pair(reinterpret_cast<cf2 *>(as_const(m.nodes + node)), p);
+    ci2 *qi = reinterpret_cast<ci2 *>(as_const(m.nodes + node));
+    const i2 plain = qi[6], flagged = qi[7];
+    v.ids = walk ? flagged : plain;
+    return v;
+}
+
 // BVH2 PACKET traversal: the 64 lanes of a wavefront descend the tree TOGETHER.  Control flow, the
 // node / leaf addresses and the stack are wave-uniform (scalar registers, scalar loads, one LDS
 // word per stack entry per wave); every lane tests its own point against the shared node boxes
@@ -260,25 +293,31 @@ __device__ __forceinline__ float prune_threshold(float best)
 // The loop is written for its listing (profiles/walk_diet_isa.txt): child references are integers from the scalar load in both
 // kinds of inner visit, the key and the threshold are updated in place, both pair ballots become bits on the scalar unit, and
 // there is ONE pop, at the loop's tail.
-typedef int i2 __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(4))) const i2 ci2;
+// STATS (k_walk_stats): the visits are counted per packet into a WalkStats.
+struct WalkStats { int nodes, tris, offered, tested, leaves, obox; };
+// root: the BVH root - mesh_root(m), or the copy the caller already holds in a register.  center_lane: the lane whose box
+// distances order the two children (packet_center_lane; 21 = the centre of a 4^3 block, also right for Morton-ordered points).
+// stats: STATS only, zeroed by the caller.  runner_up: TIES only.
+struct WalkArgs {
+    int root;
+    int center_lane = 21;
+    WalkStats *stats = nullptr;
+    unsigned long long *runner_up = nullptr;
+};
 template <bool STATS = false, bool TIES = false, bool CLAMP = false>
 __device__ __forceinline__ Nearest nearest_packet(const MeshDev &m, f3 p, bool live, int *wstack /* LDS, kStackDepth ints of this wave */,
-                                                  int *n_nodes = nullptr, int *n_tris = nullptr, float thr0 = INFINITY,
-                                                  unsigned long long *runner_up = nullptr, int center_lane = 21,
-                                                  bool have_root = false, int root = 0, int *n_offered = nullptr, int *n_tested = nullptr,
-                                                  int *n_leaves = nullptr, int *n_obox = nullptr)
+                                                  const WalkArgs &a)
 {
     Nearest nr; nr.d2 = INFINITY; nr.slot = 0; nr.face = 0x7fffffff;
     // the leaf pairs' oriented boxes (PairBox), or null: "pair_box" off - every pair of a visited leaf is tested (wave-uniform)
     const PairBox *pbox = m.pbox_off ? reinterpret_cast<const PairBox *>(m.leaves) + m.pbox_off : nullptr;
     unsigned long long key = 0x7f8000007fffffffull;   // (+inf, INT_MAX)
     unsigned long long key2 = 0x7f8000007fffffffull;
-    float thr = live ? thr0 : -INFINITY;
+    float thr = live ? INFINITY : -INFINITY;
     float thq = thr * 0.25f;                          // CLAMP: the bound the half-unit boxes vote against (an exact multiply)
     const f3 ph = mk3(p.x * 0.5f, p.y * 0.5f, p.z * 0.5f);
     int sp = 0;
-    int cur = have_root ? root : mesh_root(m);        // (wave-uniform choice; the caller that holds the root in a register passes it)
+    int cur = a.root;
     // the node boxes (PairBox records by node id), or null: "node_box" off - AABBs all the way down.  A reference >= 0 with
     // kNodeBoxFlag names an oriented parent: a node whose children both hold <= kNodeBoxMaxTris triangles and are tested by one
     // oriented box each (mesh_rules.h).  The flag travels with the reference - in the parent's record (an AABB parent: the spare
@@ -291,8 +330,7 @@ __device__ __forceinline__ Nearest nearest_packet(const MeshDev &m, f3 p, bool l
         if (cur < 0) {
             const int code = ~cur;
             const int leaf = code >> 2, cnt = (code & 3) + 1;
-            if (STATS) *n_tris += cnt;
-            if (STATS && n_leaves) ++*n_leaves;
+            if (STATS) { a.stats->tris += cnt; ++a.stats->leaves; }
             const int npairs = __builtin_amdgcn_readfirstlane((cnt + 1) >> 1);      // 1 or 2, wave-uniform (scalar loop counter)
             // Most pairs of a visited leaf are out of every lane's reach (the leaf's AABB admits a slanted patch from far away:
             // DESIGN.md 4.1): both pairs' oriented boxes in one packed evaluation, then the distance test only for the pairs
@@ -308,18 +346,12 @@ __device__ __forceinline__ Nearest nearest_packet(const MeshDev &m, f3 p, bool l
                 const int any0 = __builtin_amdgcn_ballot_w64(bb.x <= lim) != 0 ? 2 : 0, any1 = __builtin_amdgcn_ballot_w64(bb.y <= lim) != 0 ? 4 : 0;
                 need &= any0 | any1;
             }
-            if (STATS && n_offered) { *n_offered += npairs; *n_tested += __builtin_popcount((unsigned)need); }
+            if (STATS) { a.stats->offered += npairs; a.stats->tested += __builtin_popcount((unsigned)need); }
             if (need) {                                          // (nothing tested: key and bound are what they were)
                 do {
                     const int pr = __builtin_ctz((unsigned)need) - 1;
-                    cf2 *q = reinterpret_cast<cf2 *>(as_const(&m.leaves[leaf].pair[pr]));
-                    const f2 d2 = tri_dist2_pair(p, q);
-                    const f2 fc = q[22];
-                    // S3 as ONE unsigned 64-bit minimum: key = (bits of d^2) << 32 | face.  d^2 >= +0, so
-                    // its bit pattern orders like the value; equal d^2 -> lower face id wins; NaN (bits
-                    // above +inf) never wins; a padding copy has the same key as its original.
-                    const unsigned long long k0 = ((unsigned long long)(unsigned)__float_as_int(d2.x) << 32) | (unsigned)__float_as_int(fc.x);
-                    const unsigned long long k1 = ((unsigned long long)(unsigned)__float_as_int(d2.y) << 32) | (unsigned)__float_as_int(fc.y);
+                    const PairKeys k = leaf_pair_keys(m, leaf, pr, p);
+                    const unsigned long long k0 = k.k0, k1 = k.k1;
                     // (the winner's slot is looked up from its face id at the end: nothing else to carry per test; a parked
                     //  lane computes on a clamped copy of a real point and may update its key freely - it never votes
                     //  (thr = -inf) and its result is not stored - so the update needs no `live` mask)
@@ -337,14 +369,14 @@ __device__ __forceinline__ Nearest nearest_packet(const MeshDev &m, f3 p, bool l
             }
             pop = true;
         } else {
-            if (STATS) ++*n_nodes;
+            if (STATS) ++a.stats->nodes;
             // both children's lower bounds in one packed evaluation: box distances of an AABB parent, the oriented-box bound of an
             // oriented parent's record - either way <= the real d^2 of every triangle below the child, which is all the vote relies on
             i2 ids;                                              // the child references: integers from the record's own scalar load, both ways
             unsigned long long b0, b1;                           // the votes
             f2 dd;                                               // (in half units at an oriented parent under CLAMP: one visit, one unit)
             if (cur & kNodeBoxFlag) {
-                if (STATS && n_obox) ++*n_obox;
+                if (STATS) ++a.stats->obox;
                 const PairBox *rec = nbox + (cur & ~kNodeBoxFlag);
                 cf2 *q = reinterpret_cast<cf2 *>(as_const(rec));
                 dd = CLAMP ? pair_box_bound_half(q, ph.x, ph.y, ph.z) : pair_box_bound(q, p.x, p.y, p.z);
@@ -352,11 +384,8 @@ __device__ __forceinline__ Nearest nearest_packet(const MeshDev &m, f3 p, bool l
                 ids = reinterpret_cast<ci2 *>(as_const(rec))[15];
                 b0 = __builtin_amdgcn_ballot_w64(dd.x <= lim); b1 = __builtin_amdgcn_ballot_w64(dd.y <= lim);
             } else {
-                cf2 *q = reinterpret_cast<cf2 *>(as_const(m.nodes + cur));   // lo.x lo.y lo.z hi.x hi.y hi.z (children 0,1), ids, walk ids
-                dd = box_dist2_pair(q, p);
-                ci2 *qi = reinterpret_cast<ci2 *>(as_const(m.nodes + cur));
-                const i2 plain = qi[6], walk = qi[7];                        // (one 64-byte scalar load either way)
-                ids = nbox ? walk : plain;
+                const AabbVisit v = aabb_visit(m, cur, p, nbox != nullptr);
+                dd = v.dd; ids = v.ids;
                 b0 = __builtin_amdgcn_ballot_w64(dd.x <= thr); b1 = __builtin_amdgcn_ballot_w64(dd.y <= thr);
             }
             const int c0 = ids.x, c1 = ids.y;
@@ -364,8 +393,8 @@ __device__ __forceinline__ Nearest nearest_packet(const MeshDev &m, f3 p, bool l
             pop = false;
             if (v0 && v1) {
                 // order by the block's centre lane; non-negative floats order like their bit patterns
-                const int e0 = __builtin_amdgcn_readlane(__float_as_int(dd.x), center_lane);
-                const int e1 = __builtin_amdgcn_readlane(__float_as_int(dd.y), center_lane);
+                const int e0 = __builtin_amdgcn_readlane(__float_as_int(dd.x), a.center_lane);
+                const int e1 = __builtin_amdgcn_readlane(__float_as_int(dd.y), a.center_lane);
                 const bool first0 = e0 <= e1;
                 wstack[sp++] = first0 ? c1 : c0;
                 cur = first0 ? c0 : c1;
@@ -380,7 +409,7 @@ __device__ __forceinline__ Nearest nearest_packet(const MeshDev &m, f3 p, bool l
     }
     nr.d2 = __int_as_float((int)(key >> 32)); nr.face = (int)(key & 0xffffffffu);
     nr.slot = (nr.face != 0x7fffffff) ? m.face2slot[nr.face] : 0;
-    if (TIES) *runner_up = key2;
+    if (TIES) *a.runner_up = key2;
     return nr;
 }
 
@@ -538,24 +567,18 @@ __device__ __forceinline__ Nearest nearest_shared(const MeshDev &m, f3 p, bool l
                 const int leaf = code >> 2, cnt = (code & 3) + 1;
                 const int npairs = __builtin_amdgcn_readfirstlane((cnt + 1) >> 1);
                 for (int pr = 0; pr < npairs; ++pr) {
-                    cf2 *q = reinterpret_cast<cf2 *>(as_const(&m.leaves[leaf].pair[pr]));
-                    const f2 d2 = tri_dist2_pair(p, q);
-                    const f2 fc = q[22];
-                    const unsigned long long k0 = ((unsigned long long)(unsigned)__float_as_int(d2.x) << 32) | (unsigned)__float_as_int(fc.x);
-                    const unsigned long long k1 = ((unsigned long long)(unsigned)__float_as_int(d2.y) << 32) | (unsigned)__float_as_int(fc.y);
-                    key = (k0 < key) ? k0 : key;
-                    key = (k1 < key) ? k1 : key;
+                    const PairKeys k = leaf_pair_keys(m, leaf, pr, p);
+                    key = (k.k0 < key) ? k.k0 : key;
+                    key = (k.k1 < key) ? k.k1 : key;
                 }
                 const unsigned mine = (unsigned)(key >> 32);
                 const unsigned old = atomicMin(&S.thr[lane], mine);            // d^2 >= +0: the bit patterns order like the values
                 thr = live ? prune_threshold(__uint_as_float(min(old, mine))) : thr;
                 break;
             }
-            cf2 *q = reinterpret_cast<cf2 *>(as_const(m.nodes + cur));
-            const f2 dd = box_dist2_pair(q, p);
-            const float d0 = dd.x, d1 = dd.y;
-            const f2 ids = q[6];
-            const int c0 = __float_as_int(ids.x), c1 = __float_as_int(ids.y);
+            const AabbVisit v = aabb_visit(m, cur, p);
+            const float d0 = v.dd.x, d1 = v.dd.y;
+            const int c0 = v.ids.x, c1 = v.ids.y;
             const bool v0 = __any(d0 <= thr), v1 = __any(d1 <= thr);
             if (v0 && v1) {
                 const int e0 = __builtin_amdgcn_readlane(__float_as_int(d0), center_lane);
@@ -601,22 +624,18 @@ __device__ __forceinline__ Nearest nearest_packet_alt(const MeshDev &m, f3 p, bo
             const int leaf = code >> 2, cnt = (code & 3) + 1;
             const int npairs = __builtin_amdgcn_readfirstlane((cnt + 1) >> 1);
             for (int pr = 0; pr < npairs; ++pr) {
-                cf2 *q = reinterpret_cast<cf2 *>(as_const(&m.leaves[leaf].pair[pr]));
-                const f2 d2 = tri_dist2_pair(p, q);
-                const f2 fc = q[22];
-                const uint32_t b0 = (uint32_t)__float_as_int(d2.x), b1 = (uint32_t)__float_as_int(d2.y);
-                const int f0 = __float_as_int(fc.x), f1 = __float_as_int(fc.y);
+                const PairKeys k = leaf_pair_keys(m, leaf, pr, p);
+                const uint32_t b0 = (uint32_t)(k.k0 >> 32), b1 = (uint32_t)(k.k1 >> 32);
+                const int f0 = (int)(uint32_t)k.k0, f1 = (int)(uint32_t)k.k1;
                 if (b0 <= lim && f0 > face) { face = f0; fbits = b0; }
                 if (b1 <= lim && f1 > face) { face = f1; fbits = b1; }
             }
             if (sp == 0) break;
             cur = __builtin_amdgcn_readfirstlane(wstack[--sp]);
         } else {
-            cf2 *q = reinterpret_cast<cf2 *>(as_const(m.nodes + cur));
-            const f2 dd = box_dist2_pair(q, p);
-            const f2 ids = q[6];
-            const int c0 = __float_as_int(ids.x), c1 = __float_as_int(ids.y);
-            const bool v0 = __any(dd.x <= thr), v1 = __any(dd.y <= thr);
+            const AabbVisit v = aabb_visit(m, cur, p);
+            const int c0 = v.ids.x, c1 = v.ids.y;
+            const bool v0 = __any(v.dd.x <= thr), v1 = __any(v.dd.y <= thr);
             if (v0 && v1) { wstack[sp++] = c1; cur = c0; }
             else if (v0) cur = c0;
             else if (v1) cur = c1;
@@ -1170,6 +1189,22 @@ __device__ __forceinline__ f3 lattice_world(int res, int ix, int iy, int iz)
     const float rm1 = (float)(res - 1);
     const float fx = (float)ix / rm1, fy = (float)iy / rm1, fz = (float)iz / rm1;
     return mk3(fx * 2.0f + (-1.0f), fy * (-2.0f) + 1.0f, fz * 2.0f + (-1.0f));
+}
+
+// The lattice point of one lane of a packet search: lane `lane` of packet `wave` (0..3) of tile `tile` of the trimmed tiling -
+// trim, bound, point, clamp and world position in one place.  false: the tile lies beyond the trimmed tiling (the host tiled
+// the whole slab) and the workgroup has nothing to do.  cx, cy, cz: the (clamped) lattice coordinates, z relative to the slab - the
+// linear index (z R + y) R + x is formed where it is stored, after the walk, as k_nearest's LatticeFast branch does.
+struct PacketPoint { bool live; f3 p; int cx, cy, cz; };
+__device__ __forceinline__ bool packet_point(LatticeMap L, const MeshDev &m, int tile, int wave, int lane, PacketPoint &out)
+{
+    L = lattice_trim(L, m);
+    if (tile >= L.tx * L.ty * L.tz) return false;
+    int ix, iy, iz;
+    out.live = lattice_point_at(L, tile, wave, lane, ix, iy, iz);
+    lattice_clamp(L, ix, iy, iz, out.cx, out.cy, out.cz);
+    out.p = lattice_world(L.res, out.cx, out.cy, out.cz + L.z0);
+    return true;
 }
 
 // NaN / Inf / astronomically large coordinates (bad caller data) are evaluated at +-kFarCoord: far outside the cube, so the

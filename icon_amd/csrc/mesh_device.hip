@@ -919,9 +919,9 @@ void mesh_bind_arena(icon_mesh *m, const MeshLayout &L)
     d.leaves = reinterpret_cast<const LeafRec *>(b + L.leaves);
     d.dyn = m->d_dyn;
     d.n_tris = (int32_t)m->F;
-    d.pbox_off = pair_box_enabled() ? (int32_t)((L.pbox - L.leaves) / sizeof(PairBox)) : 0;
-    d.box_clamp = box_clamp_enabled();
-    d.nbox_off = node_box_enabled() ? (int32_t)((L.nbox - L.leaves) / sizeof(PairBox)) : 0;
+    d.pbox_off = option(kOptPairBox) ? (int32_t)((L.pbox - L.leaves) / sizeof(PairBox)) : 0;
+    d.box_clamp = option(kOptBoxClamp);
+    d.nbox_off = option(kOptNodeBox) ? (int32_t)((L.nbox - L.leaves) / sizeof(PairBox)) : 0;
     d.bin_start = reinterpret_cast<const int32_t *>(b + L.bin_start);
     d.bin_slots = reinterpret_cast<const int32_t *>(b + L.bin_slots);
 }

@@ -35,7 +35,7 @@ __global__ __launch_bounds__(kBlock) void k_sdf_query(MeshDev m, const float *__
     Nearest nr;
     bool ins;
     if (BRUTE) { nr = nearest_brute<kBlock>(m, p, reinterpret_cast<float *>(lds)); ins = inside_brute(m, p); }
-    else       { nr = nearest_packet(m, p, live, lds + (threadIdx.x >> 6) * kStackDepth); ins = inside_bins(m, p); }
+    else       { nr = nearest_packet(m, p, live, lds + (threadIdx.x >> 6) * kStackDepth, {mesh_root(m)}); ins = inside_bins(m, p); }
     if (!live) return;
     const SdfOut o = sdf_attrs(m, p, nr, ins);
     sdf[i] = o.sdf;
@@ -73,12 +73,12 @@ __global__ __launch_bounds__(kCoopWaves * 64) void k_sdf_query_coop(MeshDev m, c
 // ALT (diagnostics, icon_work_set_tie_rule): the alternative tie rule - highest face index among the faces within
 // `tie_ulps` float32 ulps of the minimum d^2 (nearest_packet_alt) - for measuring how much of the output hangs on
 // the unpinned tie behaviour of the kaolin leaf (lib/dataset/mesh_util.py:374-390).
-// CLAMP: the half-unit, clamped evaluation of the oriented boxes (nearest_packet; "box_clamp").  k_nearest<lattice> itself runs it;
-// k_nearest_plain is the same lattice launch on pair_box_bound, for meshes created with the option off (A/B, tests).
+// CLAMP: the half-unit, clamped evaluation of the oriented boxes (nearest_packet; "box_clamp"), lattice launches only.
+// <true, false, false> is the same lattice launch on pair_box_bound, for meshes created with the option off (A/B, tests).
 template <bool LATTICE, bool ALT, bool CLAMP>
-__device__ __forceinline__ void nearest_launch(const MeshDev &m, const Calib &cal, LatticeMap L, const float *__restrict__ pts, int64_t N,
-                                               const NearRef &near, const int32_t *__restrict__ perm,
-                                               float sdf_clip, int tie_ulps, const LatticeFast *lf)
+__global__ __launch_bounds__(kBlock) void k_nearest(MeshDev m, Calib cal, LatticeMap L, const float *__restrict__ pts, int64_t N,
+                                                    NearRef near, const int32_t *__restrict__ perm,
+                                                    float sdf_clip, int tie_ulps, const LatticeFast *lf)
 {
     __shared__ int lds[(kBlock / 64) * kStackDepth];
     int64_t i; bool live; f3 p;
@@ -92,12 +92,9 @@ __device__ __forceinline__ void nearest_launch(const MeshDev &m, const Calib &ca
             p = lattice_world_fast(lf, cx, cy, cz + L.z0);
             root = F.root;
         } else {
-            L = lattice_trim(L, m);
-            if ((int)blockIdx.x >= L.tx * L.ty * L.tz) return;
-            int ix, iy, iz;
-            live = lattice_point(L, ix, iy, iz);
-            lattice_clamp(L, ix, iy, iz, cx, cy, cz);
-            p = lattice_world(L.res, cx, cy, cz + L.z0);
+            PacketPoint pt;
+            if (!packet_point(L, m, (int)blockIdx.x, threadIdx.x >> 6, threadIdx.x & 63, pt)) return;
+            live = pt.live; p = pt.p; cx = pt.cx; cy = pt.cy; cz = pt.cz;
             root = mesh_root(m);
         }
         i = ((int64_t)cz * L.res + cy) * L.res + cx;
@@ -109,25 +106,11 @@ __device__ __forceinline__ void nearest_launch(const MeshDev &m, const Calib &ca
         p = project(resolve_calib(cal), mk3(pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]));
         root = mesh_root(m);
     }
-    Nearest nr = nearest_packet<false, false, CLAMP>(m, p, live, lds + (threadIdx.x >> 6) * kStackDepth, nullptr, nullptr, INFINITY, nullptr,
-                                                     LATTICE ? packet_center_lane(L) : 21, true, root);
+    Nearest nr = nearest_packet<false, false, CLAMP>(m, p, live, lds + (threadIdx.x >> 6) * kStackDepth, {root, LATTICE ? packet_center_lane(L) : 21});
     if (ALT) nr = nearest_packet_alt(m, p, live, lds + (threadIdx.x >> 6) * kStackDepth, (uint32_t)__float_as_int(nr.d2), (uint32_t)tie_ulps);
     // (staging the 16 x 4 x 4 block through LDS so that 16 threads store one 64-byte run removes the partial-line
     //  writes but the block-wide barrier costs 0.14 ms; not kept)
     if (live) store_near(near, i, nr, sdf_clip);
-}
-template <bool LATTICE, bool ALT = false>
-__global__ __launch_bounds__(kBlock) void k_nearest(MeshDev m, Calib cal, LatticeMap L, const float *__restrict__ pts, int64_t N,
-                                                    NearRef near, const int32_t *__restrict__ perm,
-                                                    float sdf_clip, int tie_ulps, const LatticeFast *lf)
-{
-    nearest_launch<LATTICE, ALT, LATTICE && !ALT>(m, cal, L, pts, N, near, perm, sdf_clip, tie_ulps, lf);
-}
-__global__ __launch_bounds__(kBlock) void k_nearest_plain(MeshDev m, Calib cal, LatticeMap L, const float *__restrict__ pts, int64_t N,
-                                                          NearRef near, const int32_t *__restrict__ perm,
-                                                          float sdf_clip, int tie_ulps, const LatticeFast *lf)
-{
-    nearest_launch<true, false, false>(m, cal, L, pts, N, near, perm, sdf_clip, tie_ulps, lf);
 }
 
 // Lattices of few packets (33^3 .. 65^3 slabs: the first level of the reference's schedule): one PACKET per workgroup, its walk
@@ -138,6 +121,8 @@ __global__ __launch_bounds__(NW * 64) void k_nearest_shared(MeshDev m, LatticeMa
 {
     __shared__ int lds[NW * kStackDepth];
     __shared__ __attribute__((aligned(16))) char smem[share_lds_bytes(NW)];
+    // (the prologue written out, not packet_point: with the bound check inside an inlined helper this kernel compiles to other
+    //  registers - SGPRs 94 -> 86 / 88, VGPRs 60 -> 62 - and its listing is kept as it was)
     L = lattice_trim(L, m);
     if ((int)(blockIdx.x >> 2) >= L.tx * L.ty * L.tz) return;
     int ix, iy, iz, cx, cy, cz;
@@ -159,7 +144,9 @@ __global__ __launch_bounds__(kBlock) void k_nearest_ties(MeshDev m, const float 
     if (perm) i = perm[i];
     const f3 p = clamp_raw(mk3(pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]));
     unsigned long long k2 = 0;
-    const Nearest nr = nearest_packet<false, true>(m, p, live, lds + (threadIdx.x >> 6) * kStackDepth, nullptr, nullptr, INFINITY, &k2);
+    WalkArgs wa{mesh_root(m)};
+    wa.runner_up = &k2;
+    const Nearest nr = nearest_packet<false, true>(m, p, live, lds + (threadIdx.x >> 6) * kStackDepth, wa);
     if (!live) return;
     const uint32_t b1 = (uint32_t)__float_as_int(nr.d2), b2 = (uint32_t)(k2 >> 32);
     const int f2 = (int)(k2 & 0xffffffffu);
@@ -169,62 +156,27 @@ __global__ __launch_bounds__(kBlock) void k_nearest_ties(MeshDev m, const float 
     ulps[i] = (uint8_t)(has2 ? min(b2 - b1, 255u) : 255u);
 }
 
-// diagnostics: per-wavefront BVH work of the lattice traversal (DESIGN.md reports visited nodes / point)
-__global__ __launch_bounds__(kBlock) void k_traversal_stats(MeshDev m, LatticeMap L, unsigned long long *out /* [4] */, int seeded)
-{
-    __shared__ int lds[(kBlock / 64) * kStackDepth];
-    L = lattice_trim(L, m);
-    if ((int)blockIdx.x >= L.tx * L.ty * L.tz) return;
-    int ix, iy, iz, cx, cy, cz;
-    const bool live = lattice_point(L, ix, iy, iz);
-    lattice_clamp(L, ix, iy, iz, cx, cy, cz);
-    const f3 p = lattice_world(L.res, cx, cy, cz + L.z0);
-    int nn = 0, nt = 0;
-    Nearest nr = nearest_packet<true>(m, p, live, lds + (threadIdx.x >> 6) * kStackDepth, &nn, &nt);
-    if (seeded) {       // experiment: the work of a traversal that starts from the final bound (seeded == 1) or from the
-                        // bound a coarse pass would give: best distance at the tile's centre lane + tile radius (seeded == 2)
-        nn = 0; nt = 0;
-        float thr0 = prune_threshold(nr.d2);
-        if (seeded == 2) {
-            const float dc = sqrtf(__int_as_float(__builtin_amdgcn_readlane(__float_as_int(nr.d2), 21)));
-            const float h = 2.0f / (float)(L.res - 1);
-            const float rad = 2.6f * h;                       // > half diagonal of a 4x4x4 block (sqrt(3) * 1.5 h)
-            thr0 = prune_threshold((dc + rad) * (dc + rad));
-        }
-        if (seeded == 3) {      // the bound a wave walking along x would carry over: this lane's result one packet (4 points) back
-            const float h = 2.0f / (float)(L.res - 1);
-            int na = 0, nb = 0;
-            const Nearest pv = nearest_packet<true>(m, mk3(p.x - 4.0f * h, p.y, p.z), live, lds + (threadIdx.x >> 6) * kStackDepth, &na, &nb);
-            const float dn = sqrtf(pv.d2) + 4.0001f * h;
-            thr0 = prune_threshold(dn * dn);
-        }
-        nr = nearest_packet<true>(m, p, live, lds + (threadIdx.x >> 6) * kStackDepth, &nn, &nt, thr0);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        atomicAdd(&out[0], 1ull); atomicAdd(&out[1], (unsigned long long)nn); atomicAdd(&out[2], (unsigned long long)nt);
-    }
-    if (live && nr.slot < 0) atomicAdd(&out[3], 1ull);
-    if ((threadIdx.x & 63) == 0) atomicMax(&out[4], (unsigned long long)(nn + nt));      // the longest walk: what a latency-bound launch waits for
-}
-
-// diagnostics: what the pair boxes do to the lattice walk - per packet, the nodes visited, the leaf pairs offered to the
-// distance test and the pairs tested (icon_debug_pair_stats; tools/pair_box_model.py predicts the last two on the CPU)
+// diagnostics: the work of the lattice walk, summed over the packets of a slab (icon_debug_traversal_stats / _pair_stats /
+// _walk_stats; DESIGN.md reports visited nodes / point, tools/pair_box_model.py predicts the pairs offered and tested on the CPU).
+// out = [packets, inner nodes, leaf pairs offered, pairs tested, leaves, oriented parents, triangles of the visited leaves,
+// longest walk (nodes + triangles of one packet: what a latency-bound launch waits for)].
+// The children are ordered by packet_center_lane(L) as in k_nearest: lane 21 for the default 4^3 packets, lane 0 under a
+// non-default ICON_AMD_PACKET (where traversal_stats used to keep lane 21).
 template <bool CLAMP>
-__global__ __launch_bounds__(kBlock) void k_pair_stats(MeshDev m, LatticeMap L, unsigned long long *out /* [6] */)
+__global__ __launch_bounds__(kBlock) void k_walk_stats(MeshDev m, LatticeMap L, unsigned long long *out /* [8] */)
 {
     __shared__ int lds[(kBlock / 64) * kStackDepth];
-    L = lattice_trim(L, m);
-    if ((int)blockIdx.x >= L.tx * L.ty * L.tz) return;
-    int ix, iy, iz, cx, cy, cz;
-    const bool live = lattice_point(L, ix, iy, iz);
-    lattice_clamp(L, ix, iy, iz, cx, cy, cz);
-    const f3 p = lattice_world(L.res, cx, cy, cz + L.z0);
-    int nn = 0, nt = 0, no = 0, ns = 0, nl = 0, nb = 0;
-    nearest_packet<true, false, CLAMP>(m, p, live, lds + (threadIdx.x >> 6) * kStackDepth, &nn, &nt, INFINITY, nullptr, packet_center_lane(L), false, 0, &no, &ns, &nl, &nb);
+    PacketPoint pt;
+    if (!packet_point(L, m, (int)blockIdx.x, threadIdx.x >> 6, threadIdx.x & 63, pt)) return;
+    WalkStats ws = {};
+    nearest_packet<true, false, CLAMP>(m, pt.p, pt.live, lds + (threadIdx.x >> 6) * kStackDepth,
+                                       {mesh_root(m), packet_center_lane(L), &ws});
     if ((threadIdx.x & 63) == 0) {
-        atomicAdd(&out[0], 1ull); atomicAdd(&out[1], (unsigned long long)nn);
-        atomicAdd(&out[2], (unsigned long long)no); atomicAdd(&out[3], (unsigned long long)ns);
-        atomicAdd(&out[4], (unsigned long long)nl); atomicAdd(&out[5], (unsigned long long)nb);
+        atomicAdd(&out[0], 1ull); atomicAdd(&out[1], (unsigned long long)ws.nodes);
+        atomicAdd(&out[2], (unsigned long long)ws.offered); atomicAdd(&out[3], (unsigned long long)ws.tested);
+        atomicAdd(&out[4], (unsigned long long)ws.leaves); atomicAdd(&out[5], (unsigned long long)ws.obox);
+        atomicAdd(&out[6], (unsigned long long)ws.tris);
+        atomicMax(&out[7], (unsigned long long)(ws.nodes + ws.tris));
     }
 }
 
@@ -855,33 +807,42 @@ __global__ __launch_bounds__(kScanBlock) void k_outlier_patch_self(float *__rest
 }  // namespace icon
 
 namespace icon {
-// ---- shared walks: error record and test switches ------------------------------------------------------------------------
-int g_share_ring = 0, g_share_lose = 0, g_share_spin_log2 = 0;     // icon_debug_set_option; all zero in production
-int g_lattice_fast = -1;                                          // -1: read ICON_AMD_LATTICE_FAST once (default on)
-int g_pair_box = -1;                                               // -1: read ICON_AMD_PAIR_BOX once (default on); 0 / 1: icon_debug_set_option
-int g_node_box = -1;                                               // likewise ICON_AMD_NODE_BOX / "node_box"
-int node_box_enabled()
+// ---- the process-wide switches (test / A-B; production leaves all of them alone) ------------------------------------------------
+// id: the row's place, checked below against enum Opt (common.h); key: the name icon_debug_set_option knows it by (null: an ABI
+// function of its own sets it); env: the variable read ONCE, at the first use, unless a set came first; ok: the values a set
+// accepts (null: a flag - anything non-zero is 1, from the variable too)
+struct Option { Opt id; const char *key, *env; int def; bool (*ok)(int); const char *accepts; };
+static constexpr Option kOptions[kOptCount] = {
+    {kOptPairBox, "pair_box", "ICON_AMD_PAIR_BOX", 1},              // the packet walk culls leaf pairs by their oriented boxes    } meshes and mesh
+    {kOptNodeBox, "node_box", "ICON_AMD_NODE_BOX", 1},              // ... tests the children of the bottom inner nodes by them    } batches created
+    {kOptBoxClamp, "box_clamp", "ICON_AMD_BOX_CLAMP", 1},           // the lattice launches evaluate them in half units, clamped   } AFTERWARDS
+    {kOptLatticeFast, "lattice_fast", "ICON_AMD_LATTICE_FAST", 1},  // 0: every packet derives its own set-up (A/B runs)
+    {kOptUnfused, nullptr, "ICON_AMD_UNFUSED", 0},                  // icon_debug_set_unfused: 1 forces the materialising path
+    {kOptShellSkip, nullptr, "ICON_AMD_SHELL_SKIP", 1},             // icon_debug_set_shell_skip: 0 evaluates and masks the in_cube shell
+    {kOptShareWaves, "share_waves", "ICON_AMD_SHARE", -1,           // wavefronts per shared walk (4: the adaptive schedule's searches only)
+     [](int v) { return v == -1 || v == 1 || v == 4 || v == 8 || v == 16; }, "-1 (by launch size), 1, 4, 8 or 16"},
+    {kOptShareRing, "share_ring", nullptr, 0,                       // forced ring size of the shared walks (0 = 64)
+     [](int v) { return v == 0 || (v >= 2 && v <= 64 && (v & (v - 1)) == 0); }, "0 or a power of two in 2..64"},
+    {kOptShareLose, "share_lose_push", nullptr, 0,                  // the ticket of the push that is announced but never stored (0 = none)
+     [](int v) { return v >= 0; }, "a ticket >= 1, or 0"},
+    {kOptShareSpinLog2, "share_spin_log2", nullptr, 0,              // wait bound 2^n polls (0 = 2^18)
+     [](int v) { return v >= 0 && v < 30; }, "0..29"},
+};
+constexpr bool options_in_enum_order(int o = 0) { return o == kOptCount || (kOptions[o].id == o && options_in_enum_order(o + 1)); }
+static_assert(options_in_enum_order(), "kOptions[] must list the switches in the order of enum Opt");
+static int g_opt_value[kOptCount];
+static bool g_opt_known[kOptCount];          // the value was set, or read from the environment
+int option(Opt o)
 {
-    if (g_node_box < 0) g_node_box = getenv("ICON_AMD_NODE_BOX") ? (atoi(getenv("ICON_AMD_NODE_BOX")) != 0) : 1;
-    return g_node_box;
+    if (!g_opt_known[o]) {
+        const Option &e = kOptions[o];
+        const char *v = e.env ? getenv(e.env) : nullptr;
+        g_opt_value[o] = !v ? e.def : (e.ok ? atoi(v) : atoi(v) != 0);
+        g_opt_known[o] = true;
+    }
+    return g_opt_value[o];
 }
-int g_box_clamp = -1;                                              // likewise ICON_AMD_BOX_CLAMP / "box_clamp"
-int box_clamp_enabled()
-{
-    if (g_box_clamp < 0) g_box_clamp = getenv("ICON_AMD_BOX_CLAMP") ? (atoi(getenv("ICON_AMD_BOX_CLAMP")) != 0) : 1;
-    return g_box_clamp;
-}
-int pair_box_enabled()
-{
-    if (g_pair_box < 0) g_pair_box = getenv("ICON_AMD_PAIR_BOX") ? (atoi(getenv("ICON_AMD_PAIR_BOX")) != 0) : 1;
-    return g_pair_box;
-}
-int g_share_waves = -2;                                           // -2: read ICON_AMD_SHARE once; -1: by launch size; 1 / 4 / 8 / 16: forced
-int share_waves_override()
-{
-    if (g_share_waves == -2) g_share_waves = getenv("ICON_AMD_SHARE") ? atoi(getenv("ICON_AMD_SHARE")) : -1;
-    return g_share_waves;
-}
+static void set_option(Opt o, int value) { g_opt_value[o] = kOptions[o].ok ? value : (value != 0); g_opt_known[o] = true; }
 
 int work_share_dbg(icon_work *w, ShareDbg *out)
 {
@@ -892,7 +853,7 @@ int work_share_dbg(icon_work *w, ShareDbg *out)
     void *dev = nullptr;
     ICON_HIP(hipHostGetDevicePointer(&dev, w->h_err, 0));
     out->err = (int *)dev;
-    out->ring = g_share_ring; out->lose = g_share_lose; out->spin_log2 = g_share_spin_log2;
+    out->ring = option(kOptShareRing); out->lose = option(kOptShareLose); out->spin_log2 = option(kOptShareSpinLog2);
     return ICON_OK;
 }
 
@@ -1004,8 +965,7 @@ int launch_nearest(const icon_mesh_t *mesh, const Calib &cal, const LatticeMap &
             work->cap_rows = rows;
         }
         // the record of the search's per-packet set-up (LatticeFast): 4^3 packets in the default block order only
-        if (g_lattice_fast < 0) g_lattice_fast = getenv("ICON_AMD_LATTICE_FAST") ? (atoi(getenv("ICON_AMD_LATTICE_FAST")) != 0) : 1;   // 0: every packet derives its own (A/B runs)
-        if (g_lattice_fast && (L.pk == 0 || L.pk == 4) && L.remap == 0 && L.res <= kLatticeFastMaxRes) {
+        if (option(kOptLatticeFast) && (L.pk == 0 || L.pk == 4) && L.remap == 0 && L.res <= kLatticeFastMaxRes) {
             if (!work->d_lfast) ICON_HIP(hipMalloc((void **)&work->d_lfast, kLatticeFastBytes));
             lf = work->d_lfast;
         }
@@ -1039,16 +999,16 @@ int launch_nearest(const icon_mesh_t *mesh, const Calib &cal, const LatticeMap &
             const int rc = morton_order(work, d_points, cal.m, cal.d, N, st, &perm);
             if (rc) return rc;
         }
-        const int share_env = share_waves_override();            // diagnostics: 1 = never, 8 / 16
+        const int share_env = option(kOptShareWaves);            // diagnostics: 1 = never, 8 / 16
         const int nw = (!LATTICE || alt) ? 1 : ((share_env == 1 || share_env == 8 || share_env == 16) ? share_env : share_waves(nb * 4));
         ShareDbg dbg{};
         if (nw > 1) { const int rc = work_share_dbg(work, &dbg); if (rc) return rc; }
         if (work->prof) (void)hipEventRecord(work->ev[4], st);
         if (nw == 16) hipLaunchKernelGGL(k_nearest_shared<16>, dim3((unsigned)nb * 4), dim3(16 * 64), 0, st, mesh->dev, L, near, sdf_clip, dbg);
         else if (nw == 8) hipLaunchKernelGGL(k_nearest_shared<8>, dim3((unsigned)nb * 4), dim3(8 * 64), 0, st, mesh->dev, L, near, sdf_clip, dbg);
-        else if (alt) hipLaunchKernelGGL((k_nearest<LATTICE, true>), dim3((unsigned)nb), dim3(kBlock), 0, st, mesh->dev, cal, L, d_points, N, near, perm, sdf_clip, work->tie_ulps, lf);
-        else if (LATTICE && !mesh->dev.box_clamp) hipLaunchKernelGGL(k_nearest_plain, dim3((unsigned)nb), dim3(kBlock), 0, st, mesh->dev, cal, L, d_points, N, near, perm, sdf_clip, 0, lf);
-        else hipLaunchKernelGGL((k_nearest<LATTICE, false>), dim3((unsigned)nb), dim3(kBlock), 0, st, mesh->dev, cal, L, d_points, N, near, perm, sdf_clip, 0, lf);
+        else if (alt) hipLaunchKernelGGL((k_nearest<LATTICE, true, false>), dim3((unsigned)nb), dim3(kBlock), 0, st, mesh->dev, cal, L, d_points, N, near, perm, sdf_clip, work->tie_ulps, lf);
+        else if (LATTICE && !mesh->dev.box_clamp) hipLaunchKernelGGL((k_nearest<true, false, false>), dim3((unsigned)nb), dim3(kBlock), 0, st, mesh->dev, cal, L, d_points, N, near, perm, sdf_clip, 0, lf);
+        else hipLaunchKernelGGL((k_nearest<LATTICE, false, LATTICE>), dim3((unsigned)nb), dim3(kBlock), 0, st, mesh->dev, cal, L, d_points, N, near, perm, sdf_clip, 0, lf);
         if (work->prof) { (void)hipEventRecord(work->ev[5], st); work->ev_search = true; }
     }
     ICON_HIP(hipGetLastError());
@@ -1142,17 +1102,13 @@ int patch_self(icon_work *w, int64_t N, int cmap_slot, hipStream_t st)
 
 // The f16x3 precision (the default) with the BVH search runs FUSED: no input rows in HBM (fused_f16x3.hip).
 // ICON_AMD_UNFUSED=1 forces the materialising path (tests compare the two bit for bit).
-int g_unfused = -1;      // -1: read ICON_AMD_UNFUSED once; 0 / 1: set by icon_debug_set_unfused
 bool want_fused(int precision, int search)
 {
-    if (g_unfused < 0) g_unfused = (getenv("ICON_AMD_UNFUSED") && atoi(getenv("ICON_AMD_UNFUSED")) != 0) ? 1 : 0;
-    return !g_unfused && precision == ICON_PRECISION_F16X3 && search != ICON_SEARCH_BRUTE;
+    return !option(kOptUnfused) && precision == ICON_PRECISION_F16X3 && search != ICON_SEARCH_BRUTE;
 }
 }  // namespace icon
 
 namespace {
-
-int g_shell_skip = -1;   // -1: read ICON_AMD_SHELL_SKIP once (default on); 0 / 1: set by icon_debug_set_shell_skip
 
 // Phase 1 of every query: what can be done before the outlier sign list of the whole call is known.
 //   icon prior, BVH: nearest search + k_sign (+ the call's own sign list in reference cmap mode); no rows yet
@@ -1261,7 +1217,7 @@ FusedSigns self_signs(const icon_work *work)
 
 extern "C" int icon_debug_set_unfused(int on)
 {
-    g_unfused = on ? 1 : 0;
+    set_option(kOptUnfused, on);
     return ICON_OK;
 }
 
@@ -1320,8 +1276,7 @@ static int lattice_map(int res, int z0, int z1, const icon_mesh_t *mesh, float s
     ICON_ARG(res >= 3 && (res & 1) == 1, "lattice resolution must be odd and >= 3 (seg3d_lossless.py:84-86)");
     ICON_ARG(z0 >= 0 && z1 > z0 && z1 <= res, "bad z range");
     L->res = res; L->z0 = z0; L->nz = z1 - z0;
-    if (g_shell_skip < 0) g_shell_skip = getenv("ICON_AMD_SHELL_SKIP") ? (atoi(getenv("ICON_AMD_SHELL_SKIP")) != 0) : 1;   // 0: evaluate and mask the shell (A/B runs)
-    const int off = (shell_ok && g_shell_skip) ? 1 : 0;
+    const int off = (shell_ok && option(kOptShellSkip)) ? 1 : 0;
     L->off = off;
     L->zs = std::max(z0, off); L->nzi = std::min(z1, res - off) - L->zs;
     if (L->nzi < 0) L->nzi = 0;
@@ -1489,61 +1444,52 @@ extern "C" int icon_grid_rows(const icon_mesh_t *mesh, const icon_feat_t *feat, 
     return copy_rows_out(work, d_rows, st);
 }
 
+// k_walk_stats over the planes [z0, z1) of the res^3 lattice: clamp < 0 - the walk this mesh runs ("pair_box" / "node_box" /
+// "box_clamp" as they were when the mesh was created)
+constexpr int kWalkStatWords = 8;
+static int walk_stats(const icon_mesh_t *mesh, int res, int z0, int z1, int clamp, unsigned long long h[kWalkStatWords])
+{
+    LatticeMap L;
+    int rc = lattice_map(res, z0, z1, mesh, 0.05f, true, &L);
+    if (rc) return rc;
+    unsigned long long *d = nullptr;
+    ICON_HIP(hipMalloc((void **)&d, kWalkStatWords * sizeof(unsigned long long)));
+    ICON_HIP(hipMemset(d, 0, kWalkStatWords * sizeof(unsigned long long)));
+    if (clamp < 0 ? mesh->dev.box_clamp : clamp) hipLaunchKernelGGL(k_walk_stats<true>, dim3((unsigned)(L.tx * L.ty * L.tz)), dim3(kBlock), 0, 0, mesh->dev, L, d);
+    else hipLaunchKernelGGL(k_walk_stats<false>, dim3((unsigned)(L.tx * L.ty * L.tz)), dim3(kBlock), 0, 0, mesh->dev, L, d);
+    hipError_t e = hipMemcpy(h, d, kWalkStatWords * sizeof(unsigned long long), hipMemcpyDeviceToHost);
+    (void)hipFree(d);
+    if (e != hipSuccess) return fail(ICON_ERR_HIP, std::string("walk stats: ") + hipGetErrorString(e));
+    return ICON_OK;
+}
+// out = [packets, inner nodes visited, triangles of the visited leaves, longest walk] of the un-clamped walk (pair_box_bound)
 extern "C" int icon_debug_traversal_stats(const icon_mesh_t *mesh, int res, int z0, int z1, uint64_t out[4])
 {
     ICON_ARG(mesh && out, "icon_debug_traversal_stats: null argument");
-    LatticeMap L;
-    int rc = lattice_map(res, z0, z1, mesh, 0.05f, true, &L);
+    unsigned long long h[kWalkStatWords];
+    int rc = walk_stats(mesh, res, z0, z1, 0, h);
     if (rc) return rc;
-    unsigned long long *d = nullptr;
-    ICON_HIP(hipMalloc((void **)&d, 8 * sizeof(unsigned long long)));
-    ICON_HIP(hipMemset(d, 0, 8 * sizeof(unsigned long long)));
-    hipLaunchKernelGGL(k_traversal_stats, dim3((unsigned)(L.tx * L.ty * L.tz)), dim3(kBlock), 0, 0, mesh->dev, L, d,
-                       getenv("ICON_AMD_STATS_SEEDED") ? atoi(getenv("ICON_AMD_STATS_SEEDED")) : 0);
-    unsigned long long h[8];
-    hipError_t e = hipMemcpy(h, d, sizeof(h), hipMemcpyDeviceToHost);
-    (void)hipFree(d);
-    if (e != hipSuccess) return fail(ICON_ERR_HIP, std::string("traversal stats: ") + hipGetErrorString(e));
-    out[0] = h[0]; out[1] = h[1]; out[2] = h[2]; out[3] = h[4];
+    out[0] = h[0]; out[1] = h[1]; out[2] = h[6]; out[3] = h[7];
     return ICON_OK;
 }
-
-// out = [packets, nodes visited, leaf pairs offered to the distance test, leaf pairs tested], summed over the packets of the
-// planes [z0, z1) of the res^3 lattice, for the walk this mesh runs ("pair_box" as it was when the mesh was created)
-static int walk_stats(const icon_mesh_t *mesh, int res, int z0, int z1, unsigned long long h[6])
+// out = [packets, inner nodes visited (AABB and oriented parents together), leaf pairs offered to the distance test, leaf pairs
+// tested, leaves visited, oriented parents visited] for the walk this mesh runs; icon_debug_pair_stats: the first four
+extern "C" int icon_debug_walk_stats(const icon_mesh_t *mesh, int res, int z0, int z1, uint64_t out[6])
 {
-    LatticeMap L;
-    int rc = lattice_map(res, z0, z1, mesh, 0.05f, true, &L);
+    ICON_ARG(mesh && out, "icon_debug_walk_stats: null argument");
+    unsigned long long h[kWalkStatWords];
+    int rc = walk_stats(mesh, res, z0, z1, -1, h);
     if (rc) return rc;
-    unsigned long long *d = nullptr;
-    ICON_HIP(hipMalloc((void **)&d, 6 * sizeof(unsigned long long)));
-    ICON_HIP(hipMemset(d, 0, 6 * sizeof(unsigned long long)));
-    if (mesh->dev.box_clamp) hipLaunchKernelGGL(k_pair_stats<true>, dim3((unsigned)(L.tx * L.ty * L.tz)), dim3(kBlock), 0, 0, mesh->dev, L, d);
-    else hipLaunchKernelGGL(k_pair_stats<false>, dim3((unsigned)(L.tx * L.ty * L.tz)), dim3(kBlock), 0, 0, mesh->dev, L, d);
-    hipError_t e = hipMemcpy(h, d, 6 * sizeof(unsigned long long), hipMemcpyDeviceToHost);
-    (void)hipFree(d);
-    if (e != hipSuccess) return fail(ICON_ERR_HIP, std::string("walk stats: ") + hipGetErrorString(e));
+    for (int k = 0; k < 6; ++k) out[k] = h[k];
     return ICON_OK;
 }
 extern "C" int icon_debug_pair_stats(const icon_mesh_t *mesh, int res, int z0, int z1, uint64_t out[4])
 {
     ICON_ARG(mesh && out, "icon_debug_pair_stats: null argument");
-    unsigned long long h[6];
-    int rc = walk_stats(mesh, res, z0, z1, h);
+    unsigned long long h[kWalkStatWords];
+    int rc = walk_stats(mesh, res, z0, z1, -1, h);
     if (rc) return rc;
     for (int k = 0; k < 4; ++k) out[k] = h[k];
-    return ICON_OK;
-}
-// a superset of icon_debug_pair_stats (kept for its callers' out[4]), same kernel:
-// out = [packets, inner nodes visited (AABB and oriented parents together), leaf pairs offered, leaf pairs tested, leaves visited,
-// oriented parents visited] for the walk this mesh runs ("pair_box" / "node_box" as they were when the mesh was created)
-extern "C" int icon_debug_walk_stats(const icon_mesh_t *mesh, int res, int z0, int z1, uint64_t out[6])
-{
-    ICON_ARG(mesh && out, "icon_debug_walk_stats: null argument");
-    unsigned long long h[6];
-    int rc = walk_stats(mesh, res, z0, z1, h);
-    if (rc) return rc;
-    for (int k = 0; k < 6; ++k) out[k] = h[k];
     return ICON_OK;
 }
 
@@ -1569,26 +1515,19 @@ extern "C" int icon_work_status(icon_work_t *work)
     return work_check_err(work);
 }
 
-// test / A-B switches by name (process-wide): "pair_box" 0 / 1 - the packet walk culls leaf pairs by their oriented boxes (meshes
-// and mesh batches created AFTERWARDS; 0: they run the walk without the cull); "node_box" 0 / 1 - the packet walk tests the children of the bottom
-// inner nodes by oriented boxes (likewise: meshes created afterwards; 0: AABBs only); "box_clamp" 0 / 1 - the lattice launches of k_nearest evaluate the
-// oriented boxes in half units with the excess clamped (mesh_rules.h: pair_box_bound_half; likewise: meshes created afterwards); "lattice_fast" 0 / 1; "share_waves" wavefronts per shared walk (-1 = by launch size;
-// 4: the adaptive schedule's searches only); "share_ring" forced ring size of the shared walks (0 = 64),
-// "share_lose_push" the ticket of the push that is announced but never stored (0 = none), "share_spin_log2" wait bound 2^n polls
-// (0 = 2^18).  Production leaves all of them alone.
+// the switches of the table above by name, and the two that live with their own code
 extern "C" int icon_debug_set_option(const char *key, int value)
 {
     ICON_ARG(key != nullptr, "icon_debug_set_option: key is null");
     const std::string k(key);
-    if (k == "lattice_fast") g_lattice_fast = value ? 1 : 0;
-    else if (k == "share_waves") { ICON_ARG(value == -1 || value == 1 || value == 4 || value == 8 || value == 16, "share_waves: -1 (by launch size), 1, 4, 8 or 16"); g_share_waves = value; }
-    else if (k == "pair_box") g_pair_box = value ? 1 : 0;
-    else if (k == "node_box") g_node_box = value ? 1 : 0;
-    else if (k == "box_clamp") g_box_clamp = value ? 1 : 0;
-    else if (k == "share_ring") { ICON_ARG(value == 0 || (value >= 2 && value <= 64 && (value & (value - 1)) == 0), "share_ring: 0 or a power of two in 2..64"); g_share_ring = value; }
-    else if (k == "share_lose_push") { ICON_ARG(value >= 0, "share_lose_push: a ticket >= 1, or 0"); g_share_lose = value; }
-    else if (k == "share_spin_log2") { ICON_ARG(value >= 0 && value < 30, "share_spin_log2: 0..29"); g_share_spin_log2 = value; }
-    else if (k == "qc_lanes") { ICON_ARG(value == 0 || value == 64, "qc_lanes: 0 (default) or 64"); g_qc_lanes = value; }
+    for (int o = 0; o < kOptCount; ++o) {
+        const Option &e = kOptions[o];
+        if (!e.key || k != e.key) continue;
+        ICON_ARG(!e.ok || e.ok(value), k + ": " + e.accepts);
+        set_option((Opt)o, value);
+        return ICON_OK;
+    }
+    if (k == "qc_lanes") { ICON_ARG(value == 0 || value == 64, "qc_lanes: 0 (default) or 64"); g_qc_lanes = value; }
     else if (k == "rn_lanes") { ICON_ARG(value == 0 || value == 1 || value == 8, "rn_lanes: 0 (default), 1 or 8"); g_rn_lanes = value; }
     else return fail(ICON_ERR_ARG, "icon_debug_set_option: unknown key " + k);
     return ICON_OK;
@@ -1596,7 +1535,7 @@ extern "C" int icon_debug_set_option(const char *key, int value)
 
 extern "C" int icon_debug_set_shell_skip(int on)
 {
-    g_shell_skip = on ? 1 : 0;
+    set_option(kOptShellSkip, on);
     return ICON_OK;
 }
 

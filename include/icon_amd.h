@@ -414,7 +414,8 @@ int icon_work_set_tie_rule(icon_work_t *work, int rule, int ulps);
 /* Diagnostics (synchronises): BVH work of the lattice traversal over planes [z0,z1):
  * out[0] = wavefronts (point blocks: 4^3 on fine lattices, 2^3 on coarse ones), out[1] = BVH nodes visited, out[2] = triangles
  * tested, both summed over wavefronts (every visit serves all lanes of the wavefront), out[3] = nodes + triangles of the
- * LONGEST walk (what a latency-bound launch - fewer packets than wave slots - waits for). */
+ * LONGEST walk (what a latency-bound launch - fewer packets than wave slots - waits for).  The walk on pair_box_bound ("box_clamp"
+ * off), whatever the mesh was created with; the three calls below read the counters of one kernel. */
 int icon_debug_traversal_stats(const icon_mesh_t *mesh, int res, int z0, int z1, uint64_t out[4]);
 /* the lattice walk's leaf work: out = [packets, nodes visited, leaf pairs offered to the distance test, leaf pairs tested] */
 int icon_debug_pair_stats(const icon_mesh_t *mesh, int res, int z0, int z1, uint64_t out[4]);

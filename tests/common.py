@@ -184,3 +184,10 @@ def volume_encoder_replica(num_in=3, num_out=7, num_stacks=2):
             return outs if intermediate_output else [outs[-1]]
 
     return VolumeEncoder()
+
+
+def set_option(key, value):
+    """icon_debug_set_option: a process-wide test / A-B switch of the library by name"""
+    import ctypes as C
+    from icon_amd import _lib
+    _lib.check(_lib.lib().icon_debug_set_option(key.encode(), C.c_int(int(value))), "icon_debug_set_option")

@@ -1,6 +1,6 @@
 """Meshes and helpers shared by tests/test_node_box.py (host) and tests/test_gpu_node_box.py: the meshes of tests/pair_box_cases.py plus
 small strips of 1, 2, 16, 17 and 33 triangles (the root is a leaf; the root is an oriented parent; one child just over the
-threshold), the model of the walk (tools/node_box_model.py) and the host entries of the rule."""
+threshold; `strip<n>` names a strip of any other length), the model of the walk (tools/node_box_model.py) and the host entries of the rule."""
 import ctypes as C
 import importlib.util
 import os
@@ -33,9 +33,10 @@ model = _load_model()
 @lru_cache(maxsize=None)
 def mesh(name):
     """(verts f32 [V,3], faces i64 [F,3], cmap f32 [V,3], vis f32 [V])"""
-    if name not in STRIPS:
+    if not name.startswith("strip"):
         return _pair_mesh(name)
-    n = STRIPS[name]                               # a triangle strip wound round a helix: slanted, curved, no two triangles coplanar
+    n = STRIPS[name] if name in STRIPS else int(name[5:])      # ("strip<n>": any length; STRIPS: the ones every mesh test runs)
+    # a triangle strip wound round a helix: slanted, curved, no two triangles coplanar
     j = np.arange(n + 2)
     ang = 0.35 * j
     r = np.where(j % 2 == 0, 0.45, 0.55)

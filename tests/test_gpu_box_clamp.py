@@ -6,13 +6,12 @@ so an excess beyond 2 - the only place the two differ - is met only while the th
 share_waves = 1 makes the small lattices run k_nearest<lattice> itself (one wavefront per packet), the kernel of the 257^3 call
 and the one the option selects; the default launch sizes are run as well.  The option is read when a mesh is created: every case
 builds its meshes under the setting it tests."""
-import ctypes as C
 
 import numpy as np
 import pytest
 import torch
 
-from common import assets, golden
+from common import assets, golden, set_option
 from node_box_cases import mesh
 
 pytestmark = pytest.mark.gpu
@@ -23,11 +22,6 @@ OCC_TOL = 1e-4                                           # tests/test_gpu_parity
 
 def T(x):
     return torch.from_numpy(np.ascontiguousarray(x)).to(DEV)
-
-
-def set_option(key, value):
-    from icon_amd import _lib
-    _lib.check(_lib.lib().icon_debug_set_option(key.encode(), C.c_int(value)), "icon_debug_set_option")
 
 
 @pytest.fixture(autouse=True)

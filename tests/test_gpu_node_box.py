@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 import torch
 
-from common import assets
+from common import assets, set_option
 from node_box_cases import mesh
 
 pytestmark = pytest.mark.gpu
@@ -20,11 +20,6 @@ DEV = torch.device("cuda:0")
 
 def T(x):
     return torch.from_numpy(np.ascontiguousarray(x)).to(DEV)
-
-
-def set_option(key, value):
-    from icon_amd import _lib
-    _lib.check(_lib.lib().icon_debug_set_option(key.encode(), C.c_int(value)), "icon_debug_set_option")
 
 
 @pytest.fixture(autouse=True)
@@ -156,3 +151,24 @@ def test_counters_fewer_visits_no_more_tests():
     assert st[0]["oriented_nodes"] == 0 and 0 < st[1]["oriented_nodes"] < st[1]["nodes"]
     assert st[1]["nodes"] + st[1]["leaves"] < st[0]["nodes"] + st[0]["leaves"]
     assert st[1]["pairs_tested"] <= 1.1 * st[0]["pairs_tested"]
+
+
+def test_the_three_stats_calls_agree():
+    """traversal_stats, pair_stats and walk_stats are three launches of one kernel (traversal_stats on pair_box_bound, the other two on
+    the walk the mesh runs; the walk is deterministic): the words they share agree exactly - on the
+    body (33^3 and 65^3, planes 0..8) and where the root is a leaf (4 triangles) or the only inner node (5 triangles)"""
+    for name, res in (("body", 33), ("body", 65), ("strip4", 33), ("strip5", 33)):
+        m = mesh_handle(name, 1)
+        ts, ps, ws = m.traversal_stats(res, 0, 8), m.pair_stats(res, 0, 8), m.walk_stats(res, 0, 8)
+        m.close()
+        print(f"\n{name} {res}: {ts}\n  {ps}\n  {ws}")
+        assert ts["waves"] == ws["packets"] > 0 and ts["nodes"] == ws["nodes"]
+        assert ws["leaves"] <= ts["tris"] <= 4 * ws["leaves"] and ws["leaves"] > 0
+        assert [ps[k] for k in ("packets", "nodes", "pairs_offered", "pairs_tested")] == [ws[k] for k in ("packets", "nodes", "pairs_offered", "pairs_tested")]
+        # the longest walk is one packet's nodes + triangles: no shorter than the mean, no longer than the sum
+        total = ts["nodes"] + ts["tris"]
+        assert total <= ts["longest_walk"] * ts["waves"] and ts["longest_walk"] <= total
+        if name == "strip4":                                 # the root is a leaf: no inner node, and every packet visits that leaf
+            assert ws["nodes"] == 0 and ws["leaves"] == ws["packets"] and ts["tris"] == 4 * ws["packets"] and ts["longest_walk"] == 4
+        if name == "strip5":                                 # the root is the only inner node: every packet visits it, and only it
+            assert ws["nodes"] == ws["packets"] and ws["leaves"] <= 2 * ws["packets"]

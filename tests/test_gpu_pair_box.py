@@ -3,13 +3,12 @@ result is bit for bit what the walk without it gives - volumes, point queries (e
 still win), the coarse-to-fine schedule - while the walk visits the same nodes and tests strictly fewer leaf pairs.
 share_waves = 1 makes the small lattices run k_nearest<lattice> itself (one wavefront per packet), the kernel of the 257^3 call.
 The option is read when a mesh is created: every case builds its meshes under the setting it tests."""
-import ctypes as C
 
 import numpy as np
 import pytest
 import torch
 
-from common import assets
+from common import assets, set_option
 from pair_box_cases import mesh, model
 
 pytestmark = pytest.mark.gpu
@@ -19,11 +18,6 @@ DEV = torch.device("cuda:0")
 
 def T(x):
     return torch.from_numpy(np.ascontiguousarray(x)).to(DEV)
-
-
-def set_option(key, value):
-    from icon_amd import _lib
-    _lib.check(_lib.lib().icon_debug_set_option(key.encode(), C.c_int(value)), "icon_debug_set_option")
 
 
 @pytest.fixture(autouse=True)

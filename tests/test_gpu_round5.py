@@ -1,22 +1,17 @@
 """GPU tests of round 5: the per-call tile record of the 257^3-class search, the bounded hand-over of the shared walks
 (torture, fault injection, error reporting through the C ABI), the mcube_res=512 path end to end (reference schedule
 [33,65,129,257,513] -> device marching cubes -> clean_mesh), lazy mesh validation."""
-import ctypes as C
 from types import SimpleNamespace
 
 import numpy as np
 import pytest
 import torch
 
-from common import assets, golden
+from common import assets, golden, set_option
 from icon_amd import _lib, synth
 from test_gpu_parity import T, dev, make_engine
 
 pytestmark = pytest.mark.gpu
-
-
-def set_option(key, value):
-    _lib.check(_lib.lib().icon_debug_set_option(key.encode(), C.c_int(int(value))), "icon_debug_set_option")
 
 
 @pytest.fixture()

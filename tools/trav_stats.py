@@ -4,6 +4,7 @@ from icon_amd import synth
 from icon_amd.engine import MeshHandle
 a = synth.make_assets("body"); T=lambda x: torch.from_numpy(x).cuda()
 mesh = MeshHandle(T(a.smpl_verts), T(a.smpl_faces), T(a.smpl_cmap), T(a.smpl_vis))
+# three views of one kernel's counters (k_walk_stats): traversal_stats on pair_box_bound, the other two on the walk the mesh runs
 for res in (33, 65, 129, 257):
     print(res, mesh.traversal_stats(res))
     ps = mesh.pair_stats(res)     # the oriented-box cull of the leaf pairs (ICON_AMD_PAIR_BOX=0: off); tools/pair_box_model.py predicts it
