@@ -42,6 +42,7 @@ SYMBOLS = [
     "icon_render_normal_backward_bytes", "icon_render_normal_backward",
     "icon_local_affine_bytes", "icon_local_affine_forward", "icon_local_affine_backward",
     "icon_mesh_priors_bytes", "icon_mesh_priors_forward", "icon_mesh_priors_backward",
+    "icon_smpl_bytes", "icon_smpl_forward", "icon_smpl_backward",
 ]
 
 _lib = None

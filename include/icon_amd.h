@@ -636,6 +636,44 @@ int icon_mesh_priors_backward(const float *d_verts, int64_t V, const void *d_edg
                               float target_length, int terms, const float *d_grad_edge, const float *d_grad_nc,
                               const float *d_grad_laplacian, float *d_grad_verts, void *d_scratch, int64_t scratch_bytes, void *stream);
 
+/* ---- SMPL linear blend skinning, forwards and backwards ---------------------------------------------------
+ * lbs(betas, pose, ..., pose2rot=False) of lib/smplx/lbs.py:152-252 - what dataset.smpl_model computes per step of the body-fit
+ * loop (apps/infer.py:163-273).  The rule is DESIGN.md 4.17, pinned to the reference's own lbs(); every expression is evaluated
+ * in float64 from the float32 inputs and rounded once.  The rotation matrices need not be orthonormal: plain linear algebra.
+ * Per subject b:  J = J_template + J_shapedirs betas;  rel_0 = J_0, rel_j = J_j - J_parent(j);  G_0 = [R_0 | rel_0],
+ * G_j = G_parent(j) o [R_j | rel_j];  joints_j = G_j^t;  A_j = [G_j^R | G_j^t - G_j^R J_j];
+ * v_posed = v_template + shapedirs betas + sum_p f_p posedirs[p], f = vec(R_j - I) over j >= 1 (joint-major, then row-major);
+ * T_v = sum_k skin_w[v,k] A_skin_idx[v,k];  verts_v = T_v^R v_posed + T_v^t.
+ * Tables (icon_amd/smpl.py: SmplModel builds them once per model; all device pointers, float32 / int32):
+ *   v_template [3][V], shapedirs [NB][3][V], posedirs [P][3][V] - COMPONENT-MAJOR, vertex last: lane v of a wave reads the
+ *   float next to lane v - 1's (the module's buffers are [V,3], [V,3,NB] and [P,3V]);
+ *   J_template [J][3] = J_regressor v_template and J_shapedirs [J][3][NB] = J_regressor shapedirs, formed in float64 and rounded
+ *   once (the joints are linear in betas: no call reduces over vertices for them);  parents [J], parents[j] < j for j >= 1;
+ *   skin_idx / skin_w [V][K]: the non-zero weights of vertex v, joints ascending, rows padded with (0, 0.0).
+ * A joint index outside 0..J-1 is skipped and a parent outside 0..j-1 is read as 0, so no entry is used as an address unchecked.
+ * Limits: 1 <= J <= 64, 0 <= NB <= 512, B V < 2^31 (ICON_ERR_UNSUPPORTED); 1 <= K <= J, P == 9 (J - 1) (ICON_ERR_ARG).
+ * icon_smpl_forward: d_betas [B,NB], d_rot_mats [B,J,3,3] -> d_verts [B,V,3], d_joints [B,J,3], and d_A [B,J,3,4], which the
+ * caller keeps for the backward call of the same inputs.  Two launches.
+ * icon_smpl_backward: d_grad_verts [B,V,3] / d_grad_joints [B,J,3], either may be NULL (a zero that is not read) -> d_grad_betas
+ * [B,NB], d_grad_rot_mats [B,J,3,3], every entry written.  v_posed and T_v are recomputed; the 12 J + P + NB sums over vertices
+ * go through per-workgroup partials in d_scratch (icon_smpl_bytes, 256-byte aligned, the caller's) and are added in a fixed
+ * order by the launch that walks the chain backwards.  Two launches, one when d_grad_verts is NULL.
+ * Enqueued on `stream`: no allocation, no synchronisation, nothing read back; no floating-point atomics: equal bytes from run
+ * to run. */
+typedef struct icon_smpl_tables {
+    const float *v_template, *shapedirs, *posedirs, *J_template, *J_shapedirs;
+    const int32_t *parents, *skin_idx;
+    const float *skin_w;
+    int64_t V;
+    int32_t J, NB, K, P;
+} icon_smpl_tables;
+int icon_smpl_bytes(int64_t B, int64_t V, int J, int NB, int K, int64_t *bytes);
+int icon_smpl_forward(const icon_smpl_tables *tables, const float *d_betas, const float *d_rot_mats, int64_t B,
+                      float *d_verts, float *d_joints, float *d_A, void *stream);
+int icon_smpl_backward(const icon_smpl_tables *tables, const float *d_betas, const float *d_rot_mats, int64_t B,
+                       const float *d_A, const float *d_grad_verts, const float *d_grad_joints,
+                       float *d_grad_betas, float *d_grad_rot_mats, void *d_scratch, int64_t scratch_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
