@@ -2,7 +2,7 @@
 """End-to-end on the synthetic subject: what apps/ICON.py:test_single does after netG.filter() (lines 729-761) -
 reconEngine -> export_mesh -> clean_mesh -> vertices into the [-1,1] cube - through the HIP path, with timings.
 
-    python examples/dense_recon.py [--res 257] [--adaptive] [--color] [--normal-maps] [--out body.obj]
+    python examples/dense_recon.py [--res 257] [--adaptive] [--color] [--normal-maps] [--turntable DIR] [--out body.obj]
 
 Needs an MI355X (there is no CPU path).  The inputs stand in for what the reference computes upstream of the hot path:
 `features` = HGPIFuNet.filter() output, the SMPL tensors = TestDataset.compute_vis_cmap(), the regressor = netG.if_regressor.
@@ -24,6 +24,8 @@ def main():
     ap.add_argument("--color", action="store_true", help="colour the vertices from a synthetic image (query_color, apps/infer.py:531); OBJ lines become v x y z r g b")
     ap.add_argument("--normal-maps", action="store_true", help="render the cleaned mesh from the four cameras of lib/common/render.py (icon_amd.render) "
                     "and write the normal maps as <out stem>_normal_<cam>.ppm")
+    ap.add_argument("--turntable", metavar="DIR", default=None, help="render the cleaned mesh from 360 cameras around it (the frames of the "
+                    "reference's turntable video; icon_amd.render) and write every 30th frame as DIR/turntable_<angle>.png")
     args = ap.parse_args()
     import torch
     from icon_amd import synth
@@ -69,7 +71,6 @@ def main():
           f"clean_mesh {1e3 * (t3 - t2):.2f} ms{color_ms} -> {verts.shape[0]} vertices, {faces.shape[0]} faces, "
           f"bbox {verts.min(0).values.tolist()} .. {verts.max(0).values.tolist()}")
     if args.normal_maps:
-        import os
         from icon_amd.render import Render
         render = Render(size=512, device=dev)
         render.load_meshes(verts, faces)
@@ -84,6 +85,20 @@ def main():
             with open(f"{stem}_normal_{cam}.ppm", "wb") as fh:
                 fh.write(b"P6\n512 512\n255\n" + rgb.tobytes())
         print(f"wrote {stem}_normal_0.ppm .. {stem}_normal_3.ppm")
+    if args.turntable:
+        from PIL import Image
+        from icon_amd.render import Render
+        render = Render(size=512, device=dev)
+        render.load_meshes(verts, faces)
+        for _ in render.get_rendered_frames([]):                                # warm-up: the call's scratch
+            pass
+        t6 = sync()
+        chunks = list(render.get_rendered_frames([]))                           # 12 uint8 [30,512,512,3] tensors on the device
+        print(f"turntable: 360 frames of 512^2 in {1e3 * (sync() - t6):.2f} ms, left on the device")
+        os.makedirs(args.turntable, exist_ok=True)
+        for k, frames in enumerate(chunks):                                     # the reference hands the frame to the writer as it is
+            Image.fromarray(frames[0].cpu().numpy()).save(os.path.join(args.turntable, f"turntable_{30 * k:03d}.png"))
+        print(f"wrote {args.turntable}/turntable_000.png .. turntable_330.png")
     if args.out:
         v, f = verts.cpu().numpy(), faces.cpu().numpy() + 1
         with open(args.out, "w") as fh:

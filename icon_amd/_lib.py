@@ -40,6 +40,7 @@ SYMBOLS = [
     "icon_render_bytes", "icon_render_normal",
     "icon_silhouette_bytes", "icon_silhouette_forward", "icon_silhouette_backward",
     "icon_render_normal_backward_bytes", "icon_render_normal_backward",
+    "icon_render_turntable_bytes", "icon_render_turntable",
     "icon_local_affine_bytes", "icon_local_affine_forward", "icon_local_affine_backward",
     "icon_mesh_priors_bytes", "icon_mesh_priors_forward", "icon_mesh_priors_backward",
     "icon_smpl_bytes", "icon_smpl_forward", "icon_smpl_backward",

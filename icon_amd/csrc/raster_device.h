@@ -6,6 +6,7 @@
 //     cam 2 (eye -z): X = +x, D = 100 + z      cam 3 (eye -x): X = -z, D = 100 + x         Y = y
 //   pixel (row r, column c) has its centre at X = -1 + (2 (S-1-c) + 1) / S, Y = -1 + (2 (S-1-r) + 1) / S: the kernels count pixels in
 //   MIRRORED indices i = S-1-c, j = S-1-r.
+//   turntable.hip (the video's camera at any azimuth) projects with rs_project_turn and shares everything else.
 //   A face is drawn when |area| > 1e-8; at a pixel centre p inside its bounding box grown by sqrt(blur) its barycentrics are
 //   w_k = ef_k / (area + 1e-8), clamped to [0, 1] and divided by max(sum, 1e-5); its depth is (b0 D0 + b1 D1) + b2 D2.  The blur
 //   radius of the normal maps and the silhouette's differ: every function that needs one takes it as an argument.
@@ -72,6 +73,17 @@ __device__ __forceinline__ void rs_project(const RsCtx &c, int cam, const int64_
         const float *p = c.verts + 3 * id[k];
         const float xa = side ? p[2] : p[0], za = side ? p[0] : p[2];
         X[k] = neg ? -xa : xa; Y[k] = p[1]; D[k] = front ? 100.0f - za : 100.0f + za;
+    }
+}
+// ... as the turntable camera of azimuth a sees them (turntable.hip): eye (100 cos a, 0, 100 sin a), (cs, sn) the
+// float32 pair of a.  Each product is rounded, then subtracted, in this order; at (1,0) / (0,1) / (-1,0) / (0,-1) it gives the
+// X and D of cam 1 / 0 / 3 / 2 above
+__device__ __forceinline__ void rs_project_turn(const RsCtx &c, float cs, float sn, const int64_t id[3], float X[3], float Y[3], float D[3])
+{
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float *p = c.verts + 3 * id[k];
+        X[k] = p[2] * cs - p[0] * sn; Y[k] = p[1]; D[k] = (100.0f - p[0] * cs) - p[2] * sn;
     }
 }
 // ... and a gradient (d/dX, d/dY) taken back onto the world's axes (X = -x, +z, +x, -z for cam 0..3): the addends of incidence key
@@ -151,6 +163,56 @@ __device__ __forceinline__ size_t rs_at(const RsCtx &c, int cam, int i, int j)
     return (size_t)row * c.S + cs;
 }
 
+// ---- the normal maps' own part of the rule, shared by render_normal.hip's four cameras and turntable.hip's any ----
+struct RsNormalFace {
+    float X[3], Y[3], D[3], den;     // the projected corners (the caller's rs_project / rs_project_turn); den: area + eps
+    RsBounds bb;                     // the bounding box grown by kRsNormalBlurR
+    RsBox box;
+    int64_t id[3];
+};
+// after id, X, Y and D are filled.  false: nothing to rasterise (zero area, box off the image)
+__device__ __forceinline__ bool rs_normal_setup(RsNormalFace &r, int S)
+{
+    const float area = rs_area(r.X, r.Y);
+    if (!rs_drawn(area)) return false;
+    r.den = area + kRsEps;
+    r.bb = rs_bounds(r.X, r.Y, kRsNormalBlurR);
+    r.box = rs_box(r.bb, S);
+    return !r.box.empty();
+}
+// the per-pixel rule: is the face a candidate at the pixel centre (px, py); its clamped barycentrics and depth
+__device__ __forceinline__ bool rs_normal_eval(const RsNormalFace &r, float px, float py, RsBary &q, float &pz)
+{
+    if (!(px >= r.bb.xlo && px <= r.bb.xhi && py >= r.bb.ylo && py <= r.bb.yhi)) return false;
+    float w[3];
+    rs_weights(r.X, r.Y, r.den, px, py, w);
+    if (!rs_inside(w)) {
+        const float d01 = rs_seg(px, py, r.X[0], r.Y[0], r.X[1], r.Y[1]).d2;
+        const float d02 = rs_seg(px, py, r.X[0], r.Y[0], r.X[2], r.Y[2]).d2;
+        const float d12 = rs_seg(px, py, r.X[1], r.Y[1], r.X[2], r.Y[2]).d2;
+        if (!(rs_min(rs_min(d01, d02), d12) < kRsNormalBlur)) return false;
+    }
+    q = rs_bary(w);
+    pz = rs_depth(q, r.D);
+    return !(pz < 0.0f);
+}
+// mirrored pixel (i, j), both in [0, S), of face f into a view's [S][S] z-buffer plane (image orientation).  The key: (depth bits,
+// face id), the smallest wins
+__device__ __forceinline__ void rs_normal_pixel(unsigned long long *zb, int S, const RsNormalFace &r, int64_t f, int i, int j)
+{
+    RsBary q;
+    float pz;
+    if (!rs_normal_eval(r, rs_centre(i, S), rs_centre(j, S), q, pz)) return;
+    const unsigned long long key = ((unsigned long long)__float_as_uint(pz) << 32) | (unsigned long long)(uint32_t)f;
+    atomicMin(&zb[(size_t)(S - 1 - j) * S + (size_t)(S - 1 - i)], key);
+}
+// the winner's blend of its corners' t = (n + 1) * 0.5 in channel ch: the image holds (t - 0.5) * 2, a video frame (uint8) (t * 255)
+__device__ __forceinline__ float rs_normal_texel(const RsBary &q, const float *n0, const float *n1, const float *n2, int ch)
+{
+    const float t0 = (n0[ch] + 1.0f) * 0.5f, t1 = (n1[ch] + 1.0f) * 0.5f, t2 = (n2[ch] + 1.0f) * 0.5f;
+    return (q.b[0] * t0 + q.b[1] * t1) + q.b[2] * t2;
+}
+
 // G lanes sweep a face's box: lane `sub` takes pixels sub, sub + G, ... in row order and calls fn(i, j)
 template <int G, class Fn>
 __device__ __forceinline__ void rs_sweep(const RsBox &q, int sub, Fn fn)
@@ -189,6 +251,21 @@ __device__ __forceinline__ bool rs_deferred(const RsCtx &c, const int *big, int 
     return view >= 0 && view < c.n_views && f < c.F;
 }
 
+// a call of more views than the two bits above name (turntable.hip) keeps ONE LIST PER VIEW of the chunk it is rasterising: the view
+// is the list's index, an entry the face alone (below 2^29); list `lv` holds at most F entries at big[lv F ..], its length in n_big[lv]
+__device__ __forceinline__ void rs_defer_view(int *n_big, int *big, int64_t F, int lv, int64_t f)
+{
+    const int at = atomicAdd(&n_big[lv], 1);
+    if (at >= 0 && (int64_t)at < F) big[(size_t)lv * F + at] = (int)f;
+}
+__device__ __forceinline__ int rs_deferred_view_count(const int *n_big, int64_t F, int lv) { return (int)min((int64_t)max(n_big[lv], 0), F); }
+// entry e of list lv; false: it names no face of this call
+__device__ __forceinline__ bool rs_deferred_view(const int *big, int64_t F, int lv, int e, int64_t &f)
+{
+    f = big[(size_t)lv * F + e];
+    return f >= 0 && f < F;
+}
+
 // the call's clears: n_zero words of the scratch to 0, n_zb z-buffer words (0 where a call has none) to ~0 - a kernel like the
 // others, so that a captured call consists of kernel nodes only
 __global__ __launch_bounds__(256) void k_rs_clear(uint32_t *zero, size_t n_zero, unsigned long long *zb, size_t n_zb)
@@ -216,12 +293,12 @@ int rs_lanes(const RsCtx &c)
     return g_rn_lanes == 1 ? 1 : (g_rn_lanes == 8 ? 8 : (8 * c.F > (int64_t)c.S * c.S ? 1 : kRsLanes));
 }
 
-// the checks of an entry `name`: the sizes (all a *_bytes entry needs) ...
-int rs_check_sizes(const std::string &name, int64_t V, int64_t F, int size, int n_views)
+// the checks of an entry `name`: the sizes (all a *_bytes entry needs; max_views: four cameras, or the turntable's frames) ...
+int rs_check_sizes(const std::string &name, int64_t V, int64_t F, int size, int n_views, int max_views = 4)
 {
     ICON_ARG(V > 0 && F > 0 && V < (1ll << 31) && F < (1ll << 29), name + ": 0 < V < 2^31, 0 < F < 2^29");
     ICON_ARG(size >= 8 && size <= 2048, name + ": size must be 8..2048");
-    ICON_ARG(n_views >= 1 && n_views <= 4, name + ": n_views must be 1..4");
+    ICON_ARG(n_views >= 1 && n_views <= max_views, name + ": n_views must be 1.." + std::to_string(max_views));
     return ICON_OK;
 }
 // ... and the call's: the cameras, the scratch against the `total` its bytes_name entry gives.  Fills the rule's part of the context

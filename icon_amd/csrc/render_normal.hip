@@ -6,8 +6,8 @@
 // blur_radius=log(1/1e-4)*1e-7, faces_per_pixel=30) under FoVOrthographicCameras(+-100, scale 100) restated in float32, with
 // the softmax blend (gamma = 1e-8) replaced by its limit: the candidate of smallest (depth bits, face id) wins.
 //   The cameras, the pixel centres, the face test |area| > 1e-8, the barycentrics w_k = ef_k / (area + 1e-8), their clamp and the
-//   depth (b0 D0 + b1 D1) + b2 D2 are raster_device.h's, shared with silhouette.hip and render_normal_bwd.hip.  This file's own:
-//   a face is a candidate at a pixel centre p inside its bounding box grown by sqrt(blur) when its three barycentrics are all > 0 or
+//   depth (b0 D0 + b1 D1) + b2 D2 are raster_device.h's, shared with silhouette.hip and render_normal_bwd.hip.  The normal maps'
+//   own (rs_normal_*, there too since turntable.hip renders the video's frames by it): a face is a candidate at a pixel centre p inside its bounding box grown by sqrt(blur) when its three barycentrics are all > 0 or
 //   the squared distance of p to its nearest edge is < blur, and its depth is not negative.
 //   Colour of the winner: ((b0 t0 + b1 t1) + b2 t2 - 0.5) * 2 per channel, t = (n + 1) * 0.5, n the S1 vertex normal.
 //   Background: colour 0, depth -1, face -1.
@@ -39,52 +39,19 @@ struct RnCtx : RsCtx {               // vis null: every vertex gets a normal
     unsigned long long *zb;          // [n_views][S][S], image orientation
 };
 
-struct RnRast {
-    float X[3], Y[3], D[3], den;     // den: area + eps
-    RsBounds bb;                     // the bounding box grown by kRsNormalBlurR
-    RsBox box;
-    int64_t id[3];
-};
-
 // face f as camera `cam` sees it.  false: nothing to rasterise (bad index, zero area, box off the image)
 template <class IT>
-__device__ __forceinline__ bool rn_setup(const RnCtx &c, int cam, int64_t f, RnRast &r)
+__device__ __forceinline__ bool rn_setup(const RnCtx &c, int cam, int64_t f, RsNormalFace &r)
 {
     if (!s1_face<IT>(c, f, r.id)) return false;
     rs_project(c, cam, r.id, r.X, r.Y, r.D);
-    const float area = rs_area(r.X, r.Y);
-    if (!rs_drawn(area)) return false;
-    r.den = area + kRsEps;
-    r.bb = rs_bounds(r.X, r.Y, kRsNormalBlurR);
-    r.box = rs_box(r.bb, c.S);
-    return !r.box.empty();
+    return rs_normal_setup(r, c.S);
 }
 
-// the per-pixel rule: is the face a candidate at the pixel centre (px, py); its clamped barycentrics and depth
-__device__ __forceinline__ bool rn_eval(const RnRast &r, float px, float py, RsBary &q, float &pz)
+// mirrored pixel (i, j) of face f in view `view`: both in [0, S)
+__device__ __forceinline__ void rn_pixel(const RnCtx &c, const RsNormalFace &r, int view, int64_t f, int i, int j)
 {
-    if (!(px >= r.bb.xlo && px <= r.bb.xhi && py >= r.bb.ylo && py <= r.bb.yhi)) return false;
-    float w[3];
-    rs_weights(r.X, r.Y, r.den, px, py, w);
-    if (!rs_inside(w)) {
-        const float d01 = rs_seg(px, py, r.X[0], r.Y[0], r.X[1], r.Y[1]).d2;
-        const float d02 = rs_seg(px, py, r.X[0], r.Y[0], r.X[2], r.Y[2]).d2;
-        const float d12 = rs_seg(px, py, r.X[1], r.Y[1], r.X[2], r.Y[2]).d2;
-        if (!(rs_min(rs_min(d01, d02), d12) < kRsNormalBlur)) return false;
-    }
-    q = rs_bary(w);
-    pz = rs_depth(q, r.D);
-    return !(pz < 0.0f);
-}
-
-// mirrored pixel (i, j) of face f in view `view`: both in [0, S).  The z-buffer key: (depth bits, face id), the smallest wins
-__device__ __forceinline__ void rn_pixel(const RnCtx &c, const RnRast &r, int view, int64_t f, int i, int j)
-{
-    RsBary q;
-    float pz;
-    if (!rn_eval(r, rs_centre(i, c.S), rs_centre(j, c.S), q, pz)) return;
-    const unsigned long long key = ((unsigned long long)__float_as_uint(pz) << 32) | (unsigned long long)(uint32_t)f;
-    atomicMin(&c.zb[((size_t)view * c.S + (size_t)(c.S - 1 - j)) * c.S + (size_t)(c.S - 1 - i)], key);
+    rs_normal_pixel(c.zb + (size_t)view * c.S * c.S, c.S, r, f, i, j);
 }
 
 // G lanes per face, 256 / G faces per workgroup; blockIdx.y: the view
@@ -95,7 +62,7 @@ __global__ __launch_bounds__(256) void k_rn_raster(RnCtx c)
     const int sub = threadIdx.x % G;
     const int view = blockIdx.y;
     if (f >= c.F) return;
-    RnRast r;
+    RsNormalFace r;
     if (!rn_setup<IT>(c, c.cam(view), f, r)) return;
     if (r.box.n() > kRsBigPerLane * G) {
         if (sub == 0) rs_defer(c, c.n_big, c.big, view, f);
@@ -112,7 +79,7 @@ __global__ __launch_bounds__(256) void k_rn_raster_big(RnCtx c)
     for (int e = blockIdx.x; e < nb; e += gridDim.x) {
         int view;
         int64_t f;
-        RnRast r;
+        RsNormalFace r;
         if (!rs_deferred(c, c.big, e, view, f) || !rn_setup<IT>(c, c.cam(view), f, r)) continue;
         rs_sweep_block(r.box, [&](int i, int j) { rn_pixel(c, r, view, f, i, j); });
     }
@@ -132,18 +99,16 @@ __global__ __launch_bounds__(256) void k_rn_resolve(RnCtx c)
     const unsigned long long key = c.zb[(size_t)view * npx + p];
     float rgb[3] = { 0.0f, 0.0f, 0.0f }, pz = -1.0f;
     int face = -1;
-    RnRast r;
+    RsNormalFace r;
     RsBary q;
-    // a face in the z-buffer passed rn_setup and rn_eval at this pixel: the same expressions give the same answer
+    // a face in the z-buffer passed rn_setup and rs_normal_eval at this pixel: the same expressions give the same answer
     if (key != ~0ull && (int64_t)(key & 0xffffffffull) < c.F && rn_setup<IT>(c, cam, (int64_t)(uint32_t)(key & 0xffffffffull), r) &&
-        rn_eval(r, rs_centre(i, c.S), rs_centre(j, c.S), q, pz)) {
+        rs_normal_eval(r, rs_centre(i, c.S), rs_centre(j, c.S), q, pz)) {
         face = (int)(uint32_t)(key & 0xffffffffull);
         const float *n0 = c.nrm + 3 * r.id[0], *n1 = c.nrm + 3 * r.id[1], *n2 = c.nrm + 3 * r.id[2];
 #pragma unroll
-        for (int ch = 0; ch < 3; ++ch) {
-            const float t0 = (n0[ch] + 1.0f) * 0.5f, t1 = (n1[ch] + 1.0f) * 0.5f, t2 = (n2[ch] + 1.0f) * 0.5f;
-            rgb[ch] = (((q.b[0] * t0 + q.b[1] * t1) + q.b[2] * t2) - 0.5f) * 2.0f;
-        }
+        for (int ch = 0; ch < 3; ++ch)
+            rgb[ch] = (rs_normal_texel(q, n0, n1, n2, ch) - 0.5f) * 2.0f;
     } else {
         pz = -1.0f;
     }

@@ -8,7 +8,12 @@ call, ``icon_render_normal`` (csrc/render_normal.hip; the rule is DESIGN.md 4.13
 ``torch.autograd.Function`` over ``icon_silhouette_forward`` / ``icon_silhouette_backward`` (csrc/silhouette.hip; DESIGN.md 4.14,
 parity unpinned like 4.13) - differentiable with respect to the vertices.  The normal maps are differentiable on request
 (``render_normal_device(differentiable=True)``, ``Render(normal_grad=True)``: ``icon_render_normal_backward``,
-csrc/render_normal_bwd.hip); depth maps and ``pix_to_face`` are not; video and point clouds are not covered.
+csrc/render_normal_bwd.hip); depth maps and ``pix_to_face`` are not.
+
+The turntable video (``Render.get_rendered_video``, apps/infer.py:547-563) is ``render_turntable_device``: ONE native call,
+``icon_render_turntable`` (csrc/turntable.hip; DESIGN.md 4.18, parity unpinned like 4.13), renders a mesh from a camera at every
+requested azimuth and writes the frames' bytes on the device; ``Render.get_rendered_frames`` lays the panels of every loaded
+mesh and the input images side by side.  Not differentiable.  Point clouds are not covered.
 """
 from __future__ import annotations
 
@@ -75,6 +80,22 @@ def _check_mesh(what: str, verts, faces, need_float: bool) -> torch.Tensor:
     if f.dtype not in (torch.int32, torch.int64):
         f = f.to(torch.int64)
     return f.contiguous()
+
+
+def turntable_cos_sin(angles) -> np.ndarray:
+    """azimuths in degrees (any finite floats: negative ones and those >= 360 included) -> float32 ``[n,2]``: the pairs
+    ``(cos, sin)`` of ``pi / 180 * angle`` evaluated in float64 and rounded - exactly ``(1,0)``, ``(0,1)``, ``(-1,0)``, ``(0,-1)``
+    at the whole multiples of 90, where the turntable camera is one of the four fixed ones.  The only place that
+    turns angles into what ``icon_render_turntable`` projects with; needs no device."""
+    a = np.asarray(list(angles) if not isinstance(angles, np.ndarray) else angles, dtype=np.float64).reshape(-1)
+    if not np.isfinite(a).all():
+        raise IconAmdError("render: turntable angles must be finite")
+    theta = np.pi / 180 * a
+    pairs = np.stack([np.cos(theta), np.sin(theta)], 1).astype(np.float32)
+    quarter = a / 90.0
+    whole = quarter == np.round(quarter)
+    pairs[whole] = np.array([(1, 0), (0, 1), (-1, 0), (0, -1)], np.float32)[np.mod(quarter[whole], 4).astype(np.int64)]
+    return pairs
 
 
 def _mesh_args(v, f, cams, size):
@@ -158,6 +179,71 @@ def render_normal_device(verts: torch.Tensor, faces: torch.Tensor, cam_ids: Sequ
     return out if len(out) > 1 else images
 
 
+def _tt_pairs(device: torch.device, pairs: np.ndarray) -> torch.Tensor:
+    """the pairs on the device, kept per (thread, device, stream) like the scratch: the video asks for the same chunks of angles
+    for every mesh, and a call repeated after a warm-up uploads nothing - so it can be captured into a graph"""
+    cache = getattr(_rn_tls, "pairs", None)
+    if cache is None or len(cache) > 64:
+        cache = _rn_tls.pairs = {}
+    idx = device.index if device.index is not None else torch.cuda.current_device()
+    key = (idx, torch.cuda.current_stream(idx).cuda_stream, pairs.tobytes())
+    if key not in cache:
+        cache[key] = torch.from_numpy(pairs).to(torch.device("cuda", idx))
+    return cache[key]
+
+
+def render_turntable_device(verts: torch.Tensor, faces: torch.Tensor, angles, size: int = 512, out: torch.Tensor = None, x0: int = 0,
+                            return_images: bool = False, return_depth: bool = False, return_faces: bool = False):
+    """``verts [V,3]`` (float), ``faces [F,3]`` (int32 or int64, read in place), both on one HIP device; ``angles``: 1..1024
+    azimuths in degrees (``turntable_cos_sin``) -> the frames of the turntable video, uint8 ``[n,size,size,3]`` there: frame k
+    is the normal map seen from ``(100 cos a_k, 0, 100 sin a_k)`` as bytes ``(t * 255)`` truncated, channels x, y, z, background
+    127 (the reference's ``(renderer(mesh)[0, :, :, :3] * 255.0).astype(np.uint8)``).  With ``out=`` - a
+    contiguous uint8 ``[n,size,W,3]`` canvas on the same device - the frames go into columns ``x0 .. x0 + size - 1`` of it, no
+    other byte of it is touched, and ``out`` is returned.  Then ``images [n,3,size,size]`` with ``return_images``, ``depth`` with
+    ``return_depth`` and ``pix_to_face`` with ``return_faces``, formatted as ``render_normal_device``'s; no view is mirrored.
+    ONE native call on the current stream, whatever n: the vertex normals are computed once, the views are rasterised in
+    chunks inside the call (the scratch, cached per (thread, device, stream) like ``render_normal_device``'s, does not grow
+    with n).  Nothing is allocated by it, nothing read back, the stream is not waited for; equal bytes from run to run.  Not
+    differentiable: it renders from a detached copy."""
+    from .engine import _stream
+    size = _check_size(size)
+    pairs = turntable_cos_sin(angles)
+    n = len(pairs)
+    if not 1 <= n <= 1024:
+        raise IconAmdError(f"render: a turntable call takes 1..1024 angles, got {n}")
+    if out is not None:
+        if not torch.is_tensor(out) or out.dtype != torch.uint8:
+            raise IconAmdError(f"render: out must be a uint8 tensor, got {getattr(out, 'dtype', type(out))}")
+        if out.dim() != 4 or out.shape[0] != n or out.shape[1] != size or out.shape[3] != 3 or not out.is_contiguous():
+            raise IconAmdError(f"render: out must be a contiguous [{n},{size},W,3] canvas, got {tuple(out.shape)}")
+        if int(x0) != x0 or not 0 <= int(x0) <= out.shape[2] - size:
+            raise IconAmdError(f"render: the panel x0 .. x0 + {size} - 1 must lie inside the canvas' width {out.shape[2]}, got x0 = {x0}")
+    elif x0 != 0:
+        raise IconAmdError(f"render: x0 needs a canvas (out=), got x0 = {x0}")
+    f = _check_mesh("render_turntable_device", verts, faces, need_float=False)
+    v = verts.detach().to(torch.float32).contiguous()
+    dev = v.device
+    if out is not None and out.device != dev:
+        raise IconAmdError("render_turntable_device: out must live on the device of the mesh")
+    L = _lib.lib()
+    with torch.cuda.device(dev):
+        nbytes = C.c_int64(0)
+        check(L.icon_render_turntable_bytes(C.c_int64(v.shape[0]), C.c_int64(f.shape[0]), C.c_int(size), C.c_int(n), C.byref(nbytes)),
+              "icon_render_turntable_bytes")
+        scratch = _rn_scratch(dev, nbytes.value)
+        cos_sin = _tt_pairs(dev, pairs)
+        frames = out if out is not None else torch.empty((n, size, size, 3), dtype=torch.uint8, device=dev)
+        images = torch.empty((n, 3, size, size), dtype=torch.float32, device=dev) if return_images else None
+        depth = torch.empty((n, size, size), dtype=torch.float32, device=dev) if return_depth else None
+        pix = torch.empty((n, size, size), dtype=torch.int32, device=dev) if return_faces else None
+        check(L.icon_render_turntable(_lib.ptr(v), C.c_int64(v.shape[0]), _lib.ptr(f), C.c_int64(f.shape[0]), C.c_int(1 if f.dtype == torch.int64 else 0),
+                                      _lib.ptr(cos_sin), C.c_int(n), C.c_int(size), _lib.ptr(frames), C.c_int64(frames.shape[2]), C.c_int64(int(x0)),
+                                      _lib.ptr(images), _lib.ptr(depth), _lib.ptr(pix), _lib.ptr(scratch), C.c_int64(scratch.numel()), _stream()),
+              "icon_render_turntable")
+    res = (frames,) + tuple(t for t in (images, depth, pix) if t is not None)
+    return res if len(res) > 1 else frames
+
+
 def _sil_scratch(v, f, cams, size):
     nbytes = C.c_int64(0)
     check(_lib.lib().icon_silhouette_bytes(C.c_int64(v.shape[0]), C.c_int64(f.shape[0]), C.c_int(size), C.c_int(len(cams)), C.byref(nbytes)),
@@ -215,13 +301,15 @@ def _mirror_cam2(cam_ids, cams) -> bool:
 
 
 class Render:
-    """Drop-in for ``lib.common.render.Render``'s normal maps, depth maps and soft silhouettes::
+    """Drop-in for ``lib.common.render.Render``'s normal maps, depth maps, soft silhouettes and turntable video::
 
         render = Render(size=512, device=torch.device("cuda:0"))
         render.load_meshes(verts, faces)
         T_normal_F, T_normal_B = render.get_rgb_image()          # [1,3,S,S] each, in [-1,1]
         depth_F, depth_B = render.get_depth_map(cam_ids=[0, 2])   # [S,S] each
         sil_F, sil_B = render.get_silhouette_image()             # [1,S,S] each, differentiable in verts
+        render.load_meshes([verts_pr, verts], [faces_pr, faces])
+        render.get_rendered_video([image, normal_F], "turntable.mp4")   # or: for frames in render.get_rendered_frames([...])
 
     The maps of one set of cameras are rendered once per ``load_meshes`` (one native call gives images and depths); the
     tensors handed out are views of that result.  ``Render(size, device, normal_grad=True)`` makes ``get_rgb_image``
@@ -330,3 +418,65 @@ class Render:
             k = cams.index(2)
             out[k] = torch.flip(out[k], dims=[2])
         return out
+
+    def get_rendered_frames(self, images, angles=range(360), chunk: int = 30):
+        """the frames of the turntable video, ``chunk`` at a time: a generator of uint8 DEVICE tensors ``[k,S,W,3]``.  Every frame is
+        ``[images resized ..., one panel per loaded mesh ...]`` side by side, in the reference's order, with
+        ``W = S * len(meshes) + new_w * len(images)``.  ``images``: host uint8 ``[H,W,3]`` arrays, all resized ONCE to the shape
+        the first one gives, as the reference resizes them per frame (``Image.fromarray(img).resize((new_w, S))``,
+        ``new_shape = around(S / H * (H, W))``, then the channels reversed), uploaded once and broadcast into each chunk's
+        canvas; every mesh's panel is one ``render_turntable_device`` call per chunk, written in place.  Nothing is copied to
+        the host."""
+        _need_device("Render")
+        if not self.meshes:
+            raise IconAmdError("Render: load_meshes has not been called")
+        angles = [float(a) for a in angles]
+        chunk = int(chunk)
+        if not 1 <= chunk <= 1024:
+            raise IconAmdError(f"render: chunk must be 1..1024 frames, got {chunk}")
+        S, dev = self.size, self._device()
+        panels = []
+        if len(images):
+            from PIL import Image
+            old = np.array(np.asarray(images[0]).shape[:2])
+            new_w = int(np.around((S / old[0]) * old)[1])
+            for img in images:
+                img = np.asarray(img)
+                if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3:
+                    raise IconAmdError(f"render: images must be uint8 [H,W,3] arrays, got {img.dtype} {img.shape}")
+                small = np.array(Image.fromarray(img).resize((new_w, S))).astype(np.uint8)[:, :, [2, 1, 0]]
+                panels.append(torch.from_numpy(np.ascontiguousarray(small)).to(dev))
+        left = sum(p.shape[1] for p in panels)
+        W = left + S * len(self.meshes)
+        for a0 in range(0, len(angles), chunk):
+            part = angles[a0:a0 + chunk]
+            canvas = torch.empty((len(part), S, W, 3), dtype=torch.uint8, device=dev)
+            x = 0
+            for p in panels:
+                canvas[:, :, x:x + p.shape[1]] = p
+                x += p.shape[1]
+            for k, (v, f) in enumerate(self.meshes):
+                render_turntable_device(v, f, part, S, out=canvas, x0=left + k * S)
+            yield canvas
+
+    def get_rendered_video(self, images, save_path):
+        """the reference's signature: 360 frames, one per whole degree, written to ``save_path`` with ``cv2.VideoWriter`` (``mp4v``,
+        30 fps, frame size ``(W, S)``) - each chunk of ``get_rendered_frames`` is copied to the host once.  Without ``cv2`` it raises;
+        ``get_rendered_frames`` gives the same frames to any other writer.  ``cv2`` is not installed where this was developed: the
+        tests put a recording stub in its place, the real writer is UNVERIFIED.  Unlike the reference, the call leaves the four
+        cameras of ``get_rgb_image`` alone."""
+        try:
+            import cv2
+        except ImportError as e:
+            raise IconAmdError("Render.get_rendered_video needs cv2 (opencv-python) for the video file; "
+                               "Render.get_rendered_frames yields the same frames on the device for any other writer") from e
+        video = None
+        try:
+            for frames in self.get_rendered_frames(images):
+                if video is None:
+                    video = cv2.VideoWriter(save_path, cv2.VideoWriter_fourcc(*"mp4v"), 30, (frames.shape[2], self.size))
+                for frame in frames.cpu().numpy():
+                    video.write(frame)
+        finally:
+            if video is not None:
+                video.release()

@@ -386,7 +386,9 @@ int icon_debug_set_shell_skip(int on);
  * "qc_lanes" (0 = 8, the default mapping): 64 makes icon_query_color's rasteriser sweep a face with one whole wavefront,
  * icon_visibility's mapping - tools/time_query_color.py times the two against each other; the result does not depend on it.
  * "rn_lanes" (0 = the default: chosen from F and the image size): 8 makes icon_render_normal's rasteriser sweep a face's pixel box with eight lanes, 1 with
- * one thread - tools/time_render.py times the two against each other; the result does not depend on it. */
+ * one thread - tools/time_render.py times the two against each other; the result does not depend on it.
+ * "tt_chunk" (0 = the default, 32): 1..32 makes icon_render_turntable take that many views per chunk - the tests cross chunk
+ * boundaries with a handful of views; the result does not depend on it, icon_render_turntable_bytes does. */
 int icon_debug_set_option(const char *key, int value);
 /* The searches of coarse lattices and of the adaptive schedule share one packet's BVH walk between the wavefronts of a
  * workgroup through an LDS queue (csrc/geom_device.h nearest_shared).  Every wait in that hand-over is bounded; a wave that
@@ -597,6 +599,33 @@ int icon_render_normal_backward(const float *d_verts, int64_t V, const void *d_f
                                 const int *cam_ids, int n_views, int size, const int32_t *d_pix_to_face,
                                 const float *d_grad_images, float *d_grad_verts,
                                 void *d_scratch, int64_t scratch_bytes, void *stream);
+
+/* ---- the frames of the turntable video ------------------------------------------------------------------
+ * replaces the renders of Render.get_rendered_video (lib/common/render.py:327-374: one pytorch3d render per camera and mesh,
+ * 360 cameras on a circle around the y axis, each frame copied to the host) by ONE call for all views of a mesh.  The rule is
+ * DESIGN.md 4.18 (PARITY UNPINNED): the camera of azimuth a has its eye at (100 cos a, 0, 100 sin a) and looks at the origin, +y
+ * up, under the orthographic projection of icon_render_normal; X = z c - x s, Y = y, D = (100 - x c) - z s with (c, s) the float32
+ * pair of a.  Everything after the projection is icon_render_normal's rule; no view is mirrored.  At (1,0) / (0,1) / (-1,0) /
+ * (0,-1) the float planes are those of cam 1 / 0 / 3 / 2.
+ * d_verts [V,3] f32; d_faces [F,3], int64 when faces_int64 != 0, else int32 - read in place; d_cos_sin: DEVICE [n_views,2] f32,
+ * the pairs (c, s) as icon_amd.render.turntable_cos_sin makes them; n_views: 1..1024; size: 8..2048.
+ * d_canvas: uint8 [n_views,size,canvas_width,3] or NULL - view k's frame; the mesh's panel is columns x0 .. x0 + size - 1
+ * (0 <= x0, x0 + size <= canvas_width) and NO byte outside the panel is written: several meshes and the input images share a
+ * frame side by side.  A byte is (uint8) min(max(t * 255, 0), 255) of t = (b0 t0 + b1 t1) + b2 t2, t_k = (n_k + 1) * 0.5, channels in
+ * the normal's x, y, z order; background 127.  d_images [n_views,3,size,size] f32 ((t - 0.5) * 2, background 0), d_depth
+ * [n_views,size,size] f32 (background -1), d_pix_to_face [n_views,size,size] int32 (background -1): as icon_render_normal's, each
+ * may be NULL; at least one of d_canvas / d_images is not.  A face that names a vertex that does not exist is skipped and
+ * counted: after the stream has been waited for, the first int32 of the scratch holds the number of such faces.
+ * The S1 normals are computed once per call; the views are rasterised in chunks (32 views, "tt_chunk"), so d_scratch - device
+ * memory of at least icon_render_turntable_bytes(V, F, size, n_views) bytes, 256-byte aligned, owned by the caller - holds the
+ * z-buffers of one chunk and does not grow with n_views beyond it.  Enqueued on `stream` as kernel launches only: no allocation,
+ * no synchronisation, nothing read back, no floating-point atomics; results are bit-identical from run to run and from int32 and
+ * int64 faces, whatever the chunk. */
+int icon_render_turntable_bytes(int64_t V, int64_t F, int size, int n_views, int64_t *bytes);
+int icon_render_turntable(const float *d_verts, int64_t V, const void *d_faces, int64_t F, int faces_int64,
+                          const float *d_cos_sin, int n_views, int size, uint8_t *d_canvas, int64_t canvas_width, int64_t x0,
+                          float *d_images, float *d_depth, int32_t *d_pix_to_face,
+                          void *d_scratch, int64_t scratch_bytes, void *stream);
 
 /* ---- the cloth refinement step without the renderer, forwards and backwards ------------------------------
  * what one iteration of the cloth loop of apps/infer.py:405-476 computes besides its normal maps: the LocalAffine deformation
