@@ -2,7 +2,8 @@
 """End-to-end on the synthetic subject: what apps/ICON.py:test_single does after netG.filter() (lines 729-761) -
 reconEngine -> export_mesh -> clean_mesh -> vertices into the [-1,1] cube - through the HIP path, with timings.
 
-    python examples/dense_recon.py [--res 257] [--adaptive] [--color] [--normal-maps] [--turntable DIR] [--out body.obj]
+    python examples/dense_recon.py [--res 257] [--adaptive] [--color] [--normal-maps] [--turntable DIR] [--garment OUT.obj]
+                                     [--out body.obj]
 
 Needs an MI355X (there is no CPU path).  The inputs stand in for what the reference computes upstream of the hot path:
 `features` = HGPIFuNet.filter() output, the SMPL tensors = TestDataset.compute_vis_cmap(), the regressor = netG.if_regressor.
@@ -26,6 +27,8 @@ def main():
                     "and write the normal maps as <out stem>_normal_<cam>.ppm")
     ap.add_argument("--turntable", metavar="DIR", default=None, help="render the cleaned mesh from 360 cameras around it (the frames of the "
                     "reference's turntable video; icon_amd.render) and write every 30th frame as DIR/turntable_<angle>.png")
+    ap.add_argument("--garment", metavar="OUT.obj", default=None, help="cut a garment out of the cleaned mesh (extract_cloth, apps/infer.py:565-605; "
+                    "icon_amd.garment): a fixed torso-shaped polygon, the synthetic body as the SMPL mesh with its parts split by height")
     args = ap.parse_args()
     import torch
     from icon_amd import synth
@@ -99,6 +102,23 @@ def main():
         for k, frames in enumerate(chunks):                                     # the reference hands the frame to the writer as it is
             Image.fromarray(frames[0].cpu().numpy()).save(os.path.join(args.turntable, f"turntable_{30 * k:03d}.png"))
         print(f"wrote {args.turntable}/turntable_000.png .. turntable_330.png")
+    if args.garment:
+        import numpy as np
+        from icon_amd.garment import Garment, extract_cloth_device
+        torso = np.array([[-0.2, 0.5], [0.0, 0.42], [0.2, 0.5], [0.24, 0.1], [0.18, -0.3], [-0.18, -0.3], [-0.24, 0.1]])   # model plane: what
+        body = T(a.smpl_verts[0])                                                # polygons_to_model_plane makes of a segmentation
+        band = ((body[:, 1] + 1.0) * 4.0).long().clamp(0, 7)                     # eight "parts" by height; the bands 4 and 6 (shoulders, head) go
+        remove = (band == 4) | (band == 6)
+        v_d, f_d = verts.to(dev), faces.to(dev)
+        extract_cloth_device(v_d, f_d, [torso], body, remove)                    # warm-up: the call's scratch
+        t7 = sync()
+        out = extract_cloth_device(v_d, f_d, [torso], body, remove, return_index=True)
+        ms = 1e3 * (sync() - t7)
+        if out is None:
+            print(f"garment: no face kept ({ms:.2f} ms)")
+        else:
+            Garment(*(x.cpu().numpy() for x in out)).export(args.garment)
+            print(f"garment: {out[0].shape[0]} vertices, {out[1].shape[0]} faces of {verts.shape[0]} / {faces.shape[0]} in {ms:.2f} ms; wrote {args.garment}")
     if args.out:
         v, f = verts.cpu().numpy(), faces.cpu().numpy() + 1
         with open(args.out, "w") as fh:

@@ -17,4 +17,7 @@ def __getattr__(name):
     if name in ("DenseReconEngine", "slab_bounds", "export_mesh_numpy"):
         from . import recon
         return getattr(recon, name)
+    if name in ("extract_cloth", "extract_cloth_device", "nearest_vertex_device", "transfer_labels_device"):
+        from . import garment
+        return getattr(garment, name)
     raise AttributeError(name)

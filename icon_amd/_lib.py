@@ -44,6 +44,7 @@ SYMBOLS = [
     "icon_local_affine_bytes", "icon_local_affine_forward", "icon_local_affine_backward",
     "icon_mesh_priors_bytes", "icon_mesh_priors_forward", "icon_mesh_priors_backward",
     "icon_smpl_bytes", "icon_smpl_forward", "icon_smpl_backward",
+    "icon_nearest_vertex", "icon_extract_cloth_bytes", "icon_extract_cloth",
 ]
 
 _lib = None

@@ -703,6 +703,37 @@ int icon_smpl_backward(const icon_smpl_tables *tables, const float *d_betas, con
                        const float *d_A, const float *d_grad_verts, const float *d_grad_joints,
                        float *d_grad_betas, float *d_grad_rot_mats, void *d_scratch, int64_t scratch_bytes, void *stream);
 
+/* ---- garment extraction: the submesh inside 2-D polygons, less the body parts a garment type excludes -------
+ * replaces extract_cloth (lib/common/cloth_extraction.py:75-170, called at apps/infer.py:565-605) and the classifier of
+ * smpl_to_recon_labels (:45-72).  The rule is DESIGN.md 4.19; every decision is an exact comparison in float64 on the float32
+ * coordinates widened exactly, pinned to matplotlib's Path.contains_points and sklearn's KNeighborsClassifier(n_neighbors=1).
+ * icon_nearest_vertex: d_verts [V,3] f32, d_src [Vs,3] f32 -> d_out_idx [V] int32: the LOWEST j minimising
+ *   ((dx*dx + dy*dy) + dz*dz), d = verts[i] - src[j] (numpy's ((q - s)**2).sum(-1).argmin()).  d_only: uint8 [V] or NULL - a
+ *   vertex whose byte is 0 is skipped and gets -1.  One launch; no allocation, no synchronisation.
+ * icon_extract_cloth: d_verts [V,3] f32; d_faces [F,3], int64 when faces_int64 != 0, else int32 - read in place; d_poly_xy
+ *   float64 [total_poly_verts,2], the polygons' vertices in the model's xy plane, polygon p being rows d_poly_off[p] ..
+ *   d_poly_off[p+1] - 1 (d_poly_off: int32 [P+1], DEVICE; a range that leaves [0, total_poly_verts) or holds fewer than 3
+ *   vertices selects nothing); d_src [Vs,3] f32 with d_src_remove uint8 [Vs], or all three NULL / 0: no source mesh.
+ *     selected(i): (x, y) of vertex i lies inside ANY polygon - the crossings test, each polygon closed from its last vertex
+ *                  to its first;  keep_v(i) = selected(i) and not src_remove[nearest source vertex of i] (no source mesh:
+ *                  selected(i));  a face is kept when any of its corners has keep_v - a face that names a vertex outside [0, V)
+ *                  never is;  out: the kept faces in order, the vertices they name in ascending order, faces renumbered.
+ *   d_out_verts [V,3] f32, d_out_faces [F,3] int32, d_out_vert_ids [V] int32 (the input index of every output vertex):
+ *   caller-allocated at the INPUT sizes; the first h_counts[0] vertices / h_counts[1] faces are valid (HOST int64 [2]).
+ *   d_scratch: device memory of at least icon_extract_cloth_bytes(V, F, total_poly_verts, P) bytes, 256-byte aligned, owned by
+ *   the caller; its contents need not survive between calls.  Enqueued on `stream`: one memset and seven launches (six without a
+ *   source mesh) whatever V, F and P are, no allocation; then the stream is synchronised ONCE, to hand the two counts back, as
+ *   icon_clean_mesh does.  No atomics: equal bytes from run to run and from int32 and int64 faces.  Coordinates are taken as
+ *   finite. */
+int icon_nearest_vertex(const float *d_verts, int64_t V, const float *d_src, int64_t Vs, const uint8_t *d_only,
+                        int32_t *d_out_idx, void *stream);
+int icon_extract_cloth_bytes(int64_t V, int64_t F, int64_t total_poly_verts, int64_t P, int64_t *bytes);
+int icon_extract_cloth(const float *d_verts, int64_t V, const void *d_faces, int64_t F, int faces_int64,
+                       const double *d_poly_xy, const int32_t *d_poly_off, int64_t total_poly_verts, int64_t P,
+                       const float *d_src, int64_t Vs, const uint8_t *d_src_remove,
+                       float *d_out_verts, int32_t *d_out_faces, int32_t *d_out_vert_ids, int64_t *h_counts,
+                       void *d_scratch, int64_t scratch_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
