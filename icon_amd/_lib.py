@@ -32,7 +32,7 @@ SYMBOLS = [
     "icon_query_points", "icon_query_points_dcalib", "icon_query_rows", "icon_grid_rows",
     "icon_volume_any_above", "icon_adaptive_eval", "icon_adaptive_counts", "icon_adaptive_reruns", "icon_grid_eval_slab", "icon_grid_slab_features", "icon_grid_slab_finish", "icon_grid_slab_features_msg",
     "icon_grid_slab_finish_gathered", "icon_debug_set_shell_skip", "icon_debug_set_option", "icon_work_status", "icon_sdf_query_ties", "icon_work_set_tie_rule",
-    "icon_export_mesh", "icon_mc_count", "icon_mc_emit", "icon_mc_count_range", "icon_mc_emit_keyed", "icon_debug_traversal_stats", "icon_debug_pair_stats", "icon_debug_walk_stats", "icon_debug_pair_box", "icon_debug_range_box", "icon_debug_box_bound", "icon_debug_box_bound_half", "icon_debug_set_unfused",
+    "icon_export_mesh", "icon_mc_count", "icon_mc_emit", "icon_mc_count_range", "icon_mc_emit_keyed", "icon_debug_traversal_stats", "icon_debug_pair_stats", "icon_debug_walk_stats", "icon_debug_pair_box", "icon_debug_range_box", "icon_debug_box_bound", "icon_debug_box_bound_half", "icon_debug_set_unfused", "icon_debug_mlp_pack_f16x3",
     "icon_visibility", "icon_mesh_components", "icon_clean_mesh", "icon_semantic_voxelize",
     "icon_mesh_batch_create", "icon_mesh_batch_destroy", "icon_mesh_batch_status", "icon_feat_create_batch", "icon_query_points_batch",
     "icon_feat_batch_set_volume", "icon_semantic_voxelize_batch",

@@ -437,7 +437,7 @@ __global__ __launch_bounds__(kF16Block, 2) void k_fused_f16x3(FusedGeom G, float
     issue_units(w.image, smem + kW0Off, kW0Bytes / 1024, wave0, lane0);
     float *side = reinterpret_cast<float *>(smem + kSideOff);
     for (int i = threadIdx.x; i < kSideFloats; i += kF16Block) side[i] = w.side[i];
-    const float *sb0 = side, *sb1 = side + 512, *sb2 = side + 768, *sw3 = side + 896;
+    const float *sb0 = side, *sb1 = side + 512, *sb2 = side + 768, *sw3 = side + kW3Float;
     int64_t K = 0, rank0 = 0;
     if (PRIOR == ICON_PRIOR_ICON) sign_list_extent(G, K, rank0);
     // wave-uniform 64-bit values that live across the whole MLP body: keep them in SGPRs, not in the
@@ -483,7 +483,7 @@ __global__ __launch_bounds__(kF16Block, 2) void k_fused_f16x3(FusedGeom G, float
         int tid = threadIdx.x;
         asm volatile("" : "+v"(tid));
         const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-        const int j = lane & 31, h = lane >> 5;
+        const int r = lane & 15, g = lane >> 4;
         // ---- feature phase: waves 0-3, one work item per thread -> Xs[t][16] -----------------------------
         const int t = tid;
         const bool draw = !SMALL && stealing && tile + 1 == tile_end;       // wave-uniform: this is the run's last tile
@@ -513,61 +513,57 @@ __global__ __launch_bounds__(kF16Block, 2) void k_fused_f16x3(FusedGeom G, float
             ++tile;
             continue;
         }
-        // ---- MLP: one wave = 32 points, lane (j,h) holds input slots 8h..8h+7 of point j ------------------
-        const int pt = wave * 32 + j;
-        float xr[8];
-        {
-            const float4 *q = reinterpret_cast<const float4 *>(Xs + pt * kXRow + 8 * h);
-            const float4 a = q[0], b4 = q[1];
-            xr[0] = a.x; xr[1] = a.y; xr[2] = a.z; xr[3] = a.w; xr[4] = b4.x; xr[5] = b4.y; xr[6] = b4.z; xr[7] = b4.w;
-        }
-        const float maskf = (__float_as_int(Xs[pt * kXRow + kCodeSlot]) & (int)kCodeInCube) ? 1.0f : 0.0f;
-#pragma unroll
-        for (int s = 0; s < 8; ++s) xr[s] = (s + 8 * h < w.c0) ? xr[s] : 0.0f;
-        half8 xhi, xlo;
-        split8(xr, xhi, xlo);
+        // ---- MLP: one wave = 32 points = two 16-point blocks; lane (r, g) holds k-slots 8g..8g+7 of points r and 16 + r ----
+        const int pt = wave * 32 + 16 * (g & 1) + r;          // the point this lane writes (lanes g < 2)
+        half8 xb[2];
+        const float tail = load_x(Xs + (wave * 32 + r) * kXRow + 8 * (g & 1), Xs + (wave * 32 + 16 + r) * kXRow + 8 * (g & 1), sw3, w.c0, g, xb);
+        float maskf = (__float_as_int(Xs[pt * kXRow + kCodeSlot]) & (int)kCodeInCube) ? 1.0f : 0.0f;
+        asm volatile("" : "+v"(maskf));     // the flag, not the row word and its address, crosses the MFMA body
 
-        f32x16 acc1[8];
+        f32x4 acc1[16][2];
 #pragma unroll
-        for (int m = 0; m < 8; ++m) acc1[m] = ld16(sb1 + (m * 2 + h) * 16);
+        for (int m = 0; m < 16; ++m) acc1[m][0] = acc1[m][1] = *reinterpret_cast<const f32x4 *>(sb1 + m * 16 + 4 * g);
         half8 bh[2], bl[2];
-        activate_split(l0_tile(smem + kW0Off, sb0, 0, xhi, xlo, h, lane), LeakyK{w.inv0, w.p0, w.q0}, bh, bl);
-        f32x16 acc2[4];
-        for (int c = 0; c < 16; ++c) {
-            l01_chunk(smem + (c & 1) * kBufBytes, smem + ((c + 1) & 1) * kBufBytes, smem + kW0Off, sb0, w.image, c, acc1, xhi, xlo,
-                      LeakyK{w.inv0, w.p0, w.q0}, h, lane, wave, bh, bl);
+        const LeakyK k0{w.inv0, w.p0, w.q0}, k1{w.inv1, w.p1, w.q1};
+        {
+            f32x4 h0[2][2];
+            l0_tiles(smem + kW0Off, sb0, 0, xb, g, lane, h0);
+            activate_split(h0[0][0], h0[0][1], h0[1][0], h0[1][1], k0, bh, bl);
+        }
+        f32x4 acc2[8][2];
+        for (int c = 0; c < 15; ++c) {
+            l01_chunk<false>(smem + (c & 1) * kBufBytes, smem + ((c + 1) & 1) * kBufBytes, smem + kW0Off, sb0, w.image, c, acc1, xb,
+                             k0, g, lane, wave, bh, bl);
             ICON_CHUNK_BARRIER();
         }
+        l01_chunk<true>(smem + kBufBytes, smem, smem + kW0Off, sb0, w.image, 15, acc1, xb, k0, g, lane, wave, bh, bl);
+        ICON_CHUNK_BARRIER();
 #pragma unroll
-        for (int m2 = 0; m2 < 4; ++m2) acc2[m2] = ld16(sb2 + (m2 * 2 + h) * 16);
-        activate_split(acc1[0], LeakyK{w.inv1, w.p1, w.q1}, bh, bl);
-        l2_chunk<0>(smem, smem + kBufBytes, w.image, acc1, acc2, xhi, xlo, LeakyK{w.inv1, w.p1, w.q1}, lane, wave, bh, bl);
+        for (int m2 = 0; m2 < 8; ++m2) acc2[m2][0] = acc2[m2][1] = *reinterpret_cast<const f32x4 *>(sb2 + m2 * 16 + 4 * g);
+        activate_split(acc1[0][0], acc1[1][0], acc1[0][1], acc1[1][1], k1, bh, bl);
+        l2_chunk<0>(smem, smem + kBufBytes, w.image, acc1, acc2, xb, k1, g, lane, wave, bh, bl);
         ICON_CHUNK_BARRIER();
-        l2_chunk<1>(smem + kBufBytes, smem, w.image, acc1, acc2, xhi, xlo, LeakyK{w.inv1, w.p1, w.q1}, lane, wave, bh, bl);
+        l2_chunk<1>(smem + kBufBytes, smem, w.image, acc1, acc2, xb, k1, g, lane, wave, bh, bl);
         ICON_CHUNK_BARRIER();
-        l2_chunk<2>(smem, smem + kBufBytes, w.image, acc1, acc2, xhi, xlo, LeakyK{w.inv1, w.p1, w.q1}, lane, wave, bh, bl);
+        l2_chunk<2>(smem, smem + kBufBytes, w.image, acc1, acc2, xb, k1, g, lane, wave, bh, bl);
         ICON_CHUNK_BARRIER();
-        l2_chunk<3>(smem + kBufBytes, smem, w.image, acc1, acc2, xhi, xlo, LeakyK{w.inv1, w.p1, w.q1}, lane, wave, bh, bl, more ? 0 : -1);
+        l2_chunk<3>(smem + kBufBytes, smem, w.image, acc1, acc2, xb, k1, g, lane, wave, bh, bl, more ? 0 : -1);
 
         // ---- layer 3 on the VALU (f32) ---------------------------------------------------------------------
-        const float *w3 = sw3 + h * 72;
-        float part = 0.0f;
-#pragma unroll
-        for (int m2 = 0; m2 < 4; ++m2) {
-            const f32x16 wv = ld16(w3 + m2 * 16);
-#pragma unroll
-            for (int tt = 0; tt < 16; ++tt) {
-                part = fmaf(wv[tt], leaky_scaled(acc2[m2][tt], LeakyK{w.inv2, w.p2, w.q2}), part);
-            }
+        float y2[2];
+        {
+            int tid_3 = threadIdx.x;
+            asm volatile("" : "+v"(tid_3), "+v"(acc2[0][0]));     // layer 3's lane group, re-derived behind layer 2
+            l3_sum(sw3, acc2, tail, LeakyK{w.inv2, w.p2, w.q2}, w.b3, (tid_3 >> 4) & 3, y2);
         }
-#pragma unroll
-        for (int s = 0; s < 8; ++s) part = fmaf(w3[64 + s], xr[s], part);
-        const float other = __shfl_xor(part, 32);
-        const float y = apply_last_op((part + other) + w.b3, w.last_op);
-        // where this point's occupancy goes is re-derived from the work item (a handful of integer instructions):
-        // nothing lane-dependent lives across the MFMA body
-        const int64_t oq = (int64_t)tile * tp + pt;
-        if (h == 0 && oq < G.N) {
+        // where this point's occupancy goes is re-derived from the work item (a handful of integer instructions) BEHIND the
+        // result it depends on: nothing lane-dependent lives across the MFMA body
+        int tid_o = threadIdx.x;
+        asm volatile("" : "+v"(tid_o), "+v"(y2[0]), "+v"(y2[1]));
+        const int g_o = (tid_o >> 4) & 3, pt_o = (tid_o >> 6) * 32 + 16 * (g_o & 1) + (tid_o & 15);
+        const float y = apply_last_op(g_o == 0 ? y2[0] : y2[1], w.last_op);
+        const int64_t oq = (int64_t)tile * tp + pt_o;
+        if (g_o < 2 && oq < G.N) {
             int ix, iy, iz;
             out[SRC == Src::Lattice ? lattice_item(G, oq, ix, iy, iz) : ((SRC == Src::Points && G.out_map) ? (int64_t)G.out_map[oq] : oq)] = masked_result(y, maskf != 0.0f, w.flag);
         }

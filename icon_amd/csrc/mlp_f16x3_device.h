@@ -6,7 +6,7 @@
 
 namespace icon {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef __fp16 fp16x2 __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(1))) const void gvoid_t;
@@ -15,21 +15,28 @@ typedef __attribute__((address_space(3))) void lvoid_t;
 constexpr int kF16Block = 512;                 // 8 waves x 32 points
 constexpr int kF16Pts = (kF16Block / 64) * 32; // 256 points per workgroup
 constexpr int kBufBytes = 40 * 1024;
-constexpr int kSideFloats = 512 + 256 + 128 + 144;   // b0 | b1 | b2 | w3, staged once per workgroup
+constexpr int kW3Stride = 40;                        // w3 per lane group g: 32 hidden weights + 8 raw-input weights
+constexpr int kW3Float = 512 + 256 + 128;
+constexpr int kZeroFloat = kW3Float + 4 * kW3Stride; // 16 bytes of zeros: the k >= 16 half of the packed [W_lo | 0] operands
+constexpr int kSideFloats = kZeroFloat + 4;          // b0 | b1 | b2 | w3 | zeros, staged once per workgroup
 constexpr int kW0Off = 2 * kBufBytes;                // layer-0 operands, resident for the whole workgroup
 constexpr int kW0Bytes = 32 * 1024;
 constexpr int kSideOff = kW0Off + kW0Bytes;
 constexpr int kLdsBytes = kSideOff + 4352;           // 80 KiB double buffer + 32 KiB W0 + 4.25 KiB side arrays
+constexpr int kZeroFromW0 = kSideOff + kZeroFloat * 4 - kW0Off;   // the zeros, addressed from the W0 region's base
+constexpr int kZeroFromBuf0 = kSideOff + kZeroFloat * 4;          // ... and from the first weight buffer = the start of the LDS
+static_assert(kSideFloats * 4 <= 4352 && kZeroFromW0 % 16 == 0, "side arrays");
 
-// packed image: [W0: 32 KiB][layer-1 chunks 0..15: 32 KiB each][layer-2 chunks 16..18: 32 KiB, 19: 40 KiB]
+// packed image: [W0: 32 KiB][layer-1 chunks 0..15: 32 KiB each][layer-2 chunks 16: 40 KiB (the raw-input tiles ride on the
+// FIRST one: their B operand, the split input row, leaves the registers before the chain is at its widest), 17..19: 32 KiB]
 // chunk k: size in KiB and offset in KiB inside the image
-__host__ __device__ constexpr int chunk_units(int k) { return k < 19 ? 32 : 40; }
-__host__ __device__ constexpr int chunk_offset(int k) { return 32 + 32 * k; }
+__host__ __device__ constexpr int chunk_units(int k) { return k == 16 ? 40 : 32; }
+__host__ __device__ constexpr int chunk_offset(int k) { return 32 + 32 * k + (k > 16 ? 8 : 0); }
 constexpr size_t kImageBytes = (size_t)(32 + 19 * 32 + 40) * 1024;   // 680 KiB
 
 struct MlpF16Dev {
     const char *image;          // packed f16 hi/lo A operands, chunked
-    const float *side;          // f32: b0 [16][2][16] | b1 [8][2][16] | b2 [4][2][16] (bias * weight scale) | w3 [2][72]
+    const float *side;          // f32: b0 [512] | b1 [256] | b2 [128] (bias * weight scale, channel order) | w3 [4][40] | 4 zeros
     float b3;
     float inv0, inv1, inv2;     // 1 / weight scale of layers 0..2
     // LeakyReLU constants 0.505 / scale and 0.495 / scale per layer, from the host: wave-uniform kernel arguments stay in SGPRs
@@ -45,16 +52,6 @@ __device__ __forceinline__ float masked_result(float y, bool in_cube, int *flag)
 {
     if (in_cube && not_finite(y)) *flag = 1;
     return in_cube ? y : 0.0f;
-}
-
-__device__ __forceinline__ f32x16 ld16(const float *p)
-{
-    const float4 *q = reinterpret_cast<const float4 *>(p);
-    const float4 a = q[0], b = q[1], c = q[2], d = q[3];
-    f32x16 v;
-    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-    v[8] = c.x; v[9] = c.y; v[10] = c.z; v[11] = c.w; v[12] = d.x; v[13] = d.y; v[14] = d.z; v[15] = d.w;
-    return v;
 }
 
 // lo halves of a pair: f16(v - hi), the subtraction exact in f32 (hi is a truncation of v), ONE rounding
@@ -103,17 +100,13 @@ __device__ __forceinline__ float leaky_scaled(float a, const LeakyK &k)
 #endif
 }
 
-// activation step of a finished tile: undo the weight scale, LeakyReLU(0.01), split for the next GEMM
-__device__ __forceinline__ void activate_split(const f32x16 &acc, const LeakyK &inv, half8 hi[2], half8 lo[2])
-{
-    float v[16];
-#pragma unroll
-    for (int t = 0; t < 16; ++t) v[t] = leaky_scaled(acc[t], inv);
-    split8(v, hi[0], lo[0]);
-    split8(v + 8, hi[1], lo[1]);
-}
-
-#define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_f16((a), (b), (c), 0, 0, 0)
+// The MFMA is v_mfma_f32_16x16x32_f16 (16 cycles, K = 32 per instruction).  Lane l = (r = l & 15, g = l >> 4):
+//   A (weights, 16 channels x 32 k): row r, halves k = 8g..8g+7;   B (points, 32 k x 16 points): point r, the same k;
+//   D: acc[j] = channel 4g + j of point r.
+// One wave = 32 points = two 16-point blocks b (point 16b + r).  Two finished 16-channel D tiles Ta, Tb of a block hold
+// eight values of the lane's own point: they ARE k-slots 8g..8g+7 of one K = 32 step of the next layer,
+//   slot 8g + e  <-  channel 4g + e of Ta (e < 4),  channel 16 + 4g + (e - 4) of Tb (e >= 4)      [sigma() of the packer]
+#define MFMA32(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_f16((a), (b), (c), 0, 0, 0)
 
 __device__ __forceinline__ half8 lds_op(const char *buf, int slot, int lane)
 {
@@ -137,40 +130,83 @@ __device__ __forceinline__ void issue_chunk(const char *image, char *buf, int k,
     issue_units(image + (size_t)chunk_offset(k) * 1024, buf, chunk_units(k), wave, lane);
 }
 
-// 3-term product group for 4 output tiles sharing one B operand pair
-#define TRIPLE4(ACC, M0, AH, AL, BH, BL)                                     \
-    _Pragma("unroll") for (int i4 = 0; i4 < 4; ++i4) ACC[M0 + i4] = MFMA16(AH[i4], BH, ACC[M0 + i4]); \
-    _Pragma("unroll") for (int i4 = 0; i4 < 4; ++i4) ACC[M0 + i4] = MFMA16(AH[i4], BL, ACC[M0 + i4]); \
-    _Pragma("unroll") for (int i4 = 0; i4 < 4; ++i4) ACC[M0 + i4] = MFMA16(AL[i4], BH, ACC[M0 + i4]);
-
 // The per-chunk bodies take the buffer being READ, the buffer being FILLED and the side arrays as
 // __restrict__ parameters of a force-inlined function: after inlining, the ds_reads carry alias
 // scopes that prove they cannot touch the LDS-DMA destination, so the compiler's waitcnt pass does
 // not drain the DMA queue (s_waitcnt vmcnt(0)) in front of every LDS read - the DMA for chunk k+1
 // stays in flight for the whole multiplication of chunk k and is only waited for at the barrier.
 
-// 3-term product group for 2 output tiles sharing one B operand pair
-#define TRIPLE2(ACC, M0, AH, AL, BH, BL)                                     \
-    ACC[M0] = MFMA16(AH[0], BH, ACC[M0]); ACC[M0 + 1] = MFMA16(AH[1], BH, ACC[M0 + 1]); \
-    ACC[M0] = MFMA16(AH[0], BL, ACC[M0]); ACC[M0 + 1] = MFMA16(AH[1], BL, ACC[M0 + 1]); \
-    ACC[M0] = MFMA16(AL[0], BH, ACC[M0]); ACC[M0 + 1] = MFMA16(AL[1], BH, ACC[M0 + 1]);
+// 3-term product group of one output tile M of both point blocks: 6 MFMAs (96 cycles), an accumulator comes back
+// after two instructions.  Groups are per TILE so that only one tile's operands are held while the next one's are read.
+#define GROUP6(ACC, M, AH, AL, BH, BL)                                                              \
+    ACC[M][0] = MFMA32(AH, BH[0], ACC[M][0]); ACC[M][1] = MFMA32(AH, BH[1], ACC[M][1]);             \
+    ACC[M][0] = MFMA32(AH, BL[0], ACC[M][0]); ACC[M][1] = MFMA32(AH, BL[1], ACC[M][1]);             \
+    ACC[M][0] = MFMA32(AL, BH[0], ACC[M][0]); ACC[M][1] = MFMA32(AL, BH[1], ACC[M][1]);
 
-// layer 0, hidden tile c (32 channels): 3 MFMAs from the resident W0 region
-__device__ __forceinline__ f32x16 l0_tile(const char *__restrict__ W0, const float *__restrict__ sb0, int c, half8 xhi, half8 xlo,
-                                          int h, int lane)
+// The raw-input operand of a wave (layer 0 and the tail of layer 2): K = c0 <= 16, so TWO of the three terms share one
+// K = 32 instruction:  [W_hi | W_hi] x [x_hi | x_lo]  and  [W_lo | 0] x [x_hi | x_lo]  (the x_lo half meets zeros).
+// xb[b]: lanes g < 2 hold x_hi[8g..8g+7] of point 16b + r, lanes g >= 2 hold x_lo[8(g-2)..].  row0 / row1: the f32 rows
+// of the lane's two points at input 8 (g & 1).  Returns the lane's share of layer 3's raw-input columns (f32, inputs
+// 8 (g & 1) + s of the point of block g >> 1; one fma chain from 0, s ascending): one register across the MFMA body
+// where the eight inputs would be eight.
+__device__ __forceinline__ float load_x(const float *row0, const float *row1, const float *__restrict__ sw3, int c0, int g, half8 (&xb)[2])
 {
-    f32x16 h0 = ld16(sb0 + (c * 2 + h) * 16);
-    const half8 a_hi = lds_op(W0, 2 * c, lane), a_lo = lds_op(W0, 2 * c + 1, lane);
-    h0 = MFMA16(a_hi, xhi, h0); h0 = MFMA16(a_hi, xlo, h0); h0 = MFMA16(a_lo, xhi, h0);
-    return h0;
+    float tail = 0.0f;
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+        const float4 *q = reinterpret_cast<const float4 *>(b ? row1 : row0);
+        const float4 u = q[0], v = q[1];
+        float x[8] = {u.x, u.y, u.z, u.w, v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int s = 0; s < 8; ++s) x[s] = (s + 8 * (g & 1) < c0) ? x[s] : 0.0f;
+        half8 hi, lo;
+        split8(x, hi, lo);
+        xb[b] = g < 2 ? hi : lo;
+        float t = 0.0f;
+#pragma unroll
+        for (int s = 0; s < 8; ++s) t = fmaf(sw3[g * kW3Stride + 32 + s], x[s], t);
+        tail = (g >> 1) == b ? t : tail;
+    }
+    // (opaque: computed HERE - sunk behind the MFMA body, where its result is used, it would keep the sixteen inputs alive)
+    asm volatile("" : "+v"(tail));
+    return tail;
 }
 
-// one eighth of the activation step of a finished layer-0 tile: values 2k, 2k+1 -> LeakyReLU ->
-// hi/lo halves -> pair (k&3) of the next B operand (u = k>>2)
-__device__ __forceinline__ void act_part(const f32x16 &acc, int k, const LeakyK &inv, half8 (&nh)[2], half8 (&nl)[2])
+// A operands of a raw-input tile (1 KiB: [W_hi: 32 lanes][W_lo: 32 lanes], lane (r, g & 1)): a1 = [W_hi | W_hi],
+// a2 = [W_lo | 0] - lanes g >= 2 read the 16 zero bytes behind the side arrays; zero_off: their offset from `base`
+// (kZeroFromW0 for the W0 region, kZeroFromBuf0 for the first weight buffer).  The zeros meet the x_lo half of
+// B = [x_hi | x_lo] - the same as a B of [x_hi | 0] for every finite x_lo; an x_lo that is not (|x| beyond the f16 range)
+// gives NaN, which raises the range flag as the hi * lo term always did.
+__device__ __forceinline__ void raw_operands(const char *__restrict__ base, int tile, int zero_off, int g, int lane, half8 &a1, half8 &a2)
 {
+    const int col = (lane & 31) * 16;
+    const int lo_off = g < 2 ? 512 + col : zero_off, lo_mul = g < 2 ? 1024 : 0;
+    a1 = *reinterpret_cast<const half8 *>(base + tile * 1024 + col);
+    a2 = *reinterpret_cast<const half8 *>(base + lo_off + tile * lo_mul);
+}
 
-    const float v0 = leaky_scaled(acc[2 * k], inv), v1 = leaky_scaled(acc[2 * k + 1], inv);      // 7 VALU per pair with the split below
+// layer 0, hidden channels 32c..32c+31 of both point blocks (h0[b][t]: channel tile 2c + t): 8 MFMAs from the resident W0 region
+__device__ __forceinline__ void l0_tiles(const char *__restrict__ W0, const float *__restrict__ sb0, int c, const half8 (&xb)[2],
+                                         int g, int lane, f32x4 (&h0)[2][2])
+{
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+        const f32x4 bias = *reinterpret_cast<const f32x4 *>(sb0 + (2 * c + t) * 16 + 4 * g);
+        half8 a1, a2;
+        raw_operands(W0, 2 * c + t, kZeroFromW0, g, lane, a1, a2);
+        h0[0][t] = MFMA32(a1, xb[0], bias); h0[1][t] = MFMA32(a1, xb[1], bias);
+        h0[0][t] = MFMA32(a2, xb[0], h0[0][t]); h0[1][t] = MFMA32(a2, xb[1], h0[1][t]);
+    }
+}
+
+// one eighth of the activation step of two finished tiles Ta, Tb of both blocks: block b = k >> 2, pair q = k & 3 of its
+// next B operand (slots 2q, 2q+1: from Ta for q < 2, from Tb otherwise) -> LeakyReLU -> hi/lo halves
+__device__ __forceinline__ void act_part(const f32x4 &ta0, const f32x4 &tb0, const f32x4 &ta1, const f32x4 &tb1, int k, const LeakyK &inv,
+                                         half8 (&nh)[2], half8 (&nl)[2])
+{
+    const int b = k >> 2, q = k & 3, j0 = (q & 1) * 2;
+    const f32x4 &src = b ? (q >> 1 ? tb1 : ta1) : (q >> 1 ? tb0 : ta0);
+    const float v0 = leaky_scaled(src[j0], inv), v1 = leaky_scaled(src[j0 + 1], inv);      // 7 VALU per pair with the split below
     fp16x2 hh = __builtin_amdgcn_cvt_pkrtz(v0, v1);
     fp16x2 ll = residual_pair(hh, v0, v1);
     // the (empty) volatile asm is ordered against the surrounding sched_barriers, which keeps this
@@ -178,90 +214,115 @@ __device__ __forceinline__ void act_part(const f32x16 &acc, int k, const LeakyK 
     int hb = __builtin_bit_cast(int, hh), lb = __builtin_bit_cast(int, ll);
     asm volatile("" : "+v"(hb), "+v"(lb));
     hh = __builtin_bit_cast(fp16x2, hb); ll = __builtin_bit_cast(fp16x2, lb);
-    const int u = k >> 2, q = k & 3;
-    nh[u][2 * q] = (_Float16)hh[0]; nh[u][2 * q + 1] = (_Float16)hh[1];
-    nl[u][2 * q] = (_Float16)ll[0]; nl[u][2 * q + 1] = (_Float16)ll[1];
+    nh[b][2 * q] = (_Float16)hh[0]; nh[b][2 * q + 1] = (_Float16)hh[1];
+    nl[b][2 * q] = (_Float16)ll[0]; nl[b][2 * q + 1] = (_Float16)ll[1];
 }
 
-// A operands of MFMA group g of a layer-1 chunk: output tiles 2*(g&3), +1 for k-step u = g>>2
-__device__ __forceinline__ void load_group(const char *__restrict__ L, int g, int lane, half8 (&a)[4])
+// activation step of two finished tiles outside the pipelined bodies (the first B operand of a layer)
+__device__ __forceinline__ void activate_split(const f32x4 &ta0, const f32x4 &tb0, const f32x4 &ta1, const f32x4 &tb1, const LeakyK &inv,
+                                               half8 (&bh)[2], half8 (&bl)[2])
 {
-    const int slot = ((g >> 2) * 8 + (g & 3) * 2) * 2;
-    a[0] = lds_op(L, slot, lane); a[1] = lds_op(L, slot + 2, lane);        // hi of tile 0, 1
-    a[2] = lds_op(L, slot + 1, lane); a[3] = lds_op(L, slot + 3, lane);    // lo of tile 0, 1
+#pragma unroll
+    for (int k = 0; k < 8; ++k) act_part(ta0, tb0, ta1, tb1, k, inv, bh, bl);
 }
 
-// layer 1, chunk c (K = hidden channels 32c..32c+31, B operands bh/bl prepared one iteration
-// earlier) SOFTWARE-PIPELINED with layer 0 of chunk c+1: its three MFMAs are issued first; its
-// LeakyReLU + hi/lo split (pure VALU, 8 parts) is slotted between the eight 6-MFMA groups of this
-// chunk, and the LDS reads of group g+1 are issued ahead of the MFMAs of group g.  sched_barrier
+// layer 1, chunk c (K = hidden channels 32c..32c+31 = ONE k-step, B operands bh/bl prepared one iteration
+// earlier) SOFTWARE-PIPELINED with layer 0 of chunk c+1: its eight MFMAs are issued first; its
+// LeakyReLU + hi/lo split (pure VALU, 8 parts) is slotted behind every second of the sixteen 6-MFMA groups of this
+// chunk, and the LDS reads of group t+1 are issued ahead of the MFMAs of group t.  sched_barrier
 // pins that interleave so the matrix pipe and the VALU run side by side instead of alternating.
+// The last chunk has no successor: it runs without the layer-0 part.  Tile t: hi in slot 2t, lo in 2t + 1.
+template <bool LAST>
 __device__ __forceinline__ void l01_chunk(const char *__restrict__ L, char *__restrict__ nxt, const char *__restrict__ W0,
-                                          const float *__restrict__ sb0, const char *image, int c, f32x16 (&acc1)[8],
-                                          half8 xhi, half8 xlo, const LeakyK &inv0, int h, int lane, int wave,
+                                          const float *__restrict__ sb0, const char *image, int c, f32x4 (&acc1)[16][2],
+                                          const half8 (&xb)[2], const LeakyK &inv0, int g4, int lane, int wave,
                                           half8 (&bh)[2], half8 (&bl)[2])
 {
     issue_chunk(image, nxt, c + 1, wave, lane);
-    const f32x16 h0n = l0_tile(W0, sb0, min(c + 1, 15), xhi, xlo, h, lane);   // c == 15: harmless repeat
+    f32x4 h0n[2][2];
+    if (!LAST) l0_tiles(W0, sb0, c + 1, xb, g4, lane, h0n);
     half8 nh[2], nl[2];
-    half8 a[2][4];
-    load_group(L, 0, lane, a[0]);
+    half8 a[2][2];
+    a[0][0] = lds_op(L, 0, lane); a[0][1] = lds_op(L, 1, lane);
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-    for (int g = 0; g < 8; ++g) {
-        if (g + 1 < 8) load_group(L, g + 1, lane, a[(g + 1) & 1]);
-        const int u = g >> 2, m0 = (g & 3) * 2;
-        const half8 ah[2] = {a[g & 1][0], a[g & 1][1]}, al[2] = {a[g & 1][2], a[g & 1][3]};
-        TRIPLE2(acc1, m0, ah, al, bh[u], bl[u])
-        if (g >= 1) act_part(h0n, g - 1, inv0, nh, nl);
+    for (int t = 0; t < 16; ++t) {
+        if (t + 1 < 16) { a[(t + 1) & 1][0] = lds_op(L, 2 * t + 2, lane); a[(t + 1) & 1][1] = lds_op(L, 2 * t + 3, lane); }
+        GROUP6(acc1, t, a[t & 1][0], a[t & 1][1], bh, bl)
+        if (!LAST && (t & 1)) act_part(h0n[0][0], h0n[0][1], h0n[1][0], h0n[1][1], t >> 1, inv0, nh, nl);
         __builtin_amdgcn_sched_barrier(0);
     }
-    act_part(h0n, 7, inv0, nh, nl);
-    bh[0] = nh[0]; bh[1] = nh[1]; bl[0] = nl[0]; bl[1] = nl[1];
+    if (!LAST) { bh[0] = nh[0]; bh[1] = nh[1]; bl[0] = nl[0]; bl[1] = nl[1]; }
 }
 
-// layer 2, chunk 16+Q: hidden tiles 2Q, 2Q+1 (+ the raw-input k-step in the last chunk).
-// Same pipelining as layer 1: while the 24 MFMAs of hidden tile m run, the activation + split of
-// tile m+1 (the next B operand) is slotted between the four 6-MFMA groups, two parts per group.
+// layer 2, chunk 16+Q: k-steps 2Q, 2Q+1 = hidden tiles 4Q..4Q+3 (+ the raw-input k-step in front of the first chunk).
+// Same pipelining as layer 1: while the 48 MFMAs of k-step kk run, the activation + split of
+// hidden tiles 2kk+2, 2kk+3 (the next B operand) is slotted behind the eight 6-MFMA groups, one part per group.
 template <int Q>
 __device__ __forceinline__ void l2_chunk(const char *__restrict__ L, char *__restrict__ nxt, const char *image,
-                                         f32x16 (&acc1)[8], f32x16 (&acc2)[4], half8 xhi, half8 xlo, const LeakyK &inv1,
-                                         int lane, int wave, half8 (&bh)[2], half8 (&bl)[2], int next_chunk = (Q < 3) ? 17 + Q : -1)
+                                         f32x4 (&acc1)[16][2], f32x4 (&acc2)[8][2], const half8 (&xb)[2], const LeakyK &inv1,
+                                         int g4, int lane, int wave, half8 (&bh)[2], half8 (&bl)[2], int next_chunk = (Q < 3) ? 17 + Q : -1)
 {
     // next_chunk: the chunk DMA'd into `nxt` while this one is multiplied; the persistent kernel passes 0 for
     // Q == 3 (chunk 0 of its NEXT tile) - issued from inside this body so that it shares the alias scopes
     if (next_chunk >= 0) issue_chunk(image, nxt, next_chunk, wave, lane);
+    if (Q == 0) {
+        // raw inputs first: tiles of 1 KiB behind the 32 KiB of hidden k-steps (chunk 16 always lands in the FIRST buffer)
+#pragma unroll
+        for (int m2 = 0; m2 < 8; ++m2) {
+            half8 a1, a2;
+            raw_operands(L, 32 + m2, kZeroFromBuf0, g4, lane, a1, a2);
+            acc2[m2][0] = MFMA32(a1, xb[0], acc2[m2][0]); acc2[m2][1] = MFMA32(a1, xb[1], acc2[m2][1]);
+            acc2[m2][0] = MFMA32(a2, xb[0], acc2[m2][0]); acc2[m2][1] = MFMA32(a2, xb[1], acc2[m2][1]);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
 #pragma unroll
     for (int mm = 0; mm < 2; ++mm) {
         constexpr int kLast = 7;
-        const int m = 2 * Q + mm;
+        const int kk = 2 * Q + mm, n = kk < kLast ? 2 * kk + 2 : 0;
         half8 nh[2], nl[2];
-        half8 a[2][4];
-        auto load2 = [&](int g, half8 (&dst)[4]) {          // group g: k-step u = g>>1, output tiles 2*(g&1), +1
-            const int slot = (((mm * 2 + (g >> 1)) * 4 + (g & 1) * 2) * 2);
-            dst[0] = lds_op(L, slot, lane); dst[1] = lds_op(L, slot + 2, lane);
-            dst[2] = lds_op(L, slot + 1, lane); dst[3] = lds_op(L, slot + 3, lane);
-        };
-        load2(0, a[0]);
+        half8 a[2][2];
+        a[0][0] = lds_op(L, mm * 16, lane); a[0][1] = lds_op(L, mm * 16 + 1, lane);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            if (g + 1 < 4) load2(g + 1, a[(g + 1) & 1]);
-            const int u = g >> 1, m0 = (g & 1) * 2;
-            const half8 ah[2] = {a[g & 1][0], a[g & 1][1]}, al[2] = {a[g & 1][2], a[g & 1][3]};
-            TRIPLE2(acc2, m0, ah, al, bh[u], bl[u])
-            if (m < kLast) { act_part(acc1[m < kLast ? m + 1 : m], 2 * g, inv1, nh, nl); act_part(acc1[m < kLast ? m + 1 : m], 2 * g + 1, inv1, nh, nl); }
+        for (int t = 0; t < 8; ++t) {
+            if (t + 1 < 8) { a[(t + 1) & 1][0] = lds_op(L, mm * 16 + 2 * t + 2, lane); a[(t + 1) & 1][1] = lds_op(L, mm * 16 + 2 * t + 3, lane); }
+            GROUP6(acc2, t, a[t & 1][0], a[t & 1][1], bh, bl)
+            if (kk < kLast) act_part(acc1[n][0], acc1[n + 1][0], acc1[n][1], acc1[n + 1][1], t, inv1, nh, nl);
             __builtin_amdgcn_sched_barrier(0);
         }
-        if (m < kLast) { bh[0] = nh[0]; bh[1] = nh[1]; bl[0] = nl[0]; bl[1] = nl[1]; }
-    }
-    if (Q == 3) {
-        half8 ah[4], al[4];
-#pragma unroll
-        for (int i4 = 0; i4 < 4; ++i4) { ah[i4] = lds_op(L, 32 + i4 * 2, lane); al[i4] = lds_op(L, 33 + i4 * 2, lane); }
-        TRIPLE4(acc2, 0, ah, al, xhi, xlo)
+        if (kk < kLast) { bh[0] = nh[0]; bh[1] = nh[1]; bl[0] = nl[0]; bl[1] = nl[1]; }
     }
 }
 
+// layer 3 on the VALU (f32) + the cross-lane sum.  Summation order of a point, stated for tools/sim_f16x3.py and the same
+// wherever the point sits in its wave (fused and materialising kernels place it differently): per lane group g one fma chain
+// H_g over its hidden channels 16 m2 + 4g + j (m2 = 0..7 outer, j = 0..3 inner, starting from 0);
+// H = (H_0 + H_1) + (H_2 + H_3) (partners 16, then 32 lanes apart); the raw inputs 8 h + s (s = 0..7, fma chains T_h from 0:
+// load_x, carried by lane groups 2 (block) + h) give T = T_0 + T_1;  y = (H + T) + b3.  y[b]: point 16b + r, in every lane.
+__device__ __forceinline__ void l3_sum(const float *__restrict__ sw3, const f32x4 (&acc2)[8][2], float tail, const LeakyK &inv2,
+                                       float b3, int g, float (&y)[2])
+{
+    const float *w3 = sw3 + g * kW3Stride;
+    float part[2] = {0.0f, 0.0f};
+#pragma unroll
+    for (int m2 = 0; m2 < 8; ++m2) {
+        const f32x4 wv = *reinterpret_cast<const f32x4 *>(w3 + 4 * m2);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            part[0] = fmaf(wv[j], leaky_scaled(acc2[m2][0][j], inv2), part[0]);
+            part[1] = fmaf(wv[j], leaky_scaled(acc2[m2][1][j], inv2), part[1]);
+        }
+    }
+    const float t = tail + __shfl_xor(tail, 16);        // lane groups 0, 1: T of block 0; 2, 3: T of block 1
+    const float t_other = __shfl_xor(t, 32);
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+        part[b] += __shfl_xor(part[b], 16);
+        part[b] += __shfl_xor(part[b], 32);
+        y[b] = (part[b] + ((g >> 1) == b ? t : t_other)) + b3;
+    }
+}
 
 }  // namespace icon

@@ -44,7 +44,7 @@ enum { ICON_PRIOR_ICON = 0, ICON_PRIOR_PAMIR = 1, ICON_PRIOR_PIFU = 2 };
 enum { ICON_CMAP_REFERENCE = 0, ICON_CMAP_LOCAL = 1 };
 
 /* MLP arithmetic.  F32: v_mfma_f32_32x32x2_f32, bit-for-bit an f32 fma chain.  F16X3 (the DEFAULT
- * of the host layer): every product as a_hi*b_hi + a_hi*b_lo + a_lo*b_hi on v_mfma_f32_32x32x16_f16
+ * of the host layer): every product as a_hi*b_hi + a_hi*b_lo + a_lo*b_hi on v_mfma_f32_16x16x32_f16
  * with f32 accumulation (22-bit operands; ~1e-6 of the f32 result, 5x the rate) - f32-class.
  * Its range is f16's: an input or hidden activation beyond 65504 (a thousand times anything a body mesh produces; a mesh
  * squashed flat reaches it) would make the result NaN - the kernels flag such points and redo them in plain f32
@@ -365,6 +365,13 @@ int icon_grid_rows(const icon_mesh_t *mesh, const icon_feat_t *feat, int prior_t
  * forces the materialising path (rows written by a feature kernel, patched, read back by the MLP kernel) that
  * the other precisions use; both give bit-identical results (tests/test_gpu_parity.py).  Process-wide. */
 int icon_debug_set_unfused(int on);
+/* Diagnostics, host only (no device is touched): the operand image the F16X3 kernels read, packed from a FOLDED network of
+ * input width c0 <= 16.  h_W / h_b: the four layers, [cout][cin] row-major with cin = c0, 512, 256 + c0, 128 + c0.
+ * img: 680 KiB of f16 bit patterns (icon_amd/csrc/mlp_f16x3_device.h: lane maps of the 16x16x32 MFMA), side: 1060 floats
+ * (biases x weight scale | layer 3 per lane group | zeros), inv[3]: accumulator -> activation factors of layers 0..2,
+ * scales[5]: weight scales of layers 0..2 and the activation scales of layers 0, 1 (tests/test_mlp_pack_host.py). */
+int icon_debug_mlp_pack_f16x3(int c0, const float *const *h_W, const float *const *h_b, uint16_t *img, float *side,
+                              float *inv, float *scales);
 /* Diagnostics: host != 0 makes icon_mesh_create* build on the HOST (copy to the host, sequential builder, copy back,
  * synchronises) - the checker of the device build: both emit the same arrays bit for bit.  Process-wide; default device
  * (or ICON_AMD_MESH_BUILD=host in the environment).  icon_debug_mesh_layout: byte offsets of the arena sections

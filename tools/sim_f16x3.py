@@ -83,8 +83,31 @@ def forward(sd, x, use_act_scale):
     h, l = split_w(W2 * s2)
     a2 = mm3(h[:, :256], l[:, :256], bh, bl) + mm3(h[:, 256:], l[:, 256:], xh, xl) + (B[2] * s2)[:, None]
     v2 = leaky(a2, np.float32(1.0) / s2)
-    y = W[3][:, :128] @ v2 + W[3][:, 128:] @ xT + B[3][:, None]
-    return y[0], (np.abs(v0).mean(), np.abs(v1).mean())
+    return layer3(W[3][0], B[3][0], v2, xT), (np.abs(v0).mean(), np.abs(v1).mean())
+
+
+def layer3(w3, b3, v2, xT):
+    """Layer 3 in the kernel's f32 summation order (l3_sum / load_x of mlp_f16x3_device.h).  A point's 128 channels sit in
+    four lane groups g (v_mfma_f32_16x16x32_f16: acc[j] = channel 4g + j of a 16-channel tile): each group runs one fma
+    chain H_g from 0 over its channels 16 m2 + 4g + j (m2 outer, j inner);  H = (H_0 + H_1) + (H_2 + H_3);  the raw inputs
+    8 h + s form two chains T_h from 0 (s ascending), T = T_0 + T_1;  y = (H + T) + b3 - the same for every point of a wave.
+    (The K = 32 sums INSIDE an MFMA are the hardware's; mm3 above models them as numpy's float32 matmul.)"""
+    n = v2.shape[1]
+    c0 = xT.shape[0]
+    part = np.zeros((4, n), np.float32)
+    for g in range(4):
+        for m2 in range(8):
+            for j in range(4):
+                ch = 16 * m2 + 4 * g + j
+                part[g] = np.float32(w3[ch]) * v2[ch] + part[g]          # (an fma on the device: one rounding less)
+    tail = np.zeros((2, n), np.float32)
+    for half in range(2):
+        for s in range(8):
+            k = 8 * half + s
+            if k < c0:
+                tail[half] = np.float32(w3[128 + k]) * xT[k] + tail[half]
+    H = (part[0] + part[1]) + (part[2] + part[3])
+    return (H + (tail[0] + tail[1])) + np.float32(b3)
 
 
 if __name__ == "__main__":
