@@ -11,9 +11,10 @@
 //   sizes      distinct (label, vertex) incidences through the same table (a pinch vertex counts for both sides, as in
 //              trimesh's submeshes); one atomic per wave and label
 //   winner     max of (vertices << 32 | ~label): most vertices, ties to the component holding the lowest-index face
-//   output     order-preserving compaction of the winner's faces and vertices (flags, block counts, scan, scatter), vertex
+//   output     order-preserving compaction of the winner's faces and vertices (flags here, then compact_device.h), vertex
 //              indices renumbered; (vertices, faces) counts through pinned memory - the only synchronisation
-#include "common.h"
+#include "compact_device.h"
+#include "union_find_device.h"
 
 namespace icon {
 
@@ -42,30 +43,6 @@ __device__ __forceinline__ unsigned hash_slot(unsigned long long *keys, unsigned
             if (old == key) { *fresh = false; return s; }
         }
         s = (s + 1) & mask;
-    }
-}
-
-// FRESH: agent-scope loads (the eight XCDs have an L2 each).  The first walk uses ordinary loads - a stale parent is still an
-// ancestor-or-self of what it was, the walk ends at a node that WAS a root, and the CAS below is the judge; after a lost CAS the
-// walk is repeated on fresh values.
-template <bool FRESH>
-__device__ __forceinline__ int uf_find(int *parent, int x)
-{
-    while (true) {
-        const int p = FRESH ? __hip_atomic_load(&parent[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : parent[x];
-        if (p == x) return x;
-        const int gp = FRESH ? __hip_atomic_load(&parent[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : parent[p];
-        if (gp != p) parent[x] = gp;       // path halving: benign race, always an ancestor
-        x = p;
-    }
-}
-__device__ __forceinline__ void uf_unite(int *parent, int u, int v)
-{
-    u = uf_find<false>(parent, u); v = uf_find<false>(parent, v);
-    while (u != v) {
-        const int hi = max(u, v), lo = min(u, v);
-        if (atomicCAS(&parent[hi], hi, lo) == hi) return;       // hooks the larger root under the smaller: a root is the smallest index of its tree
-        u = uf_find<true>(parent, u); v = uf_find<true>(parent, v);
     }
 }
 
@@ -120,15 +97,10 @@ __global__ __launch_bounds__(256) void k_cm_unite(CleanCtx c)
     if (g < f) uf_unite(c.parent, f, g);
 }
 
-// read-only walk to the root, result out of place (a flatten that compresses in place can have its final store overtaken by
-// another thread's path-halving store)
 __global__ __launch_bounds__(256) void k_cm_flatten(CleanCtx c)
 {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= c.F) return;
-    int x = (int)i;
-    while (true) { const int p = c.parent[x]; if (p == x) break; x = p; }
-    c.label[i] = x;
+    if (i < c.F) c.label[i] = uf_root(c.parent, (int)i);
 }
 
 // vertices per component = distinct (label, vertex) incidences.  Round 4 pushed all 3 F incidences through the hash table (287 us
@@ -184,89 +156,21 @@ __global__ __launch_bounds__(256) void k_cm_best(CleanCtx c)
 
 __global__ __launch_bounds__(256) void k_cm_flags(CleanCtx c)
 {
-    __shared__ int ws[4];
     if (c.totals[2]) return;                                     // a face names a missing vertex (uniform): nothing is written
     const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const int win = (int)(0xffffffffu - (unsigned)(*c.best & 0xffffffffull));
     const bool keep = f < c.F && c.label[f] == win;
     if (f < c.F) c.keep_f[f] = keep ? 1 : 0;
     if (keep) { c.keep_v[c.faces[3 * f]] = 1; c.keep_v[c.faces[3 * f + 1]] = 1; c.keep_v[c.faces[3 * f + 2]] = 1; }
-    const unsigned long long b = __ballot(keep);
-    if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = __popcll(b);
-    __syncthreads();
-    if (threadIdx.x == 0) c.blk_f[blockIdx.x] = ws[0] + ws[1] + ws[2] + ws[3];
+    compact_count(keep, c.blk_f);
 }
 
-__global__ __launch_bounds__(256) void k_cm_count_v(CleanCtx c)
-{
-    __shared__ int ws[4];
-    const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const unsigned long long b = __ballot(v < c.V && c.keep_v[v]);
-    if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = __popcll(b);
-    __syncthreads();
-    if (threadIdx.x == 0) c.blk_v[blockIdx.x] = ws[0] + ws[1] + ws[2] + ws[3];
-}
-
-// exclusive scan of the block counts, in place (one workgroup; eight counts per thread and round); block 0: vertices, 1: faces
-__global__ __launch_bounds__(1024) void k_cm_scan(CleanCtx c)
-{
-    __shared__ int wtot[16];
-    int *cnt = blockIdx.x == 0 ? c.blk_v : c.blk_f;
-    const int nb = (int)(((blockIdx.x == 0 ? c.V : c.F) + 255) / 256);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int carry = 0;
-    for (int base = 0; base < nb; base += 8192) {
-        const int i = base + (int)threadIdx.x * 8;
-        int v[8], sum = 0;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) { v[k] = i + k < nb ? cnt[i + k] : 0; sum += v[k]; }
-        int incl = sum;
-        for (int d = 1; d < 64; d <<= 1) { const int up = __shfl_up(incl, d); if (lane >= d) incl += up; }
-        __syncthreads();
-        if (lane == 63) wtot[w] = incl;
-        __syncthreads();
-        int before = 0, all = 0;
-#pragma unroll
-        for (int q = 0; q < 16; ++q) { const int t = wtot[q]; before += q < w ? t : 0; all += t; }
-        int run = carry + before + incl - sum;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) { if (i + k < nb) cnt[i + k] = run; run += v[k]; }
-        carry += all;
-    }
-    if (threadIdx.x == 0) c.totals[blockIdx.x] = carry;
-}
-
-__global__ __launch_bounds__(256) void k_cm_emit_v(CleanCtx c, float *__restrict__ out_verts)
-{
-    __shared__ int ws[4];
-    const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const bool keep = v < c.V && c.keep_v[v];
-    const unsigned long long b = __ballot(keep);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) ws[w] = __popcll(b);
-    __syncthreads();
-    if (!keep) return;
-    int k = c.blk_v[blockIdx.x] + __popcll(b & ((1ull << lane) - 1ull));
-    for (int q = 0; q < w; ++q) k += ws[q];
-    c.remap[v] = k;
-    out_verts[3 * (int64_t)k] = c.verts[3 * v]; out_verts[3 * (int64_t)k + 1] = c.verts[3 * v + 1]; out_verts[3 * (int64_t)k + 2] = c.verts[3 * v + 2];
-}
-
+// the emission of compact_device.h behind clean_mesh's own uniform exit: after a face that names a missing vertex, keep_f was
+// never written and `faces` must not be followed into remap
 __global__ __launch_bounds__(256) void k_cm_emit_f(CleanCtx c, int32_t *__restrict__ out_faces)
 {
-    __shared__ int ws[4];
     if (c.totals[2]) return;
-    const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const bool keep = f < c.F && c.keep_f[f];
-    const unsigned long long b = __ballot(keep);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) ws[w] = __popcll(b);
-    __syncthreads();
-    if (!keep) return;
-    int k = c.blk_f[blockIdx.x] + __popcll(b & ((1ull << lane) - 1ull));
-    for (int q = 0; q < w; ++q) k += ws[q];
-    out_faces[3 * (int64_t)k] = c.remap[c.faces[3 * f]]; out_faces[3 * (int64_t)k + 1] = c.remap[c.faces[3 * f + 1]];
-    out_faces[3 * (int64_t)k + 2] = c.remap[c.faces[3 * f + 2]];
+    compact_emit_faces(c.faces, c.keep_f, c.F, c.blk_f, c.remap, out_faces);
 }
 
 }  // namespace
@@ -338,9 +242,9 @@ extern "C" int icon_clean_mesh(const float *d_verts, int64_t V, const int64_t *d
     hipLaunchKernelGGL(k_cm_sizes, dim3(std::max(g3F, gV)), dim3(256), 0, st, c);
     hipLaunchKernelGGL(k_cm_best, dim3(gF), dim3(256), 0, st, c);
     hipLaunchKernelGGL(k_cm_flags, dim3(gF), dim3(256), 0, st, c);
-    hipLaunchKernelGGL(k_cm_count_v, dim3(gV), dim3(256), 0, st, c);
-    hipLaunchKernelGGL(k_cm_scan, dim3(2), dim3(1024), 0, st, c);
-    hipLaunchKernelGGL(k_cm_emit_v, dim3(gV), dim3(256), 0, st, c, d_out_verts);
+    hipLaunchKernelGGL(k_compact_count_v, dim3(gV), dim3(256), 0, st, c.keep_v, V, c.blk_v);
+    hipLaunchKernelGGL(k_compact_scan<int>, dim3(2), dim3(1024), 0, st, c.blk_v, V, c.blk_f, F, c.totals);
+    hipLaunchKernelGGL(k_compact_emit_v, dim3(gV), dim3(256), 0, st, d_verts, c.keep_v, V, c.blk_v, c.remap, d_out_verts, (int32_t *)nullptr);
     hipLaunchKernelGGL(k_cm_emit_f, dim3(gF), dim3(256), 0, st, c, d_out_faces);
     ICON_HIP(hipGetLastError());
     ICON_HIP(hipMemcpyAsync(s->h_totals, c.totals, 3 * sizeof(int), hipMemcpyDeviceToHost, st));

@@ -10,12 +10,11 @@
 //              widened once; the four waves of the workgroup take a quarter (kSrcSplit) of every tile each, so a 70,000-vertex
 //              mesh is 1,100 workgroups instead of 275; the four (d, j) pairs are combined lexicographically: the lowest index
 //              of the exact minimum, whatever the split.  Workgroups without a selected vertex leave at once.
-//   output     face flags (any corner kept), vertex reference flags, block counts, one scan, order-preserving emission of
-//              vertices, vertex ids and renumbered faces - the pattern of clean_mesh.hip (k_cm_count_v / k_cm_scan / k_cm_emit_*),
-//              copied here with the faces' integer type as a template parameter so that clean_mesh's code object stays as it is
+//   output     face flags (any corner kept) and vertex reference flags here; block counts, one scan, order-preserving emission
+//              of vertices, vertex ids and renumbered faces: compact_device.h, shared with clean_mesh.hip
 // No floating-point atomics, no atomics at all: the flag stores race only with stores of the same value.  Equal bytes from run
 // to run.  Coordinates are taken as finite (the host entry points check what they can see).
-#include "common.h"
+#include "compact_device.h"
 
 namespace icon {
 namespace {
@@ -123,7 +122,6 @@ __device__ __forceinline__ bool gm_keep_v(const GmCtx &c, int64_t v)
 template <class IT>
 __global__ __launch_bounds__(256) void k_gm_flags(GmCtx c)
 {
-    __shared__ int ws[4];
     const IT *faces = static_cast<const IT *>(c.faces);
     const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
     bool keep = false;
@@ -135,84 +133,7 @@ __global__ __launch_bounds__(256) void k_gm_flags(GmCtx c)
         }
         c.keep_f[f] = keep ? 1 : 0;
     }
-    const unsigned long long bal = __ballot(keep);
-    if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = __popcll(bal);
-    __syncthreads();
-    if (threadIdx.x == 0) c.blk_f[blockIdx.x] = ws[0] + ws[1] + ws[2] + ws[3];
-}
-
-__global__ __launch_bounds__(256) void k_gm_count_v(GmCtx c)
-{
-    __shared__ int ws[4];
-    const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const unsigned long long b = __ballot(v < c.V && c.ref_v[v]);
-    if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = __popcll(b);
-    __syncthreads();
-    if (threadIdx.x == 0) c.blk_v[blockIdx.x] = ws[0] + ws[1] + ws[2] + ws[3];
-}
-
-// exclusive scan of the block counts, in place (one workgroup; eight counts per thread and round); block 0: vertices, 1: faces
-__global__ __launch_bounds__(1024) void k_gm_scan(GmCtx c)
-{
-    __shared__ int wtot[16];
-    int *cnt = blockIdx.x == 0 ? c.blk_v : c.blk_f;
-    const int nb = (int)(((blockIdx.x == 0 ? c.V : c.F) + 255) / 256);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int carry = 0;
-    for (int base = 0; base < nb; base += 8192) {
-        const int i = base + (int)threadIdx.x * 8;
-        int v[8], sum = 0;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) { v[k] = i + k < nb ? cnt[i + k] : 0; sum += v[k]; }
-        int incl = sum;
-        for (int d = 1; d < 64; d <<= 1) { const int up = __shfl_up(incl, d); if (lane >= d) incl += up; }
-        __syncthreads();
-        if (lane == 63) wtot[w] = incl;
-        __syncthreads();
-        int before = 0, all = 0;
-#pragma unroll
-        for (int q = 0; q < 16; ++q) { const int t = wtot[q]; before += q < w ? t : 0; all += t; }
-        int run = carry + before + incl - sum;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) { if (i + k < nb) cnt[i + k] = run; run += v[k]; }
-        carry += all;
-    }
-    if (threadIdx.x == 0) c.totals[blockIdx.x] = carry;
-}
-
-__global__ __launch_bounds__(256) void k_gm_emit_v(GmCtx c, float *__restrict__ out_verts, int32_t *__restrict__ out_ids)
-{
-    __shared__ int ws[4];
-    const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const bool keep = v < c.V && c.ref_v[v];
-    const unsigned long long b = __ballot(keep);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) ws[w] = __popcll(b);
-    __syncthreads();
-    if (!keep) return;
-    int k = c.blk_v[blockIdx.x] + __popcll(b & ((1ull << lane) - 1ull));
-    for (int q = 0; q < w; ++q) k += ws[q];
-    c.remap[v] = k;
-    out_verts[3 * (int64_t)k] = c.verts[3 * v]; out_verts[3 * (int64_t)k + 1] = c.verts[3 * v + 1]; out_verts[3 * (int64_t)k + 2] = c.verts[3 * v + 2];
-    out_ids[k] = (int32_t)v;
-}
-
-template <class IT>
-__global__ __launch_bounds__(256) void k_gm_emit_f(GmCtx c, int32_t *__restrict__ out_faces)
-{
-    __shared__ int ws[4];
-    const IT *faces = static_cast<const IT *>(c.faces);
-    const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const bool keep = f < c.F && c.keep_f[f];                                  // a kept face names existing vertices only (k_gm_flags)
-    const unsigned long long b = __ballot(keep);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) ws[w] = __popcll(b);
-    __syncthreads();
-    if (!keep) return;
-    int k = c.blk_f[blockIdx.x] + __popcll(b & ((1ull << lane) - 1ull));
-    for (int q = 0; q < w; ++q) k += ws[q];
-    out_faces[3 * (int64_t)k] = c.remap[faces[3 * f]]; out_faces[3 * (int64_t)k + 1] = c.remap[faces[3 * f + 1]];
-    out_faces[3 * (int64_t)k + 2] = c.remap[faces[3 * f + 2]];
+    compact_count(keep, c.blk_f);                                              // a kept face names existing vertices only
 }
 
 struct GmLayout { size_t totals, ref_v, zero_end, sel, nn, keep_f, blk_f, blk_v, remap, total; };
@@ -298,11 +219,13 @@ extern "C" int icon_extract_cloth(const float *d_verts, int64_t V, const void *d
                            (const uint8_t *)c.sel, c.nn);
     if (faces_int64) hipLaunchKernelGGL(k_gm_flags<int64_t>, dim3(gF), dim3(256), 0, st, c);
     else hipLaunchKernelGGL(k_gm_flags<int32_t>, dim3(gF), dim3(256), 0, st, c);
-    hipLaunchKernelGGL(k_gm_count_v, dim3(gV), dim3(256), 0, st, c);
-    hipLaunchKernelGGL(k_gm_scan, dim3(2), dim3(1024), 0, st, c);
-    hipLaunchKernelGGL(k_gm_emit_v, dim3(gV), dim3(256), 0, st, c, d_out_verts, d_out_vert_ids);
-    if (faces_int64) hipLaunchKernelGGL(k_gm_emit_f<int64_t>, dim3(gF), dim3(256), 0, st, c, d_out_faces);
-    else hipLaunchKernelGGL(k_gm_emit_f<int32_t>, dim3(gF), dim3(256), 0, st, c, d_out_faces);
+    hipLaunchKernelGGL(k_compact_count_v, dim3(gV), dim3(256), 0, st, c.ref_v, V, c.blk_v);
+    hipLaunchKernelGGL(k_compact_scan<int64_t>, dim3(2), dim3(1024), 0, st, c.blk_v, V, c.blk_f, F, c.totals);
+    hipLaunchKernelGGL(k_compact_emit_v, dim3(gV), dim3(256), 0, st, d_verts, c.ref_v, V, c.blk_v, c.remap, d_out_verts, d_out_vert_ids);
+    if (faces_int64)
+        hipLaunchKernelGGL(k_compact_emit_f<int64_t>, dim3(gF), dim3(256), 0, st, static_cast<const int64_t *>(d_faces), c.keep_f, F, c.blk_f, c.remap, d_out_faces);
+    else
+        hipLaunchKernelGGL(k_compact_emit_f<int32_t>, dim3(gF), dim3(256), 0, st, static_cast<const int32_t *>(d_faces), c.keep_f, F, c.blk_f, c.remap, d_out_faces);
     ICON_HIP(hipGetLastError());
     ICON_HIP(hipMemcpyAsync(h_counts, c.totals, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, st));
     ICON_HIP(hipStreamSynchronize(st));

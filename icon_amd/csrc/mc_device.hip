@@ -14,7 +14,7 @@
 //                   in one 64-bit word (1024 points per block); k_mc_vertices also writes the
 //                   interpolated vertices and each point's first vertex index
 //   k_mc_faces    : per cube - triangles with vertex ids looked up through the first-index array
-#include "common.h"
+#include "scan_device.h"
 
 #include <cstdlib>
 #include <cstring>
@@ -66,8 +66,6 @@ __device__ __forceinline__ float mc_lerp(float level, float v0, float v1)
 }
 
 // flags: bit0/1/2 = +x/+y/+z edge crossed, bit3 = inside
-__device__ __forceinline__ unsigned long long mc_block_exscan(unsigned long long v, unsigned long long *wsum, unsigned long long *total);
-
 // also: block_tot[block] = (triangles << 32 | vertices) of the block's cells - the blocks away from the surface (99 % of them)
 // are skipped by the emit passes on that one word
 // [zc0, zc1): the cell layers this call triangulates (the whole cube: 0, res - 1).  A Z-slab rank of the sharded driver owns a
@@ -191,25 +189,6 @@ __device__ __forceinline__ unsigned long long mc_count(const uint8_t *flags, con
     return (unsigned long long)__popc(flags[i] & 7) | ((unsigned long long)ntri[i] << 32);
 }
 
-// block-wide exclusive scan of one 64-bit value per thread (two independent 32-bit sums packed)
-__device__ __forceinline__ unsigned long long mc_block_exscan(unsigned long long v, unsigned long long *wsum /* LDS [16] */,
-                                                              unsigned long long *total)
-{
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    unsigned long long inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned long long o = __shfl_up(inc, d);
-        if (lane >= d) inc += o;
-    }
-    if (lane == 63) wsum[w] = inc;
-    __syncthreads();
-    unsigned long long before = 0, all = 0;
-    for (int k = 0; k < kMcBlock / 64; ++k) { const unsigned long long s = wsum[k]; if (k < w) before += s; all += s; }
-    if (total) *total = all;
-    return before + inc - v;
-}
-
 // exclusive scan of the block totals (66,000 for a 257^3 volume) into offsets: one workgroup, eight consecutive entries per
 // thread and round - coalesced (a contiguous range per thread was a 41 us pass of strided loads)
 // ... and the list of the blocks that hold anything (any order): the emit passes are launched over those only (600 of 66,000
@@ -220,26 +199,18 @@ __global__ __launch_bounds__(1024) void k_mc_scanblocks(const unsigned long long
     __shared__ unsigned long long wtot[16];
     __shared__ int n_active;
     if (threadIdx.x == 0) n_active = 0;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     unsigned long long carry = 0;
     for (int64_t base = 0; base < nblocks; base += 8192) {
+        __syncthreads();                                        // (the previous round's wtot has been read; n_active is reset)
         const int64_t i = base + (int64_t)threadIdx.x * 8;
-        unsigned long long v[8], sum = 0;
+        unsigned long long v[8], sum = 0, all;
 #pragma unroll
         for (int k = 0; k < 8; ++k) { v[k] = i + k < nblocks ? block_tot[i + k] : 0ull; sum += v[k]; }
-        unsigned long long incl = sum;
-        for (int d = 1; d < 64; d <<= 1) { const unsigned long long up = __shfl_up(incl, d); if (lane >= d) incl += up; }
-        __syncthreads();
-        if (lane == 63) wtot[w] = incl;
-        __syncthreads();
-        unsigned long long before = 0, all = 0;
-#pragma unroll
-        for (int q = 0; q < 16; ++q) { const unsigned long long t = wtot[q]; before += q < w ? t : 0ull; all += t; }
-        unsigned long long run = carry + before + incl - sum;
+        unsigned long long run = block_excl_scan<16>(sum, wtot, all);       // inside this round; carry: the rounds before
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
-            if (i + k < nblocks) block_off[i + k] = run;
-            if (v[k]) active[atomicAdd(&n_active, 1)] = (int32_t)(i + k);     // (LDS counter; the first __syncthreads of the round ordered its reset)
+            if (i + k < nblocks) block_off[i + k] = carry + run;
+            if (v[k]) active[atomicAdd(&n_active, 1)] = (int32_t)(i + k);
             run += v[k];
         }
         carry += all;
@@ -258,21 +229,8 @@ __global__ __launch_bounds__(1024) void k_mc_scan_local(const unsigned long long
 {
     __shared__ unsigned long long wtot[16];
     if (blockIdx.x == 0 && threadIdx.x == 0) totals[2] = 0ull;   // the active-list counter of k_mc_scan_apply
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int64_t i = (int64_t)blockIdx.x * kMcChunk + (int64_t)threadIdx.x * 8;
-    unsigned long long v[8], sum = 0;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) { v[k] = i + k < nblocks ? block_tot[i + k] : 0ull; sum += v[k]; }
-    unsigned long long incl = sum;
-    for (int d = 1; d < 64; d <<= 1) { const unsigned long long up = __shfl_up(incl, d); if (lane >= d) incl += up; }
-    if (lane == 63) wtot[w] = incl;
-    __syncthreads();
-    unsigned long long before = 0, all = 0;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) { const unsigned long long t = wtot[q]; before += q < w ? t : 0ull; all += t; }
-    unsigned long long run = before + incl - sum;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) { if (i + k < nblocks) block_off[i + k] = run; run += v[k]; }
+    const unsigned long long all = block_scan_tile<16, 8>(block_tot, block_off, i, nblocks, 0ull, wtot);
     if (threadIdx.x == 0) chunk_tot[blockIdx.x] = all;
 }
 __global__ __launch_bounds__(1024) void k_mc_scan_apply(const unsigned long long *__restrict__ block_tot, unsigned long long *__restrict__ block_off,
@@ -313,7 +271,8 @@ __global__ __launch_bounds__(kMcBlock) void k_mc_vertices(const float *__restric
     const int n = res - 1;
     const int64_t i = blk * kMcBlock + threadIdx.x;
     const unsigned long long own = mc_count(flags, ntri, i, npts);
-    const unsigned long long ex = mc_block_exscan(own, wsum, nullptr) + block_offsets[blk];
+    unsigned long long all;
+    const unsigned long long ex = block_excl_scan<kMcBlock / 64>(own, wsum, all) + block_offsets[blk];
     if (i >= npts || own == 0ull) return;                        // first_vertex is read for vertex owners, first_tri for cells with triangles
     const int32_t v0 = (int32_t)(ex & 0xffffffffull);
     first_vertex[i] = v0;

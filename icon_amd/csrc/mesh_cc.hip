@@ -2,35 +2,13 @@
 // (lib/dataset/mesh_util.py:778-791: trimesh split -> keep the component with the most vertices,
 // called at apps/ICON.py:755-756 on the marching-cubes output).
 //
-// Lock-free union-find over the vertices: every face unites its three corners (atomicCAS hooks the larger
-// root under the smaller one, path halving on the way), a second pass flattens; the label of a vertex is
-// the smallest vertex index of its component.  A 257^3 body surface (~70k vertices / 140k faces) takes a
-// few tens of microseconds; the selection / compaction of the winning component is plumbing on the host
+// Lock-free union-find over the vertices (union_find_device.h): every face unites its three corners, a
+// second pass flattens; the label of a vertex is the smallest vertex index of its component.  A 257^3
+// body surface (~70k vertices / 140k faces) takes a few tens of microseconds; the selection / compaction of the winning component is plumbing on the host
 // layer (icon_amd/recon.py: clean_mesh).
-#include "common.h"
+#include "union_find_device.h"
 
 namespace icon {
-
-__device__ __forceinline__ int cc_find(int *parent, int x)
-{
-    while (true) {
-        const int p = parent[x];
-        if (p == x) return x;
-        const int gp = parent[p];
-        if (gp != p) parent[x] = gp;       // path halving: benign race, always an ancestor
-        x = p;
-    }
-}
-
-__device__ __forceinline__ void cc_unite(int *parent, int u, int v)
-{
-    while (true) {
-        u = cc_find(parent, u); v = cc_find(parent, v);
-        if (u == v) return;
-        const int hi = max(u, v), lo = min(u, v);
-        if (atomicCAS(&parent[hi], hi, lo) == hi) return;
-    }
-}
 
 __global__ void k_cc_init(int *parent, int64_t V)
 {
@@ -44,19 +22,14 @@ __global__ void k_cc_union(const int64_t *__restrict__ faces, int64_t F, int64_t
     if (f >= F) return;
     const int64_t a = faces[3 * f], b = faces[3 * f + 1], c = faces[3 * f + 2];
     if (a < 0 || b < 0 || c < 0 || a >= V || b >= V || c >= V) { *bad = 1; return; }
-    cc_unite(parent, (int)a, (int)b);
-    cc_unite(parent, (int)a, (int)c);
+    uf_unite(parent, (int)a, (int)b);
+    uf_unite(parent, (int)a, (int)c);
 }
 
-// read-only walk to the root, result out of place: a flatten that compresses in place can have its final
-// store parent[i] = root overtaken by another thread's path-halving store parent[i] = grandparent
 __global__ void k_cc_flatten(const int *__restrict__ parent, int *__restrict__ labels, int64_t V)
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= V) return;
-    int x = (int)i;
-    while (true) { const int p = parent[x]; if (p == x) break; x = p; }
-    labels[i] = x;
+    if (i < V) labels[i] = uf_root(parent, (int)i);
 }
 
 }  // namespace icon

@@ -28,7 +28,7 @@
 //   k_scan_cells, k_bin_fill, k_bin_sort   CSR ray bins (lists ascending, as a sequential fill would leave them)
 #pragma clang fp contract(off)
 
-#include "common.h"
+#include "scan_device.h"
 #include "mesh_rules.h"
 
 #include <cstring>
@@ -757,23 +757,14 @@ __global__ __launch_bounds__(1024) void k_scan_cells(BuildCtx c)
     __shared__ int wtot[16];
     const BinGrid g = grid_of(c);
     const int n = g.gy * g.gz;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     int64_t carry = 0;
     for (int base = 0; base < n; base += 4096) {
         const int i = base + (int)threadIdx.x * 4;
-        int v[4];
+        int v[4], all;
 #pragma unroll
         for (int k = 0; k < 4; ++k) v[k] = (i + k < n) ? c.cell_count[i + k] : 0;
-        const int mine = v[0] + v[1] + v[2] + v[3];
-        int incl = mine;
-        for (int d = 1; d < 64; d <<= 1) { const int up = __shfl_up(incl, d); if (lane >= d) incl += up; }
         __syncthreads();                                       // (the previous tile's wtot has been read)
-        if (lane == 63) wtot[w] = incl;
-        __syncthreads();
-        int before = 0, all = 0;
-#pragma unroll
-        for (int q = 0; q < 16; ++q) { const int t = wtot[q]; before += q < w ? t : 0; all += t; }
-        int64_t run = carry + before + incl - mine;
+        int64_t run = carry + block_excl_scan<16>(v[0] + v[1] + v[2] + v[3], wtot, all);
 #pragma unroll
         for (int k = 0; k < 4; ++k) { if (i + k < n) c.bin_start[i + k] = (int32_t)run; run += v[k]; }
         carry += all;

@@ -13,6 +13,7 @@
 #pragma clang fp contract(off)
 
 #include "query_device.h"
+#include "scan_device.h"
 
 namespace icon {
 
@@ -276,27 +277,9 @@ __global__ __launch_bounds__(kBlock) void k_row_crossings_wide(MeshDev m, Lattic
 
 // Exclusive scan of the per-tile outlier counts (66,308 entries for a 257^3 call; int64 offsets: a 513^3
 // lattice has 1.35e8 points) in two coalesced passes: k_scan_local scans 1,024 consecutive counts per
-// workgroup (wave shuffles + one LDS hop) and records the chunk total, k_scan_apply adds the sum of the
+// workgroup (scan_device.h: wave shuffles + one LDS hop) and records the chunk total, k_scan_apply adds the sum of the
 // preceding chunk totals.  (A single workgroup walking 65 strided entries per thread was latency-bound:
 // 0.12 ms - more than k_sign, the count and the compaction together.)
-__device__ __forceinline__ int64_t block_exclusive_scan_1024(int64_t v, int64_t *wtot /* LDS [16] */, int64_t *block_total)
-{
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int64_t incl = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int64_t up = __shfl_up(incl, d);
-        if (lane >= d) incl += up;
-    }
-    if (lane == 63) wtot[w] = incl;
-    __syncthreads();
-    int64_t base = 0, all = 0;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) { const int64_t t = wtot[k]; if (k < w) base += t; all += t; }
-    *block_total = all;
-    return base + incl - v;
-}
-
 // n_points_dev (adaptive levels): the call's size lives on the device - n = its number of 256-point blocks
 __global__ __launch_bounds__(1024) void k_scan_local(const int32_t *__restrict__ counts, int64_t n, int32_t *__restrict__ local, int64_t *__restrict__ part,
                                                      const int *__restrict__ n_points_dev)
@@ -306,7 +289,7 @@ __global__ __launch_bounds__(1024) void k_scan_local(const int32_t *__restrict__
     const int64_t i = (int64_t)blockIdx.x * 1024 + threadIdx.x;
     const int64_t v = (i < n) ? counts[i] : 0;
     int64_t total;
-    const int64_t ex = block_exclusive_scan_1024(v, wtot, &total);
+    const int64_t ex = block_excl_scan<16>(v, wtot, total);
     if (i < n) local[i] = (int32_t)ex;
     if (threadIdx.x == 0) part[blockIdx.x] = total;
 }
@@ -320,9 +303,9 @@ __global__ __launch_bounds__(1024) void k_scan_apply(const int32_t *__restrict__
     int64_t before = 0, all = 0;
     for (int64_t k = threadIdx.x; k < nchunks; k += 1024) { const int64_t t = part[k]; all += t; if (k < blockIdx.x) before += t; }
     int64_t sum_all, sum_before;
-    (void)block_exclusive_scan_1024(all, wtot, &sum_all);
+    (void)block_excl_scan<16>(all, wtot, sum_all);
     __syncthreads();
-    (void)block_exclusive_scan_1024(before, wtot, &sum_before);
+    (void)block_excl_scan<16>(before, wtot, sum_before);
     const int64_t i = (int64_t)blockIdx.x * 1024 + threadIdx.x;
     if (i < n) offsets[i] = sum_before + local[i];
     if (blockIdx.x == 0 && threadIdx.x == 0) *total = sum_all;

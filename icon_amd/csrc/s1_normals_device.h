@@ -12,7 +12,7 @@
 #pragma once
 #pragma clang fp contract(off)
 
-#include "common.h"
+#include "scan_device.h"
 
 namespace icon {
 namespace {
@@ -91,38 +91,10 @@ __global__ __launch_bounds__(256) void k_s1_count(S1Ctx c)
         if (s1_wanted(c, v[k])) atomicAdd(&c.deg[v[k]], 1);
 }
 
-__device__ __forceinline__ int wave_incl_scan(int v)
-{
-    const int lane = threadIdx.x & 63;
-    for (int d = 1; d < 64; d <<= 1) { const int o = __shfl_up(v, d); if (lane >= d) v += o; }
-    return v;
-}
-// exclusive prefix of v over the workgroup (NW wavefronts); total: the workgroup's sum
-template <int NW>
-__device__ __forceinline__ int block_excl_scan(int v, int *s_w, int &total)
-{
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int incl = wave_incl_scan(v);
-    if (lane == 63) s_w[w] = incl;
-    __syncthreads();
-    int before = 0, all = 0;
-    for (int q = 0; q < NW; ++q) { const int t = s_w[q]; before += q < w ? t : 0; all += t; }
-    __syncthreads();
-    total = all;
-    return before + incl - v;
-}
-
 __global__ __launch_bounds__(256) void k_s1_scan_blocks(S1Ctx c)
 {
     __shared__ int s_w[4];
-    const int64_t i0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
-    int d[4], sum = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) { d[k] = i0 + k < c.V ? c.deg[i0 + k] : 0; sum += d[k]; }
-    int total;
-    int run = block_excl_scan<4>(sum, s_w, total);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) { if (i0 + k < c.V) c.loc[i0 + k] = run; run += d[k]; }
+    const int total = block_scan_tile<4, 4>(c.deg, c.loc, ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4, c.V, 0, s_w);
     if (threadIdx.x == 0) c.part[blockIdx.x] = total;
 }
 
@@ -134,6 +106,7 @@ __global__ __launch_bounds__(1024) void k_s1_scan_parts(S1Ctx c, int nb)
         const int i = base + threadIdx.x;
         const int v = i < nb ? c.part[i] : 0;
         int total;
+        __syncthreads();                                        // (the previous round's s_w has been read)
         const int ex = block_excl_scan<16>(v, s_w, total);
         if (i < nb) c.part[i] = carry + ex;
         carry += total;

@@ -30,6 +30,9 @@ from ._lib import IconAmdError, check
 
 # csrc/garment.hip: kPolyTile, kSrcTile, kSrcSplit - the sizes at which the kernels take another path (tests pick shapes around them)
 POLY_TILE, SRC_TILE, SRC_SPLIT = 256, 512, 128
+# csrc/compact_device.h: kCompactRound * kCompactBlock - the vertices or faces above which the scan of the block counts carries a
+# total into another round
+SCAN_ROUND = 8192 * 256
 
 # lib/common/cloth_extraction.py:117-133 ('rightHand' is listed twice there)
 _BASE_PARTS = ["rightHand", "leftToeBase", "leftFoot", "rightFoot", "head", "leftHandIndex1", "rightHandIndex1", "rightToeBase",

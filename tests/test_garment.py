@@ -329,3 +329,5 @@ def test_tile_constants_agree():
     src = open(os.path.join(ROOT, "icon_amd", "csrc", "garment.hip")).read()
     assert f"constexpr int kPolyTile = {gm.POLY_TILE};" in src and f"constexpr int kSrcTile = {gm.SRC_TILE};" in src
     assert "constexpr int kSrcSplit = kSrcTile / 4;" in src and gm.SRC_SPLIT * 4 == gm.SRC_TILE
+    src = open(os.path.join(ROOT, "icon_amd", "csrc", "compact_device.h")).read()
+    assert "constexpr int kCompactBlock = 256;" in src and "constexpr int kCompactRound = 8192;" in src and gm.SCAN_ROUND == 8192 * 256

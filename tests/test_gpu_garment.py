@@ -124,6 +124,19 @@ def test_vertex_and_face_counts(V, F):
     _check(verts, faces, polys, src, rem, dtype=torch.int64 if (V + F) % 2 else torch.int32, view=F != 257)
 
 
+def test_both_scans_enter_a_second_round():
+    """V = F = SCAN_ROUND + 300: the one-workgroup scan of the block counts takes 8,192 counts of 256 entries per round, so the
+    vertices' scan and the faces' scan both carry a total into a second round.  Kept vertices and kept faces lie on both sides of
+    entry SCAN_ROUND (the oracle's side): without them the carry would be added to nothing"""
+    from icon_amd.garment import SCAN_ROUND as R
+    rng = np.random.RandomState(7)
+    verts = gc.cloud(rng, R + 300)
+    faces = gc.faces_covering(rng, R + 300, R + 300)
+    o = _check(verts, faces, [TRIANGLE])
+    for kept in (o["vert_ids"], np.nonzero(o["keep_f"])[0]):
+        assert (kept < R).any() and (kept >= R).any()
+
+
 def test_single_vertex():
     """V = 1 cannot meet the 5 % - 95 % condition: the vertex inside (kept / removed by its label) and outside"""
     src = np.array([[0.0, 0.0, 0.0], [2.0, 2.0, 0.0]], np.float32)

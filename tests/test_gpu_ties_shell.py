@@ -331,6 +331,22 @@ def test_clean_mesh_native_vs_plain_python_checker(case):
         clean_mesh(T(v), T(fb))
 
 
+def test_clean_mesh_vertex_scan_enters_a_second_round():
+    """V = SCAN_ROUND + 300 vertices, nearly all unreferenced: the scan of the vertices' block counts (8,192 counts of 256 entries
+    per round) carries a total into a second round.  A tetrahedron on vertices on both sides of entry SCAN_ROUND beats a lone
+    triangle; the result is stated by construction.  No case with F above SCAN_ROUND: the faces' scan is the same code, and
+    tests/test_gpu_garment.py: test_both_scans_enter_a_second_round drives it into its second round"""
+    from icon_amd.garment import SCAN_ROUND as R
+    from icon_amd.recon import clean_mesh
+    v = np.random.RandomState(5).rand(R + 300, 3).astype(np.float32)
+    tet = np.array([7, R - 1, R, R + 299])
+    local = np.array([[0, 1, 2], [0, 1, 3], [0, 2, 3], [1, 2, 3]], np.int64)
+    f = np.concatenate([tet[local], [[100, R + 5, 5000]]])
+    cv, cf = clean_mesh(T(v), T(f))
+    assert cv.dtype == torch.float32 and cf.dtype == torch.int32
+    assert np.array_equal(cv.cpu().numpy(), v[tet]) and np.array_equal(cf.cpu().numpy(), local)
+
+
 # ---------------------------------------------------------------------------------------------
 # attach(): the HIP path behind a network object carrying exactly what the reference's HGPIFuNet carries
 # ---------------------------------------------------------------------------------------------
