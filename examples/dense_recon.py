@@ -29,6 +29,8 @@ def main():
                     "reference's turntable video; icon_amd.render) and write every 30th frame as DIR/turntable_<angle>.png")
     ap.add_argument("--garment", metavar="OUT.obj", default=None, help="cut a garment out of the cleaned mesh (extract_cloth, apps/infer.py:565-605; "
                     "icon_amd.garment): a fixed torso-shaped polygon, the synthetic body as the SMPL mesh with its parts split by height")
+    ap.add_argument("--metrics", action="store_true", help="Chamfer, P2S and normal consistency of the dense lattice's mesh against the coarse-to-fine "
+                    "schedule's (icon_amd.evaluator: the three metrics of `python -m apps.train -test`, lib/dataset/Evaluator.py)")
     args = ap.parse_args()
     import torch
     from icon_amd import synth
@@ -119,6 +121,25 @@ def main():
         else:
             Garment(*(x.cpu().numpy() for x in out)).export(args.garment)
             print(f"garment: {out[0].shape[0]} vertices, {out[1].shape[0]} faces of {verts.shape[0]} / {faces.shape[0]} in {ms:.2f} ms; wrote {args.garment}")
+    if args.metrics:
+        from icon_amd.evaluator import EvalMesh, Evaluator
+        other_cls = DenseReconEngine if args.adaptive else AdaptiveReconEngine
+        other = other_cls(query_func=query_func, b_min=[[-1.0, 1.0, -1.0]], b_max=[[1.0, -1.0, 1.0]], resolutions=levels, align_corners=True,
+                          balance_value=0.5, faster=True).to(dev)
+        ov, of = clean_mesh(*other.export_mesh(other(opt=opt, netG=eng, features=features, proj_matrix=None)))
+        ov = (ov.float() - half) / half
+        meshes = [EvalMesh(verts.to(dev), faces.to(dev)), EvalMesh(ov.to(dev), of.to(dev))]
+        dense, sched = meshes[::-1] if args.adaptive else meshes
+        ev = Evaluator(dev)
+        ev.set_mesh({}, scale_factor=1.0)
+        ev.src_mesh, ev.tgt_mesh = dense, sched                                  # both are in the [-1,1] cube already: no space_transfer
+        ev.calculate_normal_consist()                                           # warm-up: the call's scratch
+        t8 = sync()
+        nc = ev.calculate_normal_consist()                                      # one native call, four 512^2 views of both meshes
+        nc_ms = 1e3 * (sync() - t8)
+        chamfer, p2s = ev.calculate_chamfer_p2s()
+        print(f"metrics, dense ({dense.vertices.shape[0]} vertices) against the schedule's mesh ({sched.vertices.shape[0]}): chamfer {chamfer:.4f}, "
+              f"p2s {p2s:.4f}, normal consistency {nc:.6f} ({nc_ms:.2f} ms)")
     if args.out:
         v, f = verts.cpu().numpy(), faces.cpu().numpy() + 1
         with open(args.out, "w") as fh:

@@ -45,6 +45,7 @@ SYMBOLS = [
     "icon_mesh_priors_bytes", "icon_mesh_priors_forward", "icon_mesh_priors_backward",
     "icon_smpl_bytes", "icon_smpl_forward", "icon_smpl_backward",
     "icon_nearest_vertex", "icon_extract_cloth_bytes", "icon_extract_cloth",
+    "icon_normal_consistency_bytes", "icon_normal_consistency",
 ]
 
 _lib = None

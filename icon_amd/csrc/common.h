@@ -412,6 +412,7 @@ int work_check_err(icon_work *w);
 extern int g_qc_lanes;                // query_color.hip: lanes per face of the colour call's rasteriser ("qc_lanes"; 0 = default)
 extern int g_rn_lanes;                // render_normal.hip: lanes per face of the renderer's rasteriser ("rn_lanes"; 0 = default)
 extern int g_tt_chunk;                // turntable.hip: views per chunk of the turntable call ("tt_chunk"; 0 = default)
+extern int g_ev_lanes;                // evaluator.hip: lanes per face of the evaluator's rasteriser ("ev_lanes"; 0 = default)
 // the process-wide test / A-B switches (query_kernels.hip: the table with their keys, environment variables and defaults)
 enum Opt { kOptPairBox, kOptNodeBox, kOptBoxClamp, kOptLatticeFast, kOptUnfused, kOptShellSkip, kOptShareWaves, kOptShareRing, kOptShareLose,
            kOptShareSpinLog2, kOptCount };

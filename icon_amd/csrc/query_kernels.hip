@@ -1513,6 +1513,7 @@ extern "C" int icon_debug_set_option(const char *key, int value)
     if (k == "qc_lanes") { ICON_ARG(value == 0 || value == 64, "qc_lanes: 0 (default) or 64"); g_qc_lanes = value; }
     else if (k == "rn_lanes") { ICON_ARG(value == 0 || value == 1 || value == 8, "rn_lanes: 0 (default), 1 or 8"); g_rn_lanes = value; }
     else if (k == "tt_chunk") { ICON_ARG(value >= 0 && value <= 32, "tt_chunk: 0 (default) or 1..32"); g_tt_chunk = value; }
+    else if (k == "ev_lanes") { ICON_ARG(value == 0 || value == 1 || value == 8, "ev_lanes: 0 (default), 1 or 8"); g_ev_lanes = value; }
     else return fail(ICON_ERR_ARG, "icon_debug_set_option: unknown key " + k);
     return ICON_OK;
 }

@@ -225,11 +225,12 @@ __global__ __launch_bounds__(64) void k_s1_normals_long(S1Ctx c, Store store)
 
 // ---- ordered sums of OTHER per-corner terms over the same lists (silhouette.hip: the per-corner gradients of a face) ----
 // Term: a trivially copyable functor; term(pass, key, out) gives the three addends of incidence key `key` in pass `pass` (it checks
-// the key's range itself).  The passes are added one after the other, each in ascending key order, into one sum.
-template <class Term>
-__device__ __forceinline__ void s1_sum_short_terms(const S1Ctx &c, int64_t v, int n, int passes, const Term &term, float s[3])
+// the key's range itself).  The passes are added one after the other, each in ascending key order, into one sum.  T: the type the
+// terms come in and are added in - float, or double (evaluator.hip's angle-weighted normals)
+template <class Term, class T = float>
+__device__ __forceinline__ void s1_sum_short_terms(const S1Ctx &c, int64_t v, int n, int passes, const Term &term, T s[3])
 {
-    s[0] = s[1] = s[2] = 0.0f;
+    s[0] = s[1] = s[2] = T(0);
     const int64_t st = s1_start(c, v);
     if (n < 0 || st < 0 || st + n > 3 * c.F) return;
     const int *list = c.inc + st;
@@ -238,7 +239,7 @@ __device__ __forceinline__ void s1_sum_short_terms(const S1Ctx &c, int64_t v, in
         for (int step = 0; step < n; ++step) {
             int best = 0x7fffffff;
             for (int q = 0; q < n; ++q) { const int k = list[q]; if (k > last && k < best) best = k; }
-            float a[3];
+            T a[3];
             term(p, best, a);
             s[0] += a[0]; s[1] += a[1]; s[2] += a[2];
             last = best;
@@ -247,7 +248,7 @@ __device__ __forceinline__ void s1_sum_short_terms(const S1Ctx &c, int64_t v, in
 }
 
 // the long lists of such a sum: k_s1_normals_long's rank sort, then the terms of every pass in that order; lane 0 calls store(v, sx, sy, sz)
-template <class Term, class Store>
+template <class Term, class Store, class T = float>
 __global__ __launch_bounds__(64) void k_s1_sum_long(S1Ctx c, int passes, Term term, Store store)
 {
     const int nl = (int)min((int64_t)*c.n_long, c.V);
@@ -265,11 +266,11 @@ __global__ __launch_bounds__(64) void k_s1_sum_long(S1Ctx c, int passes, Term te
             c.tmp[st + rank] = key;
         }
         __threadfence();                                                   // the wave's own stores, read back by other lanes below
-        float sx = 0.0f, sy = 0.0f, sz = 0.0f;
+        T sx = T(0), sy = T(0), sz = T(0);
         for (int p = 0; p < passes; ++p)
             for (int base = 0; base < n; base += 64) {
                 const int i = base + lane;
-                float a[3] = { 0.0f, 0.0f, 0.0f };
+                T a[3] = { T(0), T(0), T(0) };
                 if (i < n) term(p, __hip_atomic_load(&c.tmp[st + i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), a);
                 const int cnt = min(64, n - base);
                 for (int l = 0; l < cnt; ++l) { sx += __shfl(a[0], l); sy += __shfl(a[1], l); sz += __shfl(a[2], l); }

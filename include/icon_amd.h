@@ -741,6 +741,35 @@ int icon_extract_cloth(const float *d_verts, int64_t V, const void *d_faces, int
                        float *d_out_verts, int32_t *d_out_faces, int32_t *d_out_vert_ids, int64_t *h_counts,
                        void *d_scratch, int64_t scratch_bytes, void *stream);
 
+/* ---- the evaluator's normal maps and normal consistency ------------------------------------------------------
+ * replaces Evaluator._render_normal / _get_reproj_normal_error / calculate_normal_consist / render_normal
+ * (lib/dataset/Evaluator.py:58-177; an OpenGL renderer and trimesh's vertex_normals; call sites apps/ICON.py:556 and :639).
+ * The rule is DESIGN.md 4.20 (PARITY UNPINNED): coverage at the pixel centres in exact integers on vertices snapped to 1/256
+ * pixel, the top-left fill rule, near / far clipping at clip z = -1 / +1, the smallest (z, face id) wins, the interpolated
+ * camera normal normalised per fragment, background (1, 1, 1, 0); a face with a |clip x| or |clip y| above 64 is not drawn.
+ * Mesh a, and optionally mesh b (all of d_verts_b, d_faces_b, Vb, Fb null / 0: the single-mesh form, which only renders -
+ * d_err, d_normals_b, d_rgba_b and d_pix_b must be null then): d_verts [V,3] f32; d_faces [F,3], int64 when faces_int64 != 0,
+ * else int32 - read in place, a face that names a missing vertex is skipped; d_normals [V,3] f32 vertex normals, or NULL: the
+ * call computes angle-weighted ones in float64 (trimesh's vertex_normals restated, rounded once to float32).
+ * Views: d_view_mats [n_views,3,4] f32 - the affine model matrix of each view, row-major; d_view_muls [n_views,3] f32 - what
+ * the camera normal's components are multiplied by.  DEVICE pointers, 1 <= n_views <= 32; 8 <= size <= 2048.
+ * Outputs: d_err [n_views] float64 - per view the mean over the size^2 pixels of the squared RGB difference of the two meshes'
+ * maps, each pixel's in float32, summed in float64 in a fixed tree; d_rgba_a / d_rgba_b [n_views,size,size,4] f32, 16-byte aligned, and
+ * d_pix_a / d_pix_b [n_views,size,size] int32 (the winning face, -1: background): each written only when not NULL;
+ * d_normals_out_a / d_normals_out_b [V,3] f32: where the call computes a mesh's vertex normals and this is not NULL, they are
+ * left here (a mesh's normals are given or asked for, not both).
+ * d_scratch: device memory of at least icon_normal_consistency_bytes bytes (same sizes), 256-byte aligned, owned by the caller;
+ * its contents need not survive between calls.  Enqueued on `stream`, launches only (at most 19 whatever the sizes): no
+ * allocation, no synchronisation, nothing read back; no floating-point atomics: equal bytes from run to run and from int32
+ * and int64 faces. */
+int icon_normal_consistency_bytes(int64_t Va, int64_t Fa, int64_t Vb, int64_t Fb, int size, int n_views, int64_t *bytes);
+int icon_normal_consistency(const float *d_verts_a, int64_t Va, const void *d_faces_a, int64_t Fa, int faces_a_int64,
+                            const float *d_normals_a, const float *d_verts_b, int64_t Vb, const void *d_faces_b, int64_t Fb,
+                            int faces_b_int64, const float *d_normals_b, const float *d_view_mats, const float *d_view_muls,
+                            int n_views, int size, double *d_err, float *d_rgba_a, float *d_rgba_b, int32_t *d_pix_a,
+                            int32_t *d_pix_b, float *d_normals_out_a, float *d_normals_out_b, void *d_scratch,
+                            int64_t scratch_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,6 +15,9 @@ exactly as the reference's call site does, and print one PASS / DIFF line with t
   trimesh split (clean_mesh)                      lib/dataset/mesh_util.py:783          f1
   pytorch3d rasterize_meshes (get_visibility)     lib/dataset/mesh_util.py:298          f3
   voxelize_cuda forward_semantic_voxelization     lib/net/voxelize.py:57                a16 / f4
+  trimesh vertex_normals + the OpenGL NormalRender  lib/dataset/Evaluator.py:58-73        DESIGN.md 4.20 (--only evaluator)
+(the last row is SILENT in the default run where trimesh is absent - trimesh's own ABSENT line covers it; asked for by name,
+--only evaluator, it reports for itself: ABSENT here)
 
 --stand-ins runs every section with the repo's own CPU checkers (oracle/) in the packages' place: a self-test of this harness
 (everything must PASS; needs the HIP device, nothing else).  Exit code: 0 unless --strict and a DIFF was printed."""
@@ -348,6 +351,30 @@ def sec_render_grad(S, their_grad, name, size=128, cams=(0, 2)):
            + ("" if ok else " - class: camera convention / depth ties of the soft blend / clamp pattern"))
 
 
+def sec_evaluator(S, their_normals, their_view, name, size=128, deg=37.5):
+    """lib/dataset/Evaluator.py:58-73 (_render_normal: trimesh's vertex_normals drawn by the OpenGL NormalRender) against
+    icon_amd.evaluator (restated from the OpenGL specification and from memory): the vertex normals within 1e-6,
+    and one view - PASS means coverage equal on all but 0.5 % of the covered pixels (a real rasteriser may snap to another
+    sub-pixel grid) and colours within 2e-3 on the common ones (a real depth buffer holds 24 bits: where two faces are closer
+    than that the other may win)."""
+    from icon_amd.evaluator import normal_consistency_device
+    verts, faces = S.verts[0].float().contiguous(), S.faces[0].long().contiguous()
+    img, nrm = normal_consistency_device(verts, faces, degs=[deg], size=size, return_normals=True)
+    v, f = verts.cpu().numpy(), faces.cpu().numpy()
+    dn = float(np.abs(nrm.cpu().numpy() - np.asarray(their_normals(v, f), np.float64)).max())
+    report(name + " vertex_normals", "PASS" if dn <= 1e-6 else "DIFF", f"max |n - theirs| = {dn:.3e} over {len(v)} vertices"
+           + ("" if dn <= 1e-6 else " - class: the weights (corner angles) or the degenerate-face rule of the restatement"))
+    ours, theirs = img[0].cpu().numpy().astype(np.float64), np.asarray(their_view(v, f, deg, size), np.float64)
+    co, ct = ours[:, :, 3] > 0, theirs[:, :, 3] > 0
+    both = co & ct
+    n_cov, dc = int((co != ct).sum()), np.abs(ours - theirs)[:, :, :3].max(2)
+    n_c = int((both & (dc > 2e-3)).sum())
+    ok = co.sum() > 0 and max(n_cov, n_c) <= 0.005 * co.sum()
+    report(name + " _render_normal", "PASS" if ok else "DIFF", f"{size}^2 at {deg} degrees, {int(co.sum())} covered pixels: {n_cov} covered by one side only, "
+           f"{n_c} colour outliers; largest colour difference on the common pixels {dc[both].max() if both.any() else 0.0:.2e}"
+           + ("" if ok else " - class: sub-pixel snapping / fill rule / depth-buffer precision / flip of get_color"))
+
+
 def sec_voxelize(S, their_voxelize, name):
     """lib/net/voxelize.py:57-59,119-137"""
     from icon_amd import synth
@@ -434,6 +461,13 @@ def main():
             import normal_grad_oracle                                    # the rule of DESIGN.md 4.15 in float64 torch
             sec_render_grad(subject(), lambda v, f, cams, size, g, pix: normal_grad_oracle.loss_and_grad(v, f, pix, cams, size, g)[1], tag)
 
+        if want("evaluator"):
+            sys.path.insert(0, os.path.join(ROOT, "tests"))
+            import gl_checker                                            # the rule of DESIGN.md 4.20 in numpy
+            from icon_amd.evaluator import view_matrices
+            sec_evaluator(subject(), gl_checker.vertex_normals,
+                          lambda v, f, deg, size: gl_checker.render(v, f, None, view_matrices([deg]), np.ones((1, 3), np.float32), size)[0][0], tag)
+
         def classic(final):
             v, f = mc_classic.marching_cubes(final.cpu().numpy(), 0.5)
             return v[:, [2, 1, 0]], f[:, [0, 2, 1]]
@@ -473,6 +507,7 @@ def main():
                     return vertices[:, [2, 1, 0]], triangles.astype(np.int64)[:, [0, 2, 1]]
                 sec_marching_cubes(subject(), pymcubes, "PyMCubes marching_cubes", args.res)
         # ---- trimesh ----------------------------------------------------------------------------------------------
+        t = None
         if want("trimesh"):
             def imp():
                 import trimesh
@@ -485,6 +520,33 @@ def main():
                     best = lst[comp_num.index(max(comp_num))]
                     return np.asarray(best.vertices, np.float32), np.asarray(best.faces, np.int32)
                 sec_clean_mesh(subject(), split_largest, f"trimesh {t.__version__}")
+        # ---- trimesh + OpenGL: the evaluator's normal maps ---------------------------------------------------------------
+        # like the renderer row below: where trimesh is absent its ABSENT line covers this row too (asked for by name, --only
+        # evaluator, the row reports for itself)
+        if want("evaluator") and ("evaluator" in only or t):
+            def imp():
+                import trimesh
+                import OpenGL
+                ref_root = os.environ.get("ICON_REFERENCE_ROOT", "")
+                if ref_root and ref_root not in sys.path:
+                    sys.path.insert(0, ref_root)
+                from lib.renderer.gl.normal_render import NormalRender   # the reference's own renderer class: needs its tree and a GL context
+                return trimesh, OpenGL, NormalRender
+            ev = load("trimesh + PyOpenGL (evaluator; set ICON_REFERENCE_ROOT to the reference tree)", imp)
+            if ev:
+                state = {}
+
+                def their_view(v, f, deg, size):                         # Evaluator.py:58-73, written out
+                    r = state.setdefault(size, ev[2](width=size, height=size))
+                    view_mat, model_mat = np.identity(4), np.identity(4)
+                    model_mat[:3, :3] = r.euler_to_rot_mat(0, deg / 180.0 * np.pi, 0)
+                    view_mat[2, 2] *= -1
+                    r.set_matrices(view_mat, model_mat)
+                    mesh = ev[0].Trimesh(v, f, process=False)
+                    r.set_normal_mesh(mesh.vertices, mesh.faces, mesh.vertex_normals, mesh.faces)
+                    r.draw()
+                    return r.get_color()
+                sec_evaluator(subject(), lambda v, f: ev[0].Trimesh(v, f, process=False).vertex_normals, their_view, f"trimesh {ev[0].__version__} / PyOpenGL {ev[1].__version__}")
         # ---- pytorch3d --------------------------------------------------------------------------------------------
         p3 = None
         if want("pytorch3d"):
