@@ -20,4 +20,7 @@ def __getattr__(name):
     if name in ("extract_cloth", "extract_cloth_device", "nearest_vertex_device", "transfer_labels_device"):
         from . import garment
         return getattr(garment, name)
+    if name in ("ScanMesh", "GeoSampler", "sample_geo_device", "smpl_signs_device"):
+        from . import sampling
+        return getattr(sampling, name)
     raise AttributeError(name)

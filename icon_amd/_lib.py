@@ -46,6 +46,7 @@ SYMBOLS = [
     "icon_smpl_bytes", "icon_smpl_forward", "icon_smpl_backward",
     "icon_nearest_vertex", "icon_extract_cloth_bytes", "icon_extract_cloth",
     "icon_normal_consistency_bytes", "icon_normal_consistency",
+    "icon_sample_geo_bytes", "icon_sample_geo",
 ]
 
 _lib = None

@@ -770,6 +770,32 @@ int icon_normal_consistency(const float *d_verts_a, int64_t Va, const void *d_fa
                             int32_t *d_pix_b, float *d_normals_out_a, float *d_normals_out_b, void *d_scratch,
                             int64_t scratch_bytes, void *stream);
 
+/* ---- training samples: the points and labels of get_sampling_geo ---------------------------------------------
+ * replaces PIFuDataset.get_sampling_geo (lib/dataset/PIFuDataset.py:483-607, is_sdf=False; called per item at :226-229).
+ * The rule is DESIGN.md 4.21: nS = 4 N surface samples verts[id] + vert_normals[id] * (sigma_geo * normal), nU = N / 4 space
+ * samples calib_inv (2 u - 1) and, when zray != 0, nS R z-ray samples (surface sample k / R through calib, its z moved by
+ * 0.5 * (0.40 * normal), back through calib_inv), n = nS + nU + nS R in that order; slot i of the shuffled list holds source
+ * perm(i).  Every draw is Philox4x32-10 of (seed, stream, index); float64 arithmetic in the stated order, rounded once to
+ * float32.  Labels: the inside test of `scan` (the rule of icon_sdf_query's `inside`) on the float32 samples - trimesh's
+ * `contains` in the reference, UNPINNED.  Balancing: more than N / 2 inside -> the first N / 2 inside and N / 2 outside samples
+ * of the shuffled list, else every inside and the first N - n_in outside ones; inside rows first, labels 1 then 0.
+ * scan: the scan's mesh handle, built on `stream` or finished; d_verts [V,3] f32, the vertices it was built from (V is the
+ * handle's); d_vert_normals [V,3] f32, or NULL: the handle's own vertex normals (S1).  calib / calib_inv: HOST float64 [12],
+ * rows of the affine [3][4] and of its inverse.  1 <= N < 2^24, 1 <= R <= 64, n < 2^31.
+ * Outputs (device): d_samples [N,3] f32, d_labels [N] f32, d_counts int32 [2] = (inside rows, outside rows); rows past their
+ * sum - only when the outside samples run short - are zero with label 0.  Optional, each NULL or [n]: d_all_samples [n,3] f32
+ * and d_all_inside uint8, the shuffled list before balancing; d_all_source int32, perm(i); d_all_vertex int32, the vertex drawn
+ * for the slot (-1 for a space sample).
+ * d_scratch: device memory of at least icon_sample_geo_bytes(n) bytes, 256-byte aligned, owned by the caller; its contents
+ * need not survive between calls.  Enqueued on `stream`, three launches whatever the sizes: no allocation, no synchronisation,
+ * nothing read back; no atomics: equal bytes from run to run. */
+int icon_sample_geo_bytes(int64_t n, int64_t *bytes);
+int icon_sample_geo(const icon_mesh_t *scan, const float *d_verts, const float *d_vert_normals,
+                    const double *calib, const double *calib_inv, int64_t N, double sigma_geo, int zray, int R,
+                    uint64_t seed, float *d_samples, float *d_labels, int32_t *d_counts,
+                    float *d_all_samples, uint8_t *d_all_inside, int32_t *d_all_source, int32_t *d_all_vertex,
+                    void *d_scratch, int64_t scratch_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
