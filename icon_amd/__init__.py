@@ -4,6 +4,7 @@ Public surface (mirrors the reference's query interface, see icon_amd/engine.py)
     IconQueryEngine.query      == HGPIFuNet.query        (lib/net/HGPIFuNet.py:268-367)
     query_func                 == lib/common/train_util.py:324-348
     DenseReconEngine           == the reconEngine object (lib/common/seg3d_lossless.py:36)
+    training.attach            == HGPIFuNet.query in train mode: native rows of every stack + their gradient (icon_amd/training.py)
 The compute path is libicon_amd.so (include/icon_amd.h); there is no CPU fallback.
 """
 __version__ = "0.1.0"
@@ -23,4 +24,7 @@ def __getattr__(name):
     if name in ("ScanMesh", "GeoSampler", "sample_geo_device", "smpl_signs_device"):
         from . import sampling
         return getattr(sampling, name)
+    if name in ("point_features_device", "TrainQuery"):
+        from . import training
+        return getattr(training, name)
     raise AttributeError(name)

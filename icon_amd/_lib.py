@@ -47,6 +47,7 @@ SYMBOLS = [
     "icon_nearest_vertex", "icon_extract_cloth_bytes", "icon_extract_cloth",
     "icon_normal_consistency_bytes", "icon_normal_consistency",
     "icon_sample_geo_bytes", "icon_sample_geo",
+    "icon_train_rows_bytes", "icon_train_rows_forward", "icon_train_rows_backward",
 ]
 
 _lib = None

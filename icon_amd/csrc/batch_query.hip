@@ -64,6 +64,45 @@ __global__ __launch_bounds__(kBlock) void k_nearest_batch(BatchDev bd, const flo
     if (live) store_near(near, i, nr, sdf_clip);
 }
 
+// the geometry half of a batched icon call over the B*N points: nearest triangle (cooperative or Morton packets), the sign pass
+// (code bytes + block counts) and, for the reference cmap rule, the batch-global outlier sign list.  Shared by
+// icon_query_points_batch and icon_train_rows_forward (train_rows.hip): the search runs once per call, whoever consumes it.
+int batch_geometry(const icon_mesh_batch *mb, const BatchDev &bd, const float *d_points, int64_t N, int B, float sdf_clip,
+                   bool needs_patch, icon_work *work, hipStream_t st)
+{
+    const icon_mesh *mesh0 = mb->subj[0];
+    const float *d_calibs = bd.calibs;
+    const int64_t NB = N * (int64_t)B;
+    int rc;
+    if (mb->F > kNearLoSlots && work->cap_points_hi < work->cap_points) {      // big meshes: the byte of higher slot bits
+        (void)hipFree(work->d_near_hi); work->d_near_hi = nullptr; work->cap_points_hi = 0;
+        ICON_HIP(hipMalloc((void **)&work->d_near_hi, (size_t)work->cap_points));
+        work->cap_points_hi = work->cap_points;
+    }
+    const NearRef near = work_near(work, mesh0);
+    static const int mode = getenv("ICON_AMD_POINT_SEARCH") ? atoi(getenv("ICON_AMD_POINT_SEARCH")) : 0;   // 0 auto, 2 coop, 3 packets
+    if (mode != 3 && (NB < kPacketMinPoints || mode == 2)) {
+        const int cap = coop_cap(mb->depth_bound);
+        hipLaunchKernelGGL(k_nearest_coop<true>, dim3((unsigned)((NB + kCoopWaves - 1) / kCoopWaves)), dim3(kCoopWaves * 64),
+                           kCoopWaves * coop_wave_bytes(cap), st, MeshDev{}, Calib{}, d_points, NB, near, cap, sdf_clip, bd);
+    } else {
+        const int32_t *perm = nullptr;
+        if ((rc = morton_order_batch(work, d_points, d_calibs, N, B, st, &perm))) return rc;
+        const int64_t npad = (N + 63) / 64 * 64;
+        const int64_t nb = (npad * B + kBlock - 1) / kBlock;
+        ICON_ARG(nb < (1ll << 31), "icon_query_points_batch: too many workgroups for one launch");
+        if (work->prof) (void)hipEventRecord(work->ev[4], st);
+        hipLaunchKernelGGL(k_nearest_batch, dim3((unsigned)nb), dim3(kBlock), 0, st, bd, d_points, npad, near, perm, sdf_clip);
+        if (work->prof) { (void)hipEventRecord(work->ev[5], st); work->ev_search = true; }
+    }
+    ICON_HIP(hipGetLastError());
+    debug_sync("nearest (batch)", st);
+    if ((rc = launch_sign(mesh0, Calib{}, 0, 0, d_points, NB, sdf_clip, work, false, st, &bd))) return rc;
+    debug_sync("k_sign_wide<batch>", st);
+    if (needs_patch && (rc = outlier_list(work, NB, work->d_signs, true, st))) return rc;
+    return ICON_OK;
+}
+
 }  // namespace icon
 
 // =============================================================================================
@@ -179,34 +218,7 @@ extern "C" int icon_query_points_batch(const icon_mesh_batch_t *mb, const icon_f
     const bool needs_patch = prior_type == ICON_PRIOR_ICON && cmap_mode == ICON_CMAP_REFERENCE && (f.smpl_mask & kSmplCmap);
     const int local = (cmap_mode == ICON_CMAP_LOCAL) ? 1 : 0;
     mark(work, 0, st);
-    if (prior_type == ICON_PRIOR_ICON) {
-        if (mb->F > kNearLoSlots && work->cap_points_hi < work->cap_points) {      // big meshes: the byte of higher slot bits
-            (void)hipFree(work->d_near_hi); work->d_near_hi = nullptr; work->cap_points_hi = 0;
-            ICON_HIP(hipMalloc((void **)&work->d_near_hi, (size_t)work->cap_points));
-            work->cap_points_hi = work->cap_points;
-        }
-        const NearRef near = work_near(work, mesh0);
-        static const int mode = getenv("ICON_AMD_POINT_SEARCH") ? atoi(getenv("ICON_AMD_POINT_SEARCH")) : 0;   // 0 auto, 2 coop, 3 packets
-        if (mode != 3 && (NB < kPacketMinPoints || mode == 2)) {
-            const int cap = coop_cap(mb->depth_bound);
-            hipLaunchKernelGGL(k_nearest_coop<true>, dim3((unsigned)((NB + kCoopWaves - 1) / kCoopWaves)), dim3(kCoopWaves * 64),
-                               kCoopWaves * coop_wave_bytes(cap), st, MeshDev{}, Calib{}, d_points, NB, near, cap, sdf_clip, bd);
-        } else {
-            const int32_t *perm = nullptr;
-            if ((rc = morton_order_batch(work, d_points, d_calibs, N, B, st, &perm))) return rc;
-            const int64_t npad = (N + 63) / 64 * 64;
-            const int64_t nb = (npad * B + kBlock - 1) / kBlock;
-            ICON_ARG(nb < (1ll << 31), "icon_query_points_batch: too many workgroups for one launch");
-            if (work->prof) (void)hipEventRecord(work->ev[4], st);
-            hipLaunchKernelGGL(k_nearest_batch, dim3((unsigned)nb), dim3(kBlock), 0, st, bd, d_points, npad, near, perm, sdf_clip);
-            if (work->prof) { (void)hipEventRecord(work->ev[5], st); work->ev_search = true; }
-        }
-        ICON_HIP(hipGetLastError());
-        debug_sync("nearest (batch)", st);
-        if ((rc = launch_sign(mesh0, Calib{}, 0, 0, d_points, NB, sdf_clip, work, false, st, &bd))) return rc;
-        debug_sync("k_sign_wide<batch>", st);
-        if (needs_patch && (rc = outlier_list(work, NB, work->d_signs, true, st))) return rc;
-    }
+    if (prior_type == ICON_PRIOR_ICON && (rc = batch_geometry(mb, bd, d_points, N, B, sdf_clip, needs_patch, work, st))) return rc;
     mark(work, 1, st);
     FusedSigns fs{};
     fs.mode = needs_patch ? kSignSelf : kSignNone;

@@ -389,6 +389,9 @@ int launch_fused_f16x3(const icon_mesh *mesh, const icon_feat *feat, const icon_
 // sort_points.hip: Morton order of a batched call's B*n points, subject first: subject b's points are the sorted positions
 // [b n, (b + 1) n) (the key carries the subject above the Morton bits)
 int morton_order_batch(icon_work *w, const float *d_points, const float *d_calibs, int64_t n, int B, hipStream_t st, const int32_t **perm);
+// batch_query.hip: search + sign pass + (needs_patch) batch-global outlier list of a batched icon call; ensure_work(N * B) came first
+int batch_geometry(const icon_mesh_batch *mb, const BatchDev &bd, const float *d_points, int64_t N, int B, float sdf_clip,
+                   bool needs_patch, icon_work *work, hipStream_t st);
 // query_kernels.hip: pieces of the point-mode pipeline the batched call (batch_query.hip) shares
 int ensure_work(icon_work *w, int64_t n_points, bool need_x);                          // scratch for n_points (need_x: the 64-byte input rows too)
 int outlier_list(icon_work *w, int64_t N, int8_t *signs, bool counted, hipStream_t st);   // counted: k_sign left the block counts

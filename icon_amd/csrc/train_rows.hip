@@ -1,0 +1,329 @@
+// train_rows.hip - the regressor's input rows of HGPIFuNet.query in TRAINING (lib/net/HGPIFuNet.py:268-359) for every feature
+// stack of a call from ONE geometry pass, and the gradient of those rows back into the feature planes.  The rule is DESIGN.md
+// 4.22, restated in numpy by tests/train_oracle.py.
+//
+// Forward (icon_train_rows_forward): the B*N points in subject-major order, as the batched query takes them.
+//   icon : batch_geometry (batch_query.hip: search, sign pass, batch-global outlier list - the launches of icon_query_points_batch),
+//          k_tr_point (SMPL channels of a point by sdf_attrs, its in_cube flag, its tap record), the existing cmap patch over those
+//          channels (patch_self), k_tr_rows (a lane per point and stack: the bilinear tap of S7 from the caller's [B,C,H,W] planes)
+//   pifu : k_tr_point (z, in_cube, tap record), k_tr_rows
+// The SMPL channels live in the workspace's row buffer ([B*N][16], slots 0 .. 6 = sdf | cmap | norm), which is what patch_self
+// patches; every stack's rows copy them, so two stacks share them bit for bit.
+//
+// Backward (icon_train_rows_backward): no floating-point atomics.  k_tr_keys gives every point the key of its north-west cell
+// (subject, y0 + 1, x0 + 1) - a sentinel when none of its taps lies inside -, one stable radix sort orders the points by cell
+// (ascending point index inside a cell), and k_tr_gather runs one wavefront per texel: the texel is the nw / ne / sw / se tap of
+// the points of four cells, found by binary search; 16 channel lanes x 4 point lanes sum weight * grad in float64 (the product in
+// float32) in a fixed order and the four point lanes are combined by a fixed shuffle tree.  Every texel is written.
+#pragma clang fp contract(off)
+
+#include "query_device.h"
+
+#include <rocprim/rocprim.hpp>
+
+namespace icon {
+namespace {
+
+constexpr int kTrMaxStacks = 8;
+constexpr int kTrChanLanes = 16, kTrPointLanes = 64 / kTrChanLanes;
+
+// 16 bytes per point, forward -> backward: the projected x, y the taps are formed from (bilinear_taps gives the north-west texel, the
+// weights and which taps lie inside from them, in the forward's own operations), the sort key of the north-west cell, the feature half
+struct alignas(16) TrTap { float x, y; uint32_t key; uint32_t half; };
+static_assert(sizeof(TrTap) == 16, "TrTap must be 16 bytes");
+
+struct TrShape {
+    int B, C, H, W, S, csel, n_select, smpl_mask, cin;
+    int64_t n;                       // points per subject
+    uint32_t cells, sentinel;        // (H + 1) (W + 1) cells per subject; key of a point without a tap inside
+};
+
+struct TrStacks { const float *p[kTrMaxStacks]; };
+
+__device__ __forceinline__ uint32_t tr_key(const TrShape &q, int64_t b, const BilinearTaps &t)
+{
+    const bool any = (t.bx0 || t.bx1) && (t.by0 || t.by1);       // then x0 in [-1, W - 1], y0 in [-1, H - 1]
+    return any ? (uint32_t)b * q.cells + (uint32_t)(t.y0 + 1) * (uint32_t)(q.W + 1) + (uint32_t)(t.x0 + 1) : q.sentinel;
+}
+
+// a lane per point: what does not depend on the stack.  X: the workspace's rows [B*n][kXRow]
+template <int PRIOR>
+__global__ __launch_bounds__(kBlock) void k_tr_point(TrShape q, BatchDev bd, const float *__restrict__ pts, float sdf_clip, int cmap_local,
+                                                     NearRef near, const uint8_t *__restrict__ code8, float *__restrict__ X,
+                                                     float *__restrict__ in_cube, TrTap *__restrict__ taps)
+{
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= q.n * q.B) return;
+    const int64_t b = i / q.n;
+    const f3 p = project(batch_calib(bd, b), mk3(pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]));
+    float *row = X + i * kXRow;
+    uint32_t half = 0;
+    if (PRIOR == ICON_PRIOR_ICON) {
+        // the feature phase of k_features (query_device.h) without the planes: the geometry pre-pass left slot, code byte and d^2
+        const uint32_t code = code8[i];
+        Nearest nr;
+        nr.slot = near_slot_of(near, i); nr.face = 0;
+        nr.d2 = (code & kCodeOutlier) ? 0.0f : near_d2(near, i);
+        const SdfOut o = sdf_attrs(bd.meshes[b], p, nr, (code & kCodeInside) != 0);
+        float s = o.sdf;
+        f3 cmv = o.cm;
+        if (code & kCodeOutlier) {            // HGPIFuNet.py:298-305
+            s = (float)((int)((code >> kCodeSignShift) & 3u) - 1);
+            if (cmap_local) cmv = mk3(s, s, s);   // reference mode: patched from the sign list (patch_self)
+        }
+        half = (q.n_select == 2 && o.vis == 0.0f) ? 1u : 0u;     // feat_select: vis == 1 -> front half
+        row[0] = s;
+        row[1] = cmv.x; row[2] = cmv.y; row[3] = cmv.z;
+        row[4] = o.nrm.x; row[5] = o.nrm.y; row[6] = o.nrm.z;
+    } else {
+        row[0] = p.z;
+    }
+    in_cube[i] = in_cube_bit(p) ? 1.0f : 0.0f;
+    const BilinearTaps t = bilinear_taps(p.x, p.y, q.H, q.W);
+    TrTap r;
+    r.x = p.x; r.y = p.y; r.key = tr_key(q, b, t); r.half = half;
+    taps[i] = r;
+}
+
+// a lane per point and stack (blockIdx.y): rows [S][B][cin][n]; the tap is gather_planes' statement over [B][C][H][W] planes
+template <int PRIOR>
+__global__ __launch_bounds__(kBlock) void k_tr_rows(TrShape q, TrStacks st, const TrTap *__restrict__ taps, const float *__restrict__ X,
+                                                    float *__restrict__ rows)
+{
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= q.n * q.B) return;
+    const int s = blockIdx.y;
+    const int64_t b = i / q.n, pn = i - b * q.n;
+    const TrTap r = taps[i];
+    const BilinearTaps t = bilinear_taps(r.x, r.y, q.H, q.W);
+    const int x1 = t.x0 + 1, y1 = t.y0 + 1;
+    const bool v00 = t.bx0 && t.by0, v01 = t.bx1 && t.by0, v10 = t.bx0 && t.by1, v11 = t.bx1 && t.by1;
+    const int64_t hw = (int64_t)q.H * q.W;
+    const int64_t o00 = v00 ? (int64_t)t.y0 * q.W + t.x0 : 0, o01 = v01 ? (int64_t)t.y0 * q.W + x1 : 0;
+    const int64_t o10 = v10 ? (int64_t)y1 * q.W + t.x0 : 0, o11 = v11 ? (int64_t)y1 * q.W + x1 : 0;
+    const float *plane = st.p[s] + ((int64_t)b * q.C + (int64_t)r.half * q.csel) * hw;
+    float *out = rows + (((int64_t)s * q.B + b) * q.cin) * q.n + pn;
+    for (int c = 0; c < q.csel; ++c, plane += hw, out += q.n) {
+        const float t00 = v00 ? plane[o00] : 0.0f, t01 = v01 ? plane[o01] : 0.0f;
+        const float t10 = v10 ? plane[o10] : 0.0f, t11 = v11 ? plane[o11] : 0.0f;
+        float acc = t00 * t.nw; acc += t01 * t.ne; acc += t10 * t.sw; acc += t11 * t.se;
+        *out = acc;
+    }
+    const float *row = X + i * kXRow;
+    *out = row[0]; out += q.n;                                   // sdf (icon) / z (pifu)
+    if (PRIOR == ICON_PRIOR_ICON) {                              // [img | sdf | cmap (if) | norm (if)], HGPIFuNet.py:301-311
+        if (q.smpl_mask & kSmplCmap) { out[0] = row[1]; out[q.n] = row[2]; out[2 * q.n] = row[3]; out += 3 * q.n; }
+        if (q.smpl_mask & kSmplNorm) { out[0] = row[4]; out[q.n] = row[5]; out[2 * q.n] = row[6]; }
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void k_tr_keys(const TrTap *__restrict__ taps, int64_t NB, uint32_t *__restrict__ keys, int32_t *__restrict__ idx)
+{
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= NB) return;
+    keys[i] = taps[i].key; idx[i] = (int32_t)i;
+}
+
+// first position of the sorted keys that is >= key
+__device__ __forceinline__ int tr_lower_bound(const uint32_t *__restrict__ keys, int n, uint32_t key)
+{
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        const int mid = lo + ((hi - lo) >> 1);
+        if (keys[mid] < key) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+// a wavefront per texel (b, y, x): no barrier, no LDS
+__global__ __launch_bounds__(kBlock) void k_tr_gather(TrShape q, uint32_t stack_mask, const TrTap *__restrict__ taps, const uint32_t *__restrict__ keys,
+                                                      const int32_t *__restrict__ idx, const float *__restrict__ grad_rows, float *__restrict__ grad_planes)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t hw = (int64_t)q.H * q.W;
+    const int64_t t = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
+    if (t >= hw * q.B) return;                                   // wave-uniform
+    const int b = (int)(t / hw);
+    const int yx = (int)(t - (int64_t)b * hw), y = yx / q.W, x = yx - y * q.W;
+    const int NB = (int)(q.n * q.B);
+    // the texel is tap k = 0 nw, 1 ne, 2 sw, 3 se of the points whose north-west cell is (y - (k >> 1), x - (k & 1)): lanes 2k and
+    // 2k + 1 find that cell's segment of the sorted list
+    const int j = lane & 7, kj = j >> 1;
+    const uint32_t key = (uint32_t)b * q.cells + (uint32_t)(y + 1 - (kj >> 1)) * (uint32_t)(q.W + 1) + (uint32_t)(x + 1 - (kj & 1)) + (uint32_t)(j & 1);
+    const int found = tr_lower_bound(keys, NB, key);
+    int lo[4], hi[4], total = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { lo[k] = __shfl(found, 2 * k); hi[k] = __shfl(found, 2 * k + 1); total += hi[k] - lo[k]; }
+    const int cl = lane & (kTrChanLanes - 1), pl = lane / kTrChanLanes;
+    const int nch = q.S * q.C;
+    for (int base = 0; base < nch; base += kTrChanLanes) {
+        const int ch = base + cl;
+        const bool active = ch < nch;
+        const int s = active ? ch / q.C : 0, c = active ? ch - s * q.C : 0;
+        const uint32_t half = (uint32_t)(c / q.csel);
+        const int cp = c - (int)half * q.csel;
+        const bool wanted = active && ((stack_mask >> s) & 1u);
+        double acc = 0.0;
+        if (wanted && total > 0) {
+            const float *g = grad_rows + (((int64_t)s * q.B + b) * q.cin + cp) * q.n - (int64_t)b * q.n;   // + i: the point's own column
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                for (int p = lo[k] + pl; p < hi[k]; p += kTrPointLanes) {
+                    const int i = idx[p];
+                    const TrTap r = taps[i];
+                    if (r.half != half) continue;
+                    const BilinearTaps bt = bilinear_taps(r.x, r.y, q.H, q.W);
+                    const float w = k == 0 ? bt.nw : (k == 1 ? bt.ne : (k == 2 ? bt.sw : bt.se));
+                    const float prod = w * g[i];
+                    acc += (double)prod;
+                }
+            }
+        }
+        acc += __shfl_xor(acc, kTrChanLanes);
+        acc += __shfl_xor(acc, 2 * kTrChanLanes);
+        if (wanted && pl == 0) grad_planes[(((int64_t)s * q.B + b) * q.C + c) * hw + yx] = (float)acc;
+    }
+}
+
+struct TrLayout { size_t keys, idx, tmp, tmp_bytes, total; int end_bit; };
+
+int tr_layout(int64_t NB, uint32_t sentinel, TrLayout *L)
+{
+    int end_bit = 1;
+    while (end_bit < 32 && (sentinel >> end_bit) != 0) ++end_bit;
+    size_t tmp = 0;
+    ICON_HIP(rocprim::radix_sort_pairs(nullptr, tmp, (uint32_t *)nullptr, (uint32_t *)nullptr, (int32_t *)nullptr, (int32_t *)nullptr,
+                                       (size_t)NB, 0, end_bit, (hipStream_t)nullptr));
+    size_t o = 0;
+    auto take = [&](size_t bytes) { const size_t at = o; o = (o + bytes + 255) / 256 * 256; return at; };
+    L->keys = take(2 * (size_t)NB * sizeof(uint32_t)); L->idx = take(2 * (size_t)NB * sizeof(int32_t));
+    L->tmp = take(tmp); L->tmp_bytes = tmp;
+    L->total = o; L->end_bit = end_bit;
+    return ICON_OK;
+}
+
+int tr_shape(int B, int64_t N, int S, int C, int H, int W, int n_select, const char *what, TrShape *q)
+{
+    ICON_ARG(B >= 1 && N >= 1 && S >= 1 && C >= 1 && H >= 1 && W >= 1, std::string(what) + ": B, N, S, C, H, W must be positive");
+    ICON_ARG((int64_t)B * N < (1ll << 31), std::string(what) + ": B * N must be below 2^31");
+    if (S > kTrMaxStacks) return fail(ICON_ERR_UNSUPPORTED, std::string(what) + ": more than 8 feature stacks");
+    ICON_ARG(n_select == 1 || (n_select == 2 && C % 2 == 0), std::string(what) + ": feat_select needs an even channel count");
+    const int64_t cells = (int64_t)(H + 1) * (W + 1);
+    if (cells * B >= (1ll << 32) - 1 || (int64_t)B * H * W >= (1ll << 31) * (kBlock / 64))
+        return fail(ICON_ERR_UNSUPPORTED, std::string(what) + ": B (H + 1) (W + 1) must stay below 2^32 - 1");
+    *q = TrShape{};
+    q->B = B; q->C = C; q->H = H; q->W = W; q->S = S; q->n = N; q->n_select = n_select; q->csel = C / n_select;
+    q->cells = (uint32_t)cells; q->sentinel = (uint32_t)(cells * B);
+    return ICON_OK;
+}
+
+}  // namespace
+}  // namespace icon
+
+using namespace icon;
+
+extern "C" int icon_train_rows_bytes(int B, int64_t N, int S, int C, int H, int W, int64_t *bytes)
+{
+    ICON_ARG(bytes != nullptr, "icon_train_rows_bytes: null argument");
+    TrShape q;
+    int rc;
+    if ((rc = tr_shape(B, N, S, C, H, W, 1, "icon_train_rows_bytes", &q))) return rc;
+    TrLayout L;
+    if ((rc = tr_layout(N * (int64_t)B, q.sentinel, &L))) return rc;
+    *bytes = (int64_t)L.total;
+    return ICON_OK;
+}
+
+extern "C" int icon_train_rows_forward(const icon_mesh_batch_t *mb, int prior_type, float sdf_clip, int cmap_mode, int has_vis,
+                                       int has_cmap, int has_norm, const float *const *d_stacks, const int32_t *stack_shapes, int S,
+                                       const float *d_calibs, const float *d_points, int64_t N, float *d_rows, float *d_in_cube,
+                                       void *d_taps, int search, icon_work_t *work, void *stream)
+{
+    const char *what = "icon_train_rows_forward";
+    ICON_ARG(d_stacks && stack_shapes && d_calibs && d_points && d_rows && d_in_cube && d_taps && work, std::string(what) + ": null argument");
+    ICON_ARG(S >= 1, std::string(what) + ": no feature stack");
+    if (prior_type == ICON_PRIOR_PAMIR)
+        return fail(ICON_ERR_UNSUPPORTED, std::string(what) + ": the pamir prior is not trained here (no gradient into the volume encoder's planes)");
+    ICON_ARG(prior_type == ICON_PRIOR_ICON || prior_type == ICON_PRIOR_PIFU, std::string(what) + ": unknown prior_type");
+    if (search == ICON_SEARCH_BRUTE) return fail(ICON_ERR_UNSUPPORTED, std::string(what) + ": search 'brute' is evaluated at batch size 1 only");
+    if (work->tie_rule != 0) return fail(ICON_ERR_UNSUPPORTED, std::string(what) + ": tie rules are evaluated at batch size 1 only");
+    for (int s = 0; s < S; ++s) {
+        ICON_ARG(s >= kTrMaxStacks || d_stacks[s] != nullptr, std::string(what) + ": a feature stack is null");
+        for (int k = 0; k < 4; ++k)
+            ICON_ARG(stack_shapes[4 * s + k] == stack_shapes[k], std::string(what) + ": the feature stacks differ in shape (all must be one [B,C,H,W])");
+    }
+    const int B = stack_shapes[0], C = stack_shapes[1], H = stack_shapes[2], W = stack_shapes[3];
+    const bool icon_prior = prior_type == ICON_PRIOR_ICON;
+    TrShape q;
+    int rc;
+    if ((rc = tr_shape(B, N, S, C, H, W, (icon_prior && has_vis) ? 2 : 1, what, &q))) return rc;
+    q.smpl_mask = icon_prior ? ((has_cmap ? kSmplCmap : 0) | (has_norm ? kSmplNorm : 0)) : 0;
+    q.cin = q.csel + 1 + ((q.smpl_mask & kSmplCmap) ? 3 : 0) + ((q.smpl_mask & kSmplNorm) ? 3 : 0);
+    if (icon_prior) {
+        ICON_ARG(mb != nullptr, std::string(what) + ": the icon prior needs a mesh batch");
+        ICON_ARG(mb->B == B, std::string(what) + ": the mesh batch holds another number of subjects");
+    }
+    ICON_ARG(((uintptr_t)d_taps & 15) == 0, std::string(what) + ": the tap records must be 16-byte aligned");
+    const int64_t NB = N * (int64_t)B;
+    hipStream_t st = (hipStream_t)stream;
+    if ((rc = ensure_work(work, NB, true))) return rc;
+    work->slab_ready = false;
+    work->q_rows_ready = false; work->slab_patched = false;
+    BatchDev bd{};
+    bd.meshes = icon_prior ? mb->d_table : nullptr; bd.calibs = d_calibs; bd.n = N; bd.B = B;
+    const bool needs_patch = icon_prior && cmap_mode == ICON_CMAP_REFERENCE && (q.smpl_mask & kSmplCmap);
+    const int local = (cmap_mode == ICON_CMAP_LOCAL) ? 1 : 0;
+    if (icon_prior && (rc = batch_geometry(mb, bd, d_points, N, B, sdf_clip, needs_patch, work, st))) return rc;
+    work->flag_clean = false;                                    // no fused kernel follows the sign pass here: the next one clears its own flag
+    TrStacks stacks{};
+    for (int s = 0; s < S; ++s) stacks.p[s] = d_stacks[s];
+    TrTap *taps = static_cast<TrTap *>(d_taps);
+    const unsigned nb = (unsigned)((NB + kBlock - 1) / kBlock);
+    const NearRef near = work_near(work, icon_prior ? mb->subj[0] : nullptr);
+    if (icon_prior)
+        hipLaunchKernelGGL(k_tr_point<ICON_PRIOR_ICON>, dim3(nb), dim3(kBlock), 0, st, q, bd, d_points, sdf_clip, local, near,
+                           (const uint8_t *)work->d_code8, work->d_x, d_in_cube, taps);
+    else
+        hipLaunchKernelGGL(k_tr_point<ICON_PRIOR_PIFU>, dim3(nb), dim3(kBlock), 0, st, q, bd, d_points, sdf_clip, local, near,
+                           (const uint8_t *)work->d_code8, work->d_x, d_in_cube, taps);
+    ICON_HIP(hipGetLastError());
+    if (needs_patch && (rc = patch_self(work, NB, 1, st))) return rc;
+    if (icon_prior)
+        hipLaunchKernelGGL(k_tr_rows<ICON_PRIOR_ICON>, dim3(nb, (unsigned)S), dim3(kBlock), 0, st, q, stacks, (const TrTap *)taps, (const float *)work->d_x, d_rows);
+    else
+        hipLaunchKernelGGL(k_tr_rows<ICON_PRIOR_PIFU>, dim3(nb, (unsigned)S), dim3(kBlock), 0, st, q, stacks, (const TrTap *)taps, (const float *)work->d_x, d_rows);
+    ICON_HIP(hipGetLastError());
+    return ICON_OK;
+}
+
+extern "C" int icon_train_rows_backward(const float *d_grad_rows, const void *d_taps, int S, uint32_t stack_mask, int B, int Cin, int C,
+                                        int H, int W, int n_select, int64_t N, float *d_grad_planes, void *d_scratch,
+                                        int64_t scratch_bytes, void *stream)
+{
+    const char *what = "icon_train_rows_backward";
+    ICON_ARG(d_grad_rows && d_taps && d_grad_planes && d_scratch, std::string(what) + ": null argument");
+    TrShape q;
+    int rc;
+    if ((rc = tr_shape(B, N, S, C, H, W, n_select, what, &q))) return rc;
+    ICON_ARG(Cin > q.csel, std::string(what) + ": the rows hold fewer channels than the feature half");
+    q.cin = Cin;
+    const int64_t NB = N * (int64_t)B;
+    TrLayout L;
+    if ((rc = tr_layout(NB, q.sentinel, &L))) return rc;
+    ICON_ARG(((uintptr_t)d_scratch & 255) == 0, std::string(what) + ": the scratch must be 256-byte aligned");
+    ICON_ARG(scratch_bytes >= (int64_t)L.total, std::string(what) + ": scratch smaller than icon_train_rows_bytes");
+    char *s = static_cast<char *>(d_scratch);
+    uint32_t *k0 = reinterpret_cast<uint32_t *>(s + L.keys), *k1 = k0 + NB;
+    int32_t *i0 = reinterpret_cast<int32_t *>(s + L.idx), *i1 = i0 + NB;
+    const TrTap *taps = static_cast<const TrTap *>(d_taps);
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_tr_keys, dim3((unsigned)((NB + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, taps, NB, k0, i0);
+    ICON_HIP(hipGetLastError());
+    size_t tmp = L.tmp_bytes;
+    ICON_HIP(rocprim::radix_sort_pairs(s + L.tmp, tmp, k0, k1, i0, i1, (size_t)NB, 0, L.end_bit, st));
+    const int64_t texels = (int64_t)B * H * W, per = kBlock / 64;
+    hipLaunchKernelGGL(k_tr_gather, dim3((unsigned)((texels + per - 1) / per)), dim3(kBlock), 0, st, q, stack_mask, taps, (const uint32_t *)k1,
+                       (const int32_t *)i1, d_grad_rows, d_grad_planes);
+    ICON_HIP(hipGetLastError());
+    return ICON_OK;
+}

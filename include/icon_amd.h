@@ -796,6 +796,35 @@ int icon_sample_geo(const icon_mesh_t *scan, const float *d_verts, const float *
                     float *d_all_samples, uint8_t *d_all_inside, int32_t *d_all_source, int32_t *d_all_vertex,
                     void *d_scratch, int64_t scratch_bytes, void *stream);
 
+/* ---- training: the regressor's input rows of every feature stack, and their gradient into the planes ----------
+ * HGPIFuNet.query in training mode up to the regressor (lib/net/HGPIFuNet.py:268-359) for the icon and pifu priors; the rule
+ * is DESIGN.md 4.22.  The B*N points are taken in subject-major order as icon_query_points_batch takes them (d_points [B,N,3]
+ * world points, d_calibs [B,12] device); d_stacks: HOST array of S device pointers to float32 [B,C,H,W] planes (the caller's own
+ * tensors, not repacked), stack_shapes: HOST int32 [S][4] = B, C, H, W of every stack - all must agree.  has_vis / has_cmap /
+ * has_norm: cfg.net.smpl_feats (icon; ignored for pifu).  mb: the subjects' mesh batch (icon) or NULL (pifu).
+ * Forward outputs (device): d_rows float32 [S,B,Cin,N] = point_feat of every stack, channels [img | sdf | cmap | norm] (icon,
+ * the subsets of icon_feat_set_smpl_feats; img = the half smpl_vis selects when has_vis, else all C) or [img | z] (pifu);
+ * d_in_cube float32 [B,1,N], the strict test of :274-275; d_taps [B*N] records of 16 bytes (16-byte aligned) for the backward.
+ * The search, the SMPL channels, the sdf clip and the batch-global outlier cmap list run once per call, not per stack: the
+ * launches of icon_query_points_batch's geometry half plus three, whatever B, N and S.  The workspace grows as for any other
+ * call; otherwise no allocation, no synchronisation.  ICON_ERR_UNSUPPORTED: the pamir prior, search 'brute', a tie rule on the
+ * workspace, S > 8; ICON_ERR_ARG: stacks of differing shapes, B * N >= 2^31.
+ * Backward: d_grad_rows [S,B,Cin,N] -> d_grad_planes [S,B,C,H,W], every element of every stack whose bit of stack_mask is set
+ * written (the others are left alone): texel (s,b,c,y,x) = sum over the points whose four taps include it of weight *
+ * grad_rows[s,b,c',p], c' = c - half * (C / n_select) for the points of that feature half; products in float32, the sum in
+ * float64 in a fixed order (cells nw, ne, sw, se; ascending point index inside a cell, dealt to four lanes and combined by a
+ * fixed tree), rounded once; taps outside the image contribute nothing.  No floating-point atomics: equal bytes from run to
+ * run.  n_select: 2 when has_vis (icon), else 1.  d_scratch: icon_train_rows_bytes bytes, 256-byte aligned, the caller's;
+ * launches only (key kernel, one radix sort, gather kernel), no allocation, no synchronisation. */
+int icon_train_rows_bytes(int B, int64_t N, int S, int C, int H, int W, int64_t *bytes);
+int icon_train_rows_forward(const icon_mesh_batch_t *mb, int prior_type, float sdf_clip, int cmap_mode, int has_vis,
+                            int has_cmap, int has_norm, const float *const *d_stacks, const int32_t *stack_shapes, int S,
+                            const float *d_calibs, const float *d_points, int64_t N, float *d_rows, float *d_in_cube,
+                            void *d_taps, int search, icon_work_t *work, void *stream);
+int icon_train_rows_backward(const float *d_grad_rows, const void *d_taps, int S, uint32_t stack_mask, int B, int Cin, int C,
+                             int H, int W, int n_select, int64_t N, float *d_grad_planes, void *d_scratch,
+                             int64_t scratch_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
