@@ -25,6 +25,7 @@ import torch
 
 from . import _lib
 from ._lib import IconAmdError, check
+from ._native import need_device, scratch_for, stream
 
 TERMS = {"edge": 1, "nc": 2, "laplacian": 4}                              # include/icon_amd.h: ICON_PRIOR_*
 
@@ -142,18 +143,8 @@ class ClothTopology:
         return out
 
 
-def _scratch(device: torch.device, nbytes: int) -> torch.Tensor:
-    from .render import _rn_scratch                                       # one pool per (thread, device, stream), shared with the renderer
-    return _rn_scratch(device, nbytes)
-
-
-def _need_device(what: str) -> None:
-    if not torch.cuda.is_available():
-        raise IconAmdError(f"{what} needs the HIP device (there is no CPU fallback)")
-
-
 def _on_device(what: str, topo: ClothTopology, *tensors) -> None:
-    _need_device(what)
+    need_device(what)
     dev = tensors[0].device
     if not all(t.is_cuda and t.device == dev for t in tensors) or topo.device != dev:
         raise IconAmdError(f"{what}: the tensors and the topology must live on one HIP device (ClothTopology.to(device) moves it)")
@@ -168,26 +159,22 @@ class _LocalAffineFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, A, b, topo):
-        from .engine import _stream
         B, V, E = x.shape[0], x.shape[1], topo.num_edges
         L = _lib.lib()
         with torch.cuda.device(x.device):
-            nbytes = C.c_int64(0)
-            check(L.icon_local_affine_bytes(C.c_int64(B), C.c_int64(V), C.c_int64(E), C.byref(nbytes)), "icon_local_affine_bytes")
-            scratch = _scratch(x.device, nbytes.value)
+            scratch = scratch_for(x.device, "icon_local_affine_bytes", C.c_int64(B), C.c_int64(V), C.c_int64(E))
             y = torch.empty_like(x)
             stiff = torch.empty((), dtype=torch.float32, device=x.device)
             rigid = torch.empty((), dtype=torch.float32, device=x.device)
             check(L.icon_local_affine_forward(_lib.ptr(x), _lib.ptr(A), _lib.ptr(b), C.c_int64(B), C.c_int64(V), _lib.ptr(topo.edges),
                                               C.c_int64(E), _i64(topo), _lib.ptr(y), _lib.ptr(stiff), _lib.ptr(rigid),
-                                              _lib.ptr(scratch), C.c_int64(scratch.numel()), _stream()), "icon_local_affine_forward")
+                                              _lib.ptr(scratch), C.c_int64(scratch.numel()), stream()), "icon_local_affine_forward")
         ctx.save_for_backward(x, A, b)
         ctx.topo = topo
         return y, stiff, rigid
 
     @staticmethod
     def backward(ctx, gy, gs, gr):
-        from .engine import _stream
         x, A, b = ctx.saved_tensors
         topo = ctx.topo
         B, V, E = x.shape[0], x.shape[1], topo.num_edges
@@ -197,7 +184,7 @@ class _LocalAffineFn(torch.autograd.Function):
             gA, gb = torch.empty_like(A), torch.empty_like(b)
             check(L.icon_local_affine_backward(_lib.ptr(x), _lib.ptr(A), _lib.ptr(b), C.c_int64(B), C.c_int64(V), _lib.ptr(topo.nbr_off),
                                                _lib.ptr(topo.nbr), C.c_int64(E), _i64(topo), _lib.ptr(gy), _lib.ptr(gs), _lib.ptr(gr),
-                                               _lib.ptr(gA), _lib.ptr(gb), _stream()), "icon_local_affine_backward")
+                                               _lib.ptr(gA), _lib.ptr(gb), stream()), "icon_local_affine_backward")
         return None, gA, gb, None
 
 
@@ -262,7 +249,7 @@ class LocalAffine(torch.nn.Module):
     def forward(self, x, return_stiff=False):
         if return_stiff and self.edges is None:
             raise IconAmdError("LocalAffine: return_stiff=True needs the edges the model was built without")
-        _need_device("LocalAffine")
+        need_device("LocalAffine")
         y, stiffness, rigid = local_affine_device(x, self.A, self.b, self._topology(self.A.device))
         return (y, stiffness, rigid) if return_stiff else y
 
@@ -274,10 +261,7 @@ def _mp_args(v, topo, target_length, mask):
 
 
 def _mp_scratch(v, topo):
-    nbytes = C.c_int64(0)
-    check(_lib.lib().icon_mesh_priors_bytes(C.c_int64(v.shape[0]), C.c_int64(topo.num_edges), C.c_int64(topo.num_pairs), C.byref(nbytes)),
-          "icon_mesh_priors_bytes")
-    return _scratch(v.device, nbytes.value)
+    return scratch_for(v.device, "icon_mesh_priors_bytes", C.c_int64(v.shape[0]), C.c_int64(topo.num_edges), C.c_int64(topo.num_pairs))
 
 
 class _MeshPriorsFn(torch.autograd.Function):
@@ -285,20 +269,18 @@ class _MeshPriorsFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, v, topo, target_length, mask):
-        from .engine import _stream
         head, tail = _mp_args(v, topo, target_length, mask)
         with torch.cuda.device(v.device):
             scratch = _mp_scratch(v, topo)
             out = [torch.empty((), dtype=torch.float32, device=v.device) for _ in range(3)]
             check(_lib.lib().icon_mesh_priors_forward(*head, _lib.ptr(topo.pairs), *tail, *(_lib.ptr(o) for o in out),
-                                                      _lib.ptr(scratch), C.c_int64(scratch.numel()), _stream()), "icon_mesh_priors_forward")
+                                                      _lib.ptr(scratch), C.c_int64(scratch.numel()), stream()), "icon_mesh_priors_forward")
         ctx.save_for_backward(v)
         ctx.topo, ctx.target_length, ctx.mask = topo, target_length, mask
         return tuple(out)
 
     @staticmethod
     def backward(ctx, g_edge, g_nc, g_lap):
-        from .engine import _stream
         v, = ctx.saved_tensors
         topo = ctx.topo
         head, tail = _mp_args(v, topo, ctx.target_length, ctx.mask)
@@ -308,7 +290,7 @@ class _MeshPriorsFn(torch.autograd.Function):
             grad = torch.empty_like(v)
             check(_lib.lib().icon_mesh_priors_backward(*head, _lib.ptr(topo.pairs), _lib.ptr(topo.inc_off), _lib.ptr(topo.inc), *tail,
                                                        *(_lib.ptr(t) for t in g), _lib.ptr(grad), _lib.ptr(scratch), C.c_int64(scratch.numel()),
-                                                       _stream()), "icon_mesh_priors_backward")
+                                                       stream()), "icon_mesh_priors_backward")
         return grad, None, None, None
 
 

@@ -207,17 +207,16 @@ extern "C" int icon_clean_mesh(const float *d_verts, int64_t V, const int64_t *d
     unsigned slots = 1024;
     while ((int64_t)slots < 6 * F) slots <<= 1;                 // 3 F keys at most: the table stays at most half full
     const int64_t nbf = (F + 255) / 256, nbv = (V + 255) / 256;
-    size_t o = 0;
-    auto take = [&](size_t bytes) { const size_t at = o; o = (o + bytes + 255) / 256 * 256; return at; };
+    ScratchTake take;
     const size_t o_keys = take((size_t)slots * 8), o_cnt = take((size_t)slots * 4), o_f0 = take((size_t)slots * 4), o_f1 = take((size_t)slots * 4);
     const size_t o_slot = take((size_t)F * 12);
     const size_t o_parent = take((size_t)F * 4), o_label = take((size_t)F * 4), o_cv = take((size_t)F * 4), o_best = take(8);
     const size_t o_kf = take((size_t)F), o_kv = take((size_t)V), o_bf = take((size_t)nbf * 4), o_bv = take((size_t)nbv * 4);
     const size_t o_remap = take((size_t)V * 4), o_tot = take(16);
-    if (o > s->bytes) {
+    if (take.o > s->bytes) {
         (void)hipFree(s->buf); s->buf = nullptr; s->bytes = 0;
-        ICON_HIP(hipMalloc((void **)&s->buf, o));
-        s->bytes = o;
+        ICON_HIP(hipMalloc((void **)&s->buf, take.o));
+        s->bytes = take.o;
     }
     CleanCtx c{};
     c.verts = d_verts; c.faces = d_faces; c.V = V; c.F = F;

@@ -383,12 +383,6 @@ int mp_check(const char *who, int64_t V, int64_t E, int64_t P)
     ICON_ARG(V <= kMaxItems && E <= kMaxItems && P <= kMaxItems / 4, std::string(who) + ": V, E and 4 P must not exceed 2^38");
     return ICON_OK;
 }
-int scratch_check(const char *who, const char *query, const void *d_scratch, int64_t scratch_bytes, size_t need)
-{
-    ICON_ARG(((uintptr_t)d_scratch & 255) == 0, std::string(who) + ": the scratch must be 256-byte aligned");
-    ICON_ARG(scratch_bytes >= (int64_t)need, std::string(who) + ": the scratch is smaller than " + query + " asks for");
-    return ICON_OK;
-}
 int terms_check(const char *who, int terms, int64_t E, int64_t P, const void *edges, const void *nbr_off, const void *nbr, const void *pairs,
                 bool need_inc, const void *inc_off, const void *inc)
 {

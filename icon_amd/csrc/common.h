@@ -28,6 +28,21 @@ int fail(int code, const std::string &msg);
         if (!(cond)) return ::icon::fail(ICON_ERR_ARG, std::string(msg));    \
     } while (0)
 
+// ---- a call's scratch (host) ----------------------------------------------------------------
+// carves 256-byte aligned pieces out of a scratch: take(bytes) -> the piece's offset; `o` is the total so far
+struct ScratchTake {
+    size_t o = 0;
+    size_t operator()(size_t bytes) { const size_t at = o; o = (o + bytes + 255) / 256 * 256; return at; }
+};
+
+// the scratch an entry `who` was handed against the `need` its `bytes_name` entry reports
+inline int scratch_check(const std::string &who, const std::string &bytes_name, const void *d_scratch, int64_t scratch_bytes, size_t need)
+{
+    ICON_ARG(((uintptr_t)d_scratch & 255) == 0, who + ": the scratch must be 256-byte aligned");
+    ICON_ARG(scratch_bytes >= (int64_t)need, who + ": scratch smaller than " + bytes_name);
+    return ICON_OK;
+}
+
 // ---- device data layouts (HBM) --------------------------------------------------------------
 // BVH2 node, 64 B (one cache line): both children's boxes live in the parent so one load
 // decides both.  child >= 0: internal node index; child < 0: leaf, ~child = (leaf id << 2) |

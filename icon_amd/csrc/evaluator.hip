@@ -219,7 +219,7 @@ struct EvLayout { size_t cnt[2]; S1Layout s1[2]; size_t nrm[2], zb, partial, tot
 EvLayout ev_layout(const int64_t V[2], const int64_t F[2], int n_mesh, int S, int K)
 {
     EvLayout L{};
-    S1Take take;
+    ScratchTake take;
     for (int mi = 0; mi < n_mesh; ++mi) {
         L.cnt[mi] = take((size_t)kEvMaxViews * 4);                          // directly in front of the S1 header: one range to clear
         L.s1[mi] = s1_layout(take, V[mi], F[mi], (size_t)F[mi] * 4 * K);
@@ -287,9 +287,8 @@ extern "C" int icon_normal_consistency(const float *d_verts_a, int64_t Va, const
     const int rc = ev_check_sizes(V, F, n_mesh, size, n_views);
     if (rc) return rc;
     const EvLayout L = ev_layout(V, F, n_mesh, size, n_views);
-    ICON_ARG(((uintptr_t)d_scratch & 255) == 0, "icon_normal_consistency: the scratch must be 256-byte aligned");
+    if (const int e = scratch_check("icon_normal_consistency", "icon_normal_consistency_bytes", d_scratch, scratch_bytes, L.total)) return e;
     ICON_ARG((((uintptr_t)d_rgba_a | (uintptr_t)d_rgba_b) & 15) == 0, "icon_normal_consistency: the RGBA outputs must be 16-byte aligned");
-    ICON_ARG(scratch_bytes >= (int64_t)L.total, "icon_normal_consistency: scratch smaller than icon_normal_consistency_bytes");
     hipStream_t st = (hipStream_t)stream;
     char *s = static_cast<char *>(d_scratch);
     const float *verts[2] = { d_verts_a, d_verts_b }, *normals[2] = { d_normals_a, d_normals_b };

@@ -141,13 +141,12 @@ struct GmLayout { size_t totals, ref_v, zero_end, sel, nn, keep_f, blk_f, blk_v,
 GmLayout gm_layout(int64_t V, int64_t F)
 {
     GmLayout L{};
-    size_t o = 0;
-    auto take = [&](size_t bytes) { const size_t at = o; o = (o + bytes + 255) / 256 * 256; return at; };
+    ScratchTake take;
     L.totals = take(16); L.ref_v = take((size_t)V);
-    L.zero_end = o;                                                            // [0, zero_end): cleared by one memset per call
+    L.zero_end = take.o;                                                       // [0, zero_end): cleared by one memset per call
     L.sel = take((size_t)V); L.nn = take((size_t)V * 4); L.keep_f = take((size_t)F);
     L.blk_f = take((size_t)((F + 255) / 256) * 4); L.blk_v = take((size_t)((V + 255) / 256) * 4); L.remap = take((size_t)V * 4);
-    L.total = o;
+    L.total = take.o;
     return L;
 }
 
@@ -198,9 +197,8 @@ extern "C" int icon_extract_cloth(const float *d_verts, int64_t V, const void *d
     const bool with_src = d_src || Vs || d_src_remove;
     ICON_ARG(!with_src || (d_src && d_src_remove && Vs > 0 && Vs < (1ll << 31)),
              "icon_extract_cloth: d_src, Vs and d_src_remove go together (all NULL / 0: no source mesh), 0 < Vs < 2^31");
-    ICON_ARG(((uintptr_t)d_scratch & 255) == 0, "icon_extract_cloth: the scratch must be 256-byte aligned");
     const GmLayout L = gm_layout(V, F);
-    ICON_ARG(scratch_bytes >= (int64_t)L.total, "icon_extract_cloth: scratch smaller than icon_extract_cloth_bytes");
+    if (const int e = scratch_check("icon_extract_cloth", "icon_extract_cloth_bytes", d_scratch, scratch_bytes, L.total)) return e;
     hipStream_t st = (hipStream_t)stream;
     char *s = static_cast<char *>(d_scratch);
     GmCtx c{};

@@ -206,15 +206,14 @@ struct QcLayout { size_t hdr, deg, cur, vis, zero_end, loc, part, inc, tmp, big,
 QcLayout qc_layout(int64_t V, int64_t F, int S)
 {
     QcLayout L{};
-    size_t o = 0;
-    auto take = [&](size_t bytes) { const size_t at = o; o = (o + bytes + 255) / 256 * 256; return at; };
+    ScratchTake take;
     L.hdr = take(sizeof(QcHdr)); L.deg = take((size_t)V * 4); L.cur = take((size_t)V * 4); L.vis = take((size_t)V * 4);
-    L.zero_end = o;                                                        // [0, zero_end): cleared by one memset per call
+    L.zero_end = take.o;                                                   // [0, zero_end): cleared by one memset per call
     L.loc = take((size_t)V * 4); L.part = take((size_t)((V + kScanItems - 1) / kScanItems) * 4);
     L.inc = take((size_t)F * 12); L.tmp = take((size_t)F * 12);
     L.big = take((size_t)F * 4); L.longv = take((size_t)V * 4);
     L.zb = take((size_t)(S / 2) * (S / 2) * 8);
-    L.total = o;
+    L.total = take.o;
     return L;
 }
 
@@ -268,9 +267,8 @@ extern "C" int icon_query_color(const float *d_verts, int64_t V, const void *d_f
     const int rc = qc_check_sizes(V, F, image_size);
     if (rc) return rc;
     ICON_ARG(H > 0 && W > 0 && (int64_t)H * W < (1ll << 31), "icon_query_color: bad image size");
-    ICON_ARG(((uintptr_t)d_scratch & 255) == 0, "icon_query_color: the scratch must be 256-byte aligned");
     const QcLayout L = qc_layout(V, F, image_size);
-    ICON_ARG(scratch_bytes >= (int64_t)L.total, "icon_query_color: scratch smaller than icon_query_color_bytes");
+    if (const int e = scratch_check("icon_query_color", "icon_query_color_bytes", d_scratch, scratch_bytes, L.total)) return e;
     hipStream_t st = (hipStream_t)stream;
     char *s = static_cast<char *>(d_scratch);
     QcCtx c{};

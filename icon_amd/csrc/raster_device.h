@@ -312,8 +312,7 @@ int rs_context(const std::string &name, const char *bytes_name, const float *d_v
         ICON_ARG(cam_ids[k] >= 0 && cam_ids[k] <= 3, name + ": cam_ids must be 0..3");
         cams |= cam_ids[k] << (2 * k);
     }
-    ICON_ARG(((uintptr_t)d_scratch & 255) == 0, name + ": the scratch must be 256-byte aligned");
-    ICON_ARG(scratch_bytes >= (int64_t)total, name + ": scratch smaller than " + bytes_name);
+    if (const int e = scratch_check(name, bytes_name, d_scratch, scratch_bytes, total)) return e;
     c.verts = d_verts; c.faces = d_faces; c.V = V; c.F = F; c.S = size; c.n_views = n_views; c.cams = cams; c.flip = n_views == 2 ? 1 : 0;
     return ICON_OK;
 }

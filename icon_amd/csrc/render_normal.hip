@@ -147,7 +147,7 @@ struct RnLayout { S1Layout s1; size_t nrm, zb, total; };            // the defer
 RnLayout rn_layout(int64_t V, int64_t F, int S, int n_views)
 {
     RnLayout L{};
-    S1Take take;
+    ScratchTake take;
     L.s1 = s1_layout(take, V, F, (size_t)F * 4 * n_views);
     L.nrm = take((size_t)V * 12);
     L.zb = take((size_t)n_views * S * S * 8);

@@ -325,7 +325,7 @@ struct RnbLayout { S1Layout s1; size_t big, Nv, gNv, gn, gxy, fc, total; };
 RnbLayout rnb_layout(int64_t V, int64_t F, int n_views)
 {
     RnbLayout L{};
-    S1Take take;
+    ScratchTake take;
     L.s1 = s1_layout(take, V, F);
     L.big = take((size_t)F * 4 * n_views);
     L.Nv = take((size_t)V * 12); L.gNv = take((size_t)V * 12);

@@ -37,14 +37,10 @@ struct S1Ctx {
 struct S1Hdr { int bad_faces, n_big, n_long, pad; };
 
 // ---- host: the S1 pieces of a call's scratch, 256-byte aligned; [0, zero_end) is what the call's clear sets to 0 ----
-struct S1Take {
-    size_t o = 0;
-    size_t operator()(size_t bytes) { const size_t at = o; o = (o + bytes + 255) / 256 * 256; return at; }
-};
 struct S1Layout { size_t hdr, deg, cur, zero_end, loc, part, inc, tmp, mid, longv; };
 
 // appends the pieces to `take`; mid: `mid_bytes` of the caller's own between tmp and longv (render_normal.hip's deferred list lives there)
-S1Layout s1_layout(S1Take &take, int64_t V, int64_t F, size_t mid_bytes = 0)
+S1Layout s1_layout(ScratchTake &take, int64_t V, int64_t F, size_t mid_bytes = 0)
 {
     S1Layout L{};
     L.hdr = take(sizeof(S1Hdr)); L.deg = take((size_t)V * 4); L.cur = take((size_t)V * 4);

@@ -177,10 +177,9 @@ struct SgLayout { size_t all, inside, total; };
 SgLayout sg_layout(int64_t n)
 {
     SgLayout L{};
-    size_t o = 0;
-    auto take = [&](size_t bytes) { const size_t at = o; o = (o + bytes + 255) / 256 * 256; return at; };
+    ScratchTake take;
     L.all = take((size_t)n * 12); L.inside = take((size_t)n);
-    L.total = o;
+    L.total = take.o;
     return L;
 }
 
@@ -219,9 +218,8 @@ extern "C" int icon_sample_geo(const icon_mesh_t *scan, const float *d_verts, co
     while ((1ll << (2 * p.half_bits)) < p.n) ++p.half_bits;
     p.sigma = sigma_geo; p.seed = seed;
     for (int k = 0; k < 12; ++k) { p.calib[k] = calib[k]; p.calib_inv[k] = calib_inv[k]; }
-    ICON_ARG(((uintptr_t)d_scratch & 255) == 0, "icon_sample_geo: the scratch must be 256-byte aligned");
     const SgLayout L = sg_layout(p.n);
-    ICON_ARG(scratch_bytes >= (int64_t)L.total, "icon_sample_geo: scratch smaller than icon_sample_geo_bytes");
+    if (const int e = scratch_check("icon_sample_geo", "icon_sample_geo_bytes", d_scratch, scratch_bytes, L.total)) return e;
     char *s = static_cast<char *>(d_scratch);
     float *all = d_all_samples ? d_all_samples : reinterpret_cast<float *>(s + L.all);
     uint8_t *inside = d_all_inside ? d_all_inside : reinterpret_cast<uint8_t *>(s + L.inside);

@@ -194,7 +194,7 @@ struct SilLayout { S1Layout s1; size_t rec, box, cg, total; };
 SilLayout sil_layout(int64_t V, int64_t F, int n_views)
 {
     SilLayout L{};
-    S1Take take;
+    ScratchTake take;
     L.s1 = s1_layout(take, V, F);
     L.rec = take((size_t)F * n_views * sizeof(SilRec)); L.box = take((size_t)F * n_views * sizeof(SilBox));
     L.cg = take((size_t)F * n_views * 24);

@@ -426,8 +426,7 @@ extern "C" int icon_smpl_backward(const icon_smpl_tables *tables, const float *d
     ICON_ARG(d_A && d_grad_rot_mats && (tables->NB == 0 || d_grad_betas) && d_scratch, std::string(who) + ": null argument");
     int64_t need = 0;
     icon_smpl_bytes(B, tables->V, tables->J, tables->NB, tables->K, &need);
-    ICON_ARG(((uintptr_t)d_scratch & 255) == 0, std::string(who) + ": the scratch must be 256-byte aligned");
-    ICON_ARG(scratch_bytes >= need, std::string(who) + ": the scratch is smaller than icon_smpl_bytes asks for");
+    if (const int e = scratch_check(who, "icon_smpl_bytes", d_scratch, scratch_bytes, (size_t)need)) return e;
     c.A = const_cast<float *>(d_A); c.g_verts = d_grad_verts; c.g_joints = d_grad_joints;
     c.g_betas = d_grad_betas; c.g_rot = d_grad_rot_mats; c.part = static_cast<double *>(d_scratch);
     hipStream_t st = (hipStream_t)stream;

@@ -194,11 +194,10 @@ int tr_layout(int64_t NB, uint32_t sentinel, TrLayout *L)
     size_t tmp = 0;
     ICON_HIP(rocprim::radix_sort_pairs(nullptr, tmp, (uint32_t *)nullptr, (uint32_t *)nullptr, (int32_t *)nullptr, (int32_t *)nullptr,
                                        (size_t)NB, 0, end_bit, (hipStream_t)nullptr));
-    size_t o = 0;
-    auto take = [&](size_t bytes) { const size_t at = o; o = (o + bytes + 255) / 256 * 256; return at; };
+    ScratchTake take;
     L->keys = take(2 * (size_t)NB * sizeof(uint32_t)); L->idx = take(2 * (size_t)NB * sizeof(int32_t));
     L->tmp = take(tmp); L->tmp_bytes = tmp;
-    L->total = o; L->end_bit = end_bit;
+    L->total = take.o; L->end_bit = end_bit;
     return ICON_OK;
 }
 
@@ -310,8 +309,7 @@ extern "C" int icon_train_rows_backward(const float *d_grad_rows, const void *d_
     const int64_t NB = N * (int64_t)B;
     TrLayout L;
     if ((rc = tr_layout(NB, q.sentinel, &L))) return rc;
-    ICON_ARG(((uintptr_t)d_scratch & 255) == 0, std::string(what) + ": the scratch must be 256-byte aligned");
-    ICON_ARG(scratch_bytes >= (int64_t)L.total, std::string(what) + ": scratch smaller than icon_train_rows_bytes");
+    if ((rc = scratch_check(what, "icon_train_rows_bytes", d_scratch, scratch_bytes, L.total))) return rc;
     char *s = static_cast<char *>(d_scratch);
     uint32_t *k0 = reinterpret_cast<uint32_t *>(s + L.keys), *k1 = k0 + NB;
     int32_t *i0 = reinterpret_cast<int32_t *>(s + L.idx), *i1 = i0 + NB;

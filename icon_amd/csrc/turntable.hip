@@ -202,7 +202,7 @@ struct TtLayout { S1Layout s1; size_t nrm, zb, total; };            // the defer
 TtLayout tt_layout(int64_t V, int64_t F, int S, int chunk)
 {
     TtLayout L{};
-    S1Take take;
+    ScratchTake take;
     L.s1 = s1_layout(take, V, F, (size_t)F * 4 * chunk);
     L.nrm = take((size_t)V * 12);
     L.zb = take((size_t)chunk * S * S * 8);
@@ -255,8 +255,7 @@ extern "C" int icon_render_turntable(const float *d_verts, int64_t V, const void
              "icon_render_turntable: the panel must lie inside the canvas: 0 <= x0, x0 + size <= canvas_width <= 2^31");
     const int chunk = tt_chunk(n_views);
     const TtLayout L = tt_layout(V, F, size, chunk);
-    ICON_ARG(((uintptr_t)d_scratch & 255) == 0, "icon_render_turntable: the scratch must be 256-byte aligned");
-    ICON_ARG(scratch_bytes >= (int64_t)L.total, "icon_render_turntable: scratch smaller than icon_render_turntable_bytes");
+    if (const int e = scratch_check("icon_render_turntable", "icon_render_turntable_bytes", d_scratch, scratch_bytes, L.total)) return e;
     hipStream_t st = (hipStream_t)stream;
     char *s = static_cast<char *>(d_scratch);
     TtCtx c{};

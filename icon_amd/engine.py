@@ -26,10 +26,7 @@ import torch.nn as nn
 
 from . import _lib
 from ._lib import IconAmdError, check, ptr
-
-
-def _stream() -> C.c_void_p:
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+from ._native import need_device, stream as _stream
 
 
 def _on(t: torch.Tensor):
@@ -1217,8 +1214,7 @@ def get_visibility(xy: torch.Tensor, z: torch.Tensor, faces: torch.Tensor, image
     as in the reference).  Inputs may live on the host (the reference's call sites pass CPU tensors,
     TestDataset.py:134-137) - they are moved to the current HIP device; the result comes back on
     the device of ``z``.  No pytorch3d involved."""
-    if not torch.cuda.is_available():
-        raise IconAmdError("get_visibility needs the HIP device (there is no CPU fallback)")
+    need_device("get_visibility")
     dev = torch.device("cuda", torch.cuda.current_device())
     out_dev = z.device
     xy_d = xy.detach().to(dev, torch.float32).reshape(-1, 2).contiguous()

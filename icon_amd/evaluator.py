@@ -26,7 +26,8 @@ import torch
 
 from . import _lib
 from ._lib import IconAmdError, check
-from .render import _check_mesh, _check_size, _rn_scratch, _rn_tls
+from ._native import constants, faces_arg, scratch_for, stream
+from .render import _check_mesh, _check_size
 
 MAX_VIEWS = 32
 
@@ -53,20 +54,6 @@ def view_matrices(degs, scale_factor: float = 1.0, offset: float = 0.0) -> np.nd
         out[k, :, :3] = euler_to_rot_mat(0, deg / 180.0 * np.pi, 0) * float(scale_factor)
         out[k, 1, 3] = float(offset)
     return out.astype(np.float32)
-
-
-def _views_on_device(device: torch.device, mats: np.ndarray, muls: np.ndarray):
-    """the view matrices and multipliers on the device, kept per (thread, device, stream) like the scratch: a repeated call
-    uploads nothing, so it can be captured into a graph"""
-    cache = getattr(_rn_tls, "ev_views", None)
-    if cache is None or len(cache) > 64:
-        cache = _rn_tls.ev_views = {}
-    idx = device.index if device.index is not None else torch.cuda.current_device()
-    key = (idx, torch.cuda.current_stream(idx).cuda_stream, mats.tobytes(), muls.tobytes())
-    if key not in cache:
-        dev = torch.device("cuda", idx)
-        cache[key] = (torch.from_numpy(mats).to(dev), torch.from_numpy(muls).to(dev))
-    return cache[key]
 
 
 def _check_views(degs, mats, muls, scale_factor, offset):
@@ -116,7 +103,6 @@ def normal_consistency_device(verts_a, faces_a, verts_b=None, faces_b=None, degs
     ONE native call enqueued on the current stream, launches only: nothing is allocated by it, nothing read back, the stream is
     not waited for - so a face that names a vertex that does not exist cannot raise here; it is skipped.  Equal bytes from run
     to run.  Not differentiable.  Bad input raises ``IconAmdError`` before anything is launched."""
-    from .engine import _stream
     size = _check_size(size)
     single = verts_b is None and faces_b is None
     if not single and (verts_b is None or faces_b is None):
@@ -134,12 +120,10 @@ def normal_consistency_device(verts_a, faces_a, verts_b=None, faces_b=None, degs
     dev, K = va.device, mats.shape[0]
     L = _lib.lib()
     with torch.cuda.device(dev):
-        d_mats, d_muls = _views_on_device(dev, mats, muls)
+        d_mats, d_muls = constants(dev, mats, muls)
         Vb, Fb = (0, 0) if single else (vb.shape[0], fb.shape[0])
-        nbytes = C.c_int64(0)
-        check(L.icon_normal_consistency_bytes(C.c_int64(va.shape[0]), C.c_int64(fa.shape[0]), C.c_int64(Vb), C.c_int64(Fb), C.c_int(size),
-                                              C.c_int(K), C.byref(nbytes)), "icon_normal_consistency_bytes")
-        scratch = _rn_scratch(dev, nbytes.value)
+        scratch = scratch_for(dev, "icon_normal_consistency_bytes", C.c_int64(va.shape[0]), C.c_int64(fa.shape[0]), C.c_int64(Vb), C.c_int64(Fb),
+                              C.c_int(size), C.c_int(K))
         images = return_images or single
         err = None if single else torch.empty(K, dtype=torch.float64, device=dev)
         rgba_a = torch.empty((K, size, size, 4), dtype=torch.float32, device=dev) if images else None
@@ -148,12 +132,12 @@ def normal_consistency_device(verts_a, faces_a, verts_b=None, faces_b=None, degs
         pix_b = torch.empty((K, size, size), dtype=torch.int32, device=dev) if return_faces and not single else None
         out_a = torch.empty_like(va) if return_normals and na is None else None
         out_b = torch.empty_like(vb) if return_normals and not single and nb is None else None
-        i64 = lambda f: C.c_int(1 if f is not None and f.dtype == torch.int64 else 0)
+        i64 = lambda f: C.c_int(0) if f is None else faces_arg(f)[1]
         check(L.icon_normal_consistency(_lib.ptr(va), C.c_int64(va.shape[0]), _lib.ptr(fa), C.c_int64(fa.shape[0]), i64(fa), _lib.ptr(na),
                                         _lib.ptr(vb), C.c_int64(Vb), _lib.ptr(fb), C.c_int64(Fb), i64(fb), _lib.ptr(nb),
                                         _lib.ptr(d_mats), _lib.ptr(d_muls), C.c_int(K), C.c_int(size), _lib.ptr(err),
                                         _lib.ptr(rgba_a), _lib.ptr(rgba_b), _lib.ptr(pix_a), _lib.ptr(pix_b), _lib.ptr(out_a), _lib.ptr(out_b),
-                                        _lib.ptr(scratch), C.c_int64(scratch.numel()), _stream()), "icon_normal_consistency")
+                                        _lib.ptr(scratch), C.c_int64(scratch.numel()), stream()), "icon_normal_consistency")
     nrm_a, nrm_b = (na if na is not None else out_a), (nb if nb is not None else out_b)
     if single:
         out = (rgba_a,) + ((pix_a,) if return_faces else ()) + ((nrm_a,) if return_normals else ())

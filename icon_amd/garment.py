@@ -19,7 +19,6 @@ merged here (the meshes of this pipeline have none).  Coordinates given in float
 from __future__ import annotations
 
 import ctypes as C
-import threading
 from typing import Optional, Sequence
 
 import numpy as np
@@ -27,6 +26,7 @@ import torch
 
 from . import _lib
 from ._lib import IconAmdError, check
+from ._native import faces_arg, need_device, scratch_for, stream
 
 # csrc/garment.hip: kPolyTile, kSrcTile, kSrcSplit - the sizes at which the kernels take another path (tests pick shapes around them)
 POLY_TILE, SRC_TILE, SRC_SPLIT = 256, 512, 128
@@ -128,23 +128,6 @@ def _pack_polygons(polygons, what: str):
 
 # ---- the device side ---------------------------------------------------------------------------------------------------------
 
-_tls = threading.local()
-
-
-def _scratch(device: torch.device, nbytes: int) -> torch.Tensor:
-    """the call's scratch: one tensor per (thread, device, stream), grown on demand and reused - per stream for the reasons
-    recon._qc_scratch gives: two calls on two streams may run at once, and the allocator orders reuse per stream"""
-    pool = getattr(_tls, "pool", None)
-    if pool is None:
-        pool = _tls.pool = {}
-    idx = device.index if device.index is not None else torch.cuda.current_device()
-    key = (idx, torch.cuda.current_stream(idx).cuda_stream)
-    buf = pool.get(key)
-    if buf is None or buf.numel() < nbytes:
-        buf = pool[key] = torch.empty(nbytes, dtype=torch.uint8, device=torch.device("cuda", idx))
-    return buf
-
-
 def _check_points(t, name: str, what: str):
     if not torch.is_tensor(t):
         raise IconAmdError(f"{what}: {name} must be a tensor, got {type(t).__name__}")
@@ -155,8 +138,7 @@ def _check_points(t, name: str, what: str):
 
 
 def _check_device(what: str, **tensors):
-    if not torch.cuda.is_available():
-        raise IconAmdError(f"{what} needs the HIP device (there is no CPU fallback)")
+    need_device(what)
     devs = {n: t.device for n, t in tensors.items() if t is not None}
     first = next(iter(devs.values()))
     if any(not t.is_cuda for t in tensors.values() if t is not None) or any(d != first for d in devs.values()):
@@ -169,7 +151,6 @@ def nearest_vertex_device(verts: torch.Tensor, src_verts: torch.Tensor, only: Op
     source vertex at the smallest float64 squared distance (rule 3; numpy's ``((q - s)**2).sum(-1).argmin()``).  ``only``: bool or
     uint8 ``[V]``; a vertex whose entry is 0 is skipped and gets -1.  One native launch (icon_nearest_vertex) on the current
     stream: nothing is allocated by it, nothing waited for."""
-    from .engine import _stream
     what = "nearest_vertex_device"
     _check_points(verts, "verts", what)
     _check_points(src_verts, "src_verts", what)
@@ -189,7 +170,7 @@ def nearest_vertex_device(verts: torch.Tensor, src_verts: torch.Tensor, only: Op
         return out
     with torch.cuda.device(dev):
         check(_lib.lib().icon_nearest_vertex(_lib.ptr(v), C.c_int64(v.shape[0]), _lib.ptr(s), C.c_int64(s.shape[0]), _lib.ptr(o),
-                                             _lib.ptr(out), _stream()), "icon_nearest_vertex")
+                                             _lib.ptr(out), stream()), "icon_nearest_vertex")
     return out
 
 
@@ -214,7 +195,6 @@ def extract_cloth_device(verts: torch.Tensor, faces: torch.Tensor, polygons: Seq
     int32, the input index of every output vertex - or ``None`` when no face is kept.  A face that names a vertex that does
     not exist is never kept.  The call waits for the stream once, for the two counts; its scratch is cached per (thread, device,
     stream)."""
-    from .engine import _stream
     what = "extract_cloth_device"
     _check_points(verts, "verts", what)
     if not torch.is_tensor(faces) or faces.dtype.is_floating_point or faces.dtype == torch.bool:
@@ -237,28 +217,22 @@ def extract_cloth_device(verts: torch.Tensor, faces: torch.Tensor, polygons: Seq
     if V == 0 or F == 0:
         return None
     v = verts.detach().to(torch.float32).contiguous()
-    f = faces.detach()
-    if f.dtype not in (torch.int32, torch.int64):
-        f = f.to(torch.int64)
-    f = f.contiguous()
+    f, f_i64 = faces_arg(faces)
     s = None if src_verts is None else src_verts.detach().to(torch.float32).contiguous()
     r = None if src_remove is None else src_remove.detach().to(torch.uint8).contiguous()
     L = _lib.lib()
     with torch.cuda.device(dev):
         d_xy = torch.from_numpy(xy).to(dev)
         d_off = torch.from_numpy(off).to(dev)
-        nbytes = C.c_int64(0)
-        check(L.icon_extract_cloth_bytes(C.c_int64(V), C.c_int64(F), C.c_int64(xy.shape[0]), C.c_int64(len(off) - 1), C.byref(nbytes)),
-              "icon_extract_cloth_bytes")
-        scratch = _scratch(dev, nbytes.value)
+        scratch = scratch_for(dev, "icon_extract_cloth_bytes", C.c_int64(V), C.c_int64(F), C.c_int64(xy.shape[0]), C.c_int64(len(off) - 1))
         ov = torch.empty((V, 3), dtype=torch.float32, device=dev)
         of = torch.empty((F, 3), dtype=torch.int32, device=dev)
         ids = torch.empty(V, dtype=torch.int32, device=dev)
         hc = (C.c_int64 * 2)()
-        check(L.icon_extract_cloth(_lib.ptr(v), C.c_int64(V), _lib.ptr(f), C.c_int64(F), C.c_int(1 if f.dtype == torch.int64 else 0),
+        check(L.icon_extract_cloth(_lib.ptr(v), C.c_int64(V), _lib.ptr(f), C.c_int64(F), f_i64,
                                    _lib.ptr(d_xy), _lib.ptr(d_off), C.c_int64(xy.shape[0]), C.c_int64(len(off) - 1),
                                    _lib.ptr(s), C.c_int64(0 if s is None else s.shape[0]), _lib.ptr(r),
-                                   _lib.ptr(ov), _lib.ptr(of), _lib.ptr(ids), hc, _lib.ptr(scratch), C.c_int64(scratch.numel()), _stream()),
+                                   _lib.ptr(ov), _lib.ptr(of), _lib.ptr(ids), hc, _lib.ptr(scratch), C.c_int64(scratch.numel()), stream()),
               "icon_extract_cloth")
     nv, nf = int(hc[0]), int(hc[1])
     if nf == 0:
@@ -334,8 +308,7 @@ def extract_cloth(recon, segmentation: dict, K, R, t, smpl=None, vert_segmentati
         remove = torch.from_numpy(np.isin(labels, [names.index(p) for p in wanted]))
     if not faces.is_cuda and faces.numel() and (int(faces.min()) < 0 or int(faces.max()) >= verts.shape[0]):   # host data: no device involved
         raise IconAmdError(f"{what}: face index out of range")
-    if not torch.cuda.is_available():
-        raise IconAmdError(f"{what} needs the HIP device (there is no CPU fallback)")
+    need_device(what)
     dev = verts.device if verts.is_cuda else torch.device("cuda", torch.cuda.current_device())
     f = faces.detach()
     f = f.to(dev) if f.dtype in (torch.int32, torch.int64) else f.to(dev, torch.int64)

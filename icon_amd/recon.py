@@ -26,6 +26,7 @@ import torch.nn as nn
 
 from . import _lib
 from ._lib import IconAmdError, check
+from ._native import faces_arg, need_device, scratch_for, stream
 
 
 def slab_partition(res: int, world_size: int, weights=None):
@@ -250,7 +251,6 @@ class DenseReconEngine(nn.Module):
     def _hip_slab_mesh(buf, z0, res, zc0, zc1, halo, level):
         """marching cubes over the cell layers [zc0, zc1) of the volume whose planes z0, z0 + 1, ... are `buf` (device), the
         x / y edge crossings of layer zc1 included when `halo`; -> (keys [nv] i64, verts [nv,3] f32, faces [nf,3] i64 local)"""
-        from .engine import _stream
         if not buf.is_cuda:
             raise IconAmdError("forward_mesh: the slab triangulation runs on the HIP device (there is no CPU path)")
         dev = buf.device
@@ -260,13 +260,13 @@ class DenseReconEngine(nn.Module):
         cv, cf = C.c_int64(0), C.c_int64(0)
         with torch.cuda.device(dev):
             check(L.icon_mc_count_range(virt, C.c_int(res), C.c_float(level), C.c_int(zc0), C.c_int(zc1), C.c_int(1 if halo else 0),
-                                        work.h, _stream(), C.byref(cv), C.byref(cf)), "icon_mc_count_range")
+                                        work.h, stream(), C.byref(cv), C.byref(cf)), "icon_mc_count_range")
             nv, nf = cv.value, cf.value
             verts = torch.empty((max(nv, 1), 3), dtype=torch.float32, device=dev)
             faces = torch.empty((max(nf, 1), 3), dtype=torch.int64, device=dev)
             keys = torch.empty((max(nv, 1),), dtype=torch.int64, device=dev)
             if nv:
-                check(L.icon_mc_emit_keyed(_lib.ptr(verts), _lib.ptr(faces), _lib.ptr(keys), work.h, _stream()), "icon_mc_emit_keyed")
+                check(L.icon_mc_emit_keyed(_lib.ptr(verts), _lib.ptr(faces), _lib.ptr(keys), work.h, stream()), "icon_mc_emit_keyed")
         return keys[:nv], verts[:nv], faces[:nf]
 
     def _gather_mesh(self, slab, parts, res, dist, world, rank, dev):
@@ -651,11 +651,10 @@ class DenseReconEngine(nn.Module):
         st = [max((rs[-1][k] - 1) // max(rs[0][k] - 1, 1), 1) for k in range(3)]   # x, y, z
         if occ.is_cuda and occ.is_contiguous() and occ.dtype == torch.float32 and occ.shape[0] == occ.shape[1] == occ.shape[2]:
             # one native kernel + the stream wait the reference's own test implies (icon_volume_any_above)
-            from .engine import _stream
             hit = C.c_int(0)
             with torch.cuda.device(occ.device):
                 check(_lib.lib().icon_volume_any_above(_lib.ptr(occ), C.c_int(occ.shape[0]), C.c_int(st[0]), C.c_int(st[1]), C.c_int(st[2]),
-                                                       C.c_float(0.5), _mc_workspace(occ.device).h, _stream(), C.byref(hit)), "icon_volume_any_above")
+                                                       C.c_float(0.5), _mc_workspace(occ.device).h, stream(), C.byref(hit)), "icon_volume_any_above")
             return occ if hit.value else None
         if (occ[::st[2], ::st[1], ::st[0]] > 0.5).sum() == 0:
             return None
@@ -724,12 +723,11 @@ class DenseReconEngine(nn.Module):
 def mesh_components(faces: torch.Tensor, n_verts: int) -> torch.Tensor:
     """[V] int32 component label of every vertex (the smallest vertex index of its component), computed on
     the device by icon_mesh_components (union-find over the faces)."""
-    from .engine import _stream
     if not faces.is_cuda:
         raise IconAmdError("mesh_components needs device tensors (there is no CPU path)")
     f = faces.detach().to(torch.int64).reshape(-1, 3).contiguous()
     labels = torch.empty(int(n_verts), dtype=torch.int32, device=f.device)
-    check(_lib.lib().icon_mesh_components(_lib.ptr(f), C.c_int64(f.shape[0]), C.c_int64(int(n_verts)), _lib.ptr(labels), _stream()),
+    check(_lib.lib().icon_mesh_components(_lib.ptr(f), C.c_int64(f.shape[0]), C.c_int64(int(n_verts)), _lib.ptr(labels), stream()),
           "icon_mesh_components")
     return labels
 
@@ -766,9 +764,7 @@ def clean_mesh(verts: torch.Tensor, faces: torch.Tensor):
     tensors, seg3d_lossless.py:601-602) are moved to the current HIP device for the labelling.
     ONE native call since round 4 (icon_clean_mesh, csrc/clean_mesh.hip: edge hash table, union-find over the faces, vertex
     counts, order-preserving compaction; 2.0 ms of torch sort / unique / bincount operators before)."""
-    from .engine import _stream
-    if not torch.cuda.is_available():
-        raise IconAmdError("clean_mesh needs the HIP device (there is no CPU fallback)")
+    need_device("clean_mesh")
     out_dev = verts.device
     dev = verts.device if verts.is_cuda else torch.device("cuda", torch.cuda.current_device())
     v = verts.detach().to(dev, torch.float32).reshape(-1, 3).contiguous()
@@ -780,7 +776,7 @@ def clean_mesh(verts: torch.Tensor, faces: torch.Tensor):
         of = torch.empty((f.shape[0], 3), dtype=torch.int32, device=dev)
         hc = (C.c_int64 * 2)()
         check(_lib.lib().icon_clean_mesh(_lib.ptr(v), C.c_int64(v.shape[0]), _lib.ptr(f), C.c_int64(f.shape[0]), _lib.ptr(ov), _lib.ptr(of),
-                                         hc, _mc_workspace(dev).h, _stream()), "clean_mesh")
+                                         hc, _mc_workspace(dev).h, stream()), "clean_mesh")
     return ov[: hc[0]].to(out_dev), of[: hc[1]].to(out_dev)
 
 
@@ -797,24 +793,6 @@ def _mc_workspace(device: torch.device):
     if idx not in pool:
         pool[idx] = Workspace()
     return pool[idx]
-
-
-_qc_tls = threading.local()
-
-
-def _qc_scratch(device: torch.device, nbytes: int) -> torch.Tensor:
-    """query_color scratch: one tensor per (thread, device, stream), grown on demand and reused.  Per stream, because two calls
-    on different streams may run at once and must not share a z-buffer; and because torch's allocator orders the reuse of a
-    freed block only against the stream it was allocated on - which, keyed like this, is the stream that used it."""
-    pool = getattr(_qc_tls, "pool", None)
-    if pool is None:
-        pool = _qc_tls.pool = {}
-    idx = device.index if device.index is not None else torch.cuda.current_device()
-    key = (idx, torch.cuda.current_stream(idx).cuda_stream)
-    buf = pool.get(key)
-    if buf is None or buf.numel() < nbytes:
-        buf = pool[key] = torch.empty(nbytes, dtype=torch.uint8, device=torch.device("cuda", idx))
-    return buf
 
 
 def _qc_shapes(verts, faces, image):
@@ -834,30 +812,22 @@ def _query_color_launch(verts, faces, image, image_size, return_vis, return_bad)
     """validates, enqueues icon_query_color on the current stream -> (colors, vis or None, bad or None); bad: a device int32 [1],
     the number of faces the call skipped because they name a vertex that does not exist (copied out of the scratch header on
     the same stream)"""
-    from .engine import _stream
     _qc_shapes(verts, faces, image)
-    if not torch.cuda.is_available():
-        raise IconAmdError("query_color needs the HIP device (there is no CPU fallback)")
+    need_device("query_color")
     if not (verts.is_cuda and faces.is_cuda and image.is_cuda) or not (verts.device == faces.device == image.device):
         raise IconAmdError("query_color_device: verts, faces and image must live on one HIP device (query_color moves host tensors)")
     dev = verts.device
     v = verts.detach().to(torch.float32).contiguous()
-    f = faces.detach()
-    if f.dtype not in (torch.int32, torch.int64):
-        f = f.to(torch.int64)
-    f = f.contiguous()
+    f, f_i64 = faces_arg(faces)
     img = image.detach().to(torch.float32).contiguous()
     L = _lib.lib()
     with torch.cuda.device(dev):
-        nbytes = C.c_int64(0)
-        check(L.icon_query_color_bytes(C.c_int64(v.shape[0]), C.c_int64(f.shape[0]), C.c_int(int(image_size)), C.byref(nbytes)),
-              "icon_query_color_bytes")
-        scratch = _qc_scratch(dev, nbytes.value)
+        scratch = scratch_for(dev, "icon_query_color_bytes", C.c_int64(v.shape[0]), C.c_int64(f.shape[0]), C.c_int(int(image_size)))
         colors = torch.empty((v.shape[0], 3), dtype=torch.float32, device=dev)
         vis = torch.empty(v.shape[0], dtype=torch.float32, device=dev) if return_vis else None
-        check(L.icon_query_color(_lib.ptr(v), C.c_int64(v.shape[0]), _lib.ptr(f), C.c_int64(f.shape[0]), C.c_int(1 if f.dtype == torch.int64 else 0),
+        check(L.icon_query_color(_lib.ptr(v), C.c_int64(v.shape[0]), _lib.ptr(f), C.c_int64(f.shape[0]), f_i64,
                                  _lib.ptr(img), C.c_int(img.shape[2]), C.c_int(img.shape[3]), C.c_int(int(image_size)), _lib.ptr(colors),
-                                 _lib.ptr(vis), _lib.ptr(scratch), C.c_int64(scratch.numel()), _stream()), "icon_query_color")
+                                 _lib.ptr(vis), _lib.ptr(scratch), C.c_int64(scratch.numel()), stream()), "icon_query_color")
         bad = scratch[:4].view(torch.int32).clone() if return_bad else None     # first word of the header (include/icon_amd.h)
     return colors, vis, bad
 
@@ -883,8 +853,7 @@ def query_color(verts: torch.Tensor, faces: torch.Tensor, image: torch.Tensor, d
     _qc_shapes(verts, faces, image)
     if not faces.is_cuda and (int(faces.min()) < 0 or int(faces.max()) >= verts.shape[0]):      # host data: no device involved
         raise IconAmdError("query_color: face index out of range")
-    if not torch.cuda.is_available():
-        raise IconAmdError("query_color needs the HIP device (there is no CPU fallback)")
+    need_device("query_color")
     dev = torch.device(device) if device is not None else (verts.device if verts.is_cuda else torch.device("cuda", torch.cuda.current_device()))
     if dev.type != "cuda":
         raise IconAmdError(f"query_color: device must be a HIP device, got {dev} (there is no CPU fallback)")
@@ -920,18 +889,17 @@ def merge_keyed_meshes(keys, verts, faces):
 
 def export_mesh_device(occ: torch.Tensor, level: float = 0.5):
     """Marching cubes on the GPU (icon_mc_count / icon_mc_emit): device tensors in, device tensors out."""
-    from .engine import _stream
     occ = occ.detach().to(torch.float32).contiguous()
     assert occ.dim() == 3 and occ.shape[0] == occ.shape[1] == occ.shape[2]
     _mc_work = _mc_workspace(occ.device)
     L = _lib.lib()
     nv, nf = C.c_int64(0), C.c_int64(0)
-    check(L.icon_mc_count(_lib.ptr(occ), C.c_int(occ.shape[0]), C.c_float(level), _mc_work.h, _stream(), C.byref(nv), C.byref(nf)),
+    check(L.icon_mc_count(_lib.ptr(occ), C.c_int(occ.shape[0]), C.c_float(level), _mc_work.h, stream(), C.byref(nv), C.byref(nf)),
           "icon_mc_count")
     verts = torch.empty((max(nv.value, 1), 3), dtype=torch.float32, device=occ.device)
     faces = torch.empty((max(nf.value, 1), 3), dtype=torch.int64, device=occ.device)
     if nv.value and nf.value:
-        check(L.icon_mc_emit(_lib.ptr(verts), _lib.ptr(faces), _mc_work.h, _stream()), "icon_mc_emit")
+        check(L.icon_mc_emit(_lib.ptr(verts), _lib.ptr(faces), _mc_work.h, stream()), "icon_mc_emit")
     return verts[: nv.value], faces[: nf.value]
 
 

@@ -18,7 +18,6 @@ mesh and the input images side by side.  Not differentiable.  Point clouds are n
 from __future__ import annotations
 
 import ctypes as C
-import threading
 from typing import Sequence
 
 import numpy as np
@@ -26,27 +25,7 @@ import torch
 
 from . import _lib
 from ._lib import IconAmdError, check
-
-_rn_tls = threading.local()
-
-
-def _rn_scratch(device: torch.device, nbytes: int) -> torch.Tensor:
-    """renderer scratch: one tensor per (thread, device, stream), grown on demand and reused - calls on different streams may
-    run at once and must not share a z-buffer (recon._qc_scratch has the allocator side of the argument)"""
-    pool = getattr(_rn_tls, "pool", None)
-    if pool is None:
-        pool = _rn_tls.pool = {}
-    idx = device.index if device.index is not None else torch.cuda.current_device()
-    key = (idx, torch.cuda.current_stream(idx).cuda_stream)
-    buf = pool.get(key)
-    if buf is None or buf.numel() < nbytes:
-        buf = pool[key] = torch.empty(nbytes, dtype=torch.uint8, device=torch.device("cuda", idx))
-    return buf
-
-
-def _need_device(what: str) -> None:
-    if not torch.cuda.is_available():
-        raise IconAmdError(f"{what} needs the HIP device (there is no CPU fallback)")
+from ._native import constants, faces_arg, need_device as _need_device, scratch_for, stream
 
 
 def _check_cams(cam_ids) -> list:
@@ -76,10 +55,7 @@ def _check_mesh(what: str, verts, faces, need_float: bool) -> torch.Tensor:
     _need_device(what)
     if not (verts.is_cuda and faces.is_cuda) or verts.device != faces.device:
         raise IconAmdError(f"{what}: verts and faces must live on one HIP device (Render.load_meshes moves host data)")
-    f = faces.detach()
-    if f.dtype not in (torch.int32, torch.int64):
-        f = f.to(torch.int64)
-    return f.contiguous()
+    return faces_arg(faces)[0]
 
 
 def turntable_cos_sin(angles) -> np.ndarray:
@@ -106,18 +82,15 @@ def _mesh_args(v, f, cams, size):
 
 def _rn_forward(v, f, cams, size, return_depth, return_faces):
     """the native forward call on a float32, contiguous ``v`` and an int32 / int64, contiguous ``f``"""
-    from .engine import _stream
     dev, n = v.device, len(cams)
     L = _lib.lib()
     with torch.cuda.device(dev):
-        nbytes = C.c_int64(0)
-        check(L.icon_render_bytes(C.c_int64(v.shape[0]), C.c_int64(f.shape[0]), C.c_int(size), C.c_int(n), C.byref(nbytes)), "icon_render_bytes")
-        scratch = _rn_scratch(dev, nbytes.value)
+        scratch = scratch_for(dev, "icon_render_bytes", C.c_int64(v.shape[0]), C.c_int64(f.shape[0]), C.c_int(size), C.c_int(n))
         images = torch.empty((n, 3, size, size), dtype=torch.float32, device=dev)
         depth = torch.empty((n, size, size), dtype=torch.float32, device=dev) if return_depth else None
         pix = torch.empty((n, size, size), dtype=torch.int32, device=dev) if return_faces else None
         check(L.icon_render_normal(*_mesh_args(v, f, cams, size), _lib.ptr(images), _lib.ptr(depth), _lib.ptr(pix),
-                                   _lib.ptr(scratch), C.c_int64(scratch.numel()), _stream()), "icon_render_normal")
+                                   _lib.ptr(scratch), C.c_int64(scratch.numel()), stream()), "icon_render_normal")
     return images, depth, pix
 
 
@@ -136,19 +109,16 @@ class _RenderNormal(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_images, _grad_depth, _grad_pix):
-        from .engine import _stream
         v, f, pix = ctx.saved_tensors
         cams, size = ctx.cams, ctx.size
         g = grad_images.to(torch.float32).contiguous()
         L = _lib.lib()
         with torch.cuda.device(v.device):
-            nbytes = C.c_int64(0)
-            check(L.icon_render_normal_backward_bytes(C.c_int64(v.shape[0]), C.c_int64(f.shape[0]), C.c_int(size), C.c_int(len(cams)), C.byref(nbytes)),
-                  "icon_render_normal_backward_bytes")
-            scratch = _rn_scratch(v.device, nbytes.value)                     # this thread's and this stream's: autograd has its own
+            scratch = scratch_for(v.device, "icon_render_normal_backward_bytes", C.c_int64(v.shape[0]), C.c_int64(f.shape[0]), C.c_int(size),
+                                  C.c_int(len(cams)))                          # this thread's and this stream's: autograd has its own
             grad_verts = torch.empty_like(v)
             check(L.icon_render_normal_backward(*_mesh_args(v, f, cams, size), _lib.ptr(pix), _lib.ptr(g), _lib.ptr(grad_verts),
-                                                _lib.ptr(scratch), C.c_int64(scratch.numel()), _stream()), "icon_render_normal_backward")
+                                                _lib.ptr(scratch), C.c_int64(scratch.numel()), stream()), "icon_render_normal_backward")
         return grad_verts, None, None, None
 
 
@@ -179,19 +149,6 @@ def render_normal_device(verts: torch.Tensor, faces: torch.Tensor, cam_ids: Sequ
     return out if len(out) > 1 else images
 
 
-def _tt_pairs(device: torch.device, pairs: np.ndarray) -> torch.Tensor:
-    """the pairs on the device, kept per (thread, device, stream) like the scratch: the video asks for the same chunks of angles
-    for every mesh, and a call repeated after a warm-up uploads nothing - so it can be captured into a graph"""
-    cache = getattr(_rn_tls, "pairs", None)
-    if cache is None or len(cache) > 64:
-        cache = _rn_tls.pairs = {}
-    idx = device.index if device.index is not None else torch.cuda.current_device()
-    key = (idx, torch.cuda.current_stream(idx).cuda_stream, pairs.tobytes())
-    if key not in cache:
-        cache[key] = torch.from_numpy(pairs).to(torch.device("cuda", idx))
-    return cache[key]
-
-
 def render_turntable_device(verts: torch.Tensor, faces: torch.Tensor, angles, size: int = 512, out: torch.Tensor = None, x0: int = 0,
                             return_images: bool = False, return_depth: bool = False, return_faces: bool = False):
     """``verts [V,3]`` (float), ``faces [F,3]`` (int32 or int64, read in place), both on one HIP device; ``angles``: 1..1024
@@ -205,7 +162,6 @@ def render_turntable_device(verts: torch.Tensor, faces: torch.Tensor, angles, si
     chunks inside the call (the scratch, cached per (thread, device, stream) like ``render_normal_device``'s, does not grow
     with n).  Nothing is allocated by it, nothing read back, the stream is not waited for; equal bytes from run to run.  Not
     differentiable: it renders from a detached copy."""
-    from .engine import _stream
     size = _check_size(size)
     pairs = turntable_cos_sin(angles)
     n = len(pairs)
@@ -227,28 +183,22 @@ def render_turntable_device(verts: torch.Tensor, faces: torch.Tensor, angles, si
         raise IconAmdError("render_turntable_device: out must live on the device of the mesh")
     L = _lib.lib()
     with torch.cuda.device(dev):
-        nbytes = C.c_int64(0)
-        check(L.icon_render_turntable_bytes(C.c_int64(v.shape[0]), C.c_int64(f.shape[0]), C.c_int(size), C.c_int(n), C.byref(nbytes)),
-              "icon_render_turntable_bytes")
-        scratch = _rn_scratch(dev, nbytes.value)
-        cos_sin = _tt_pairs(dev, pairs)
+        scratch = scratch_for(dev, "icon_render_turntable_bytes", C.c_int64(v.shape[0]), C.c_int64(f.shape[0]), C.c_int(size), C.c_int(n))
+        cos_sin, = constants(dev, pairs)                                     # the video asks for the same chunks of angles for every mesh
         frames = out if out is not None else torch.empty((n, size, size, 3), dtype=torch.uint8, device=dev)
         images = torch.empty((n, 3, size, size), dtype=torch.float32, device=dev) if return_images else None
         depth = torch.empty((n, size, size), dtype=torch.float32, device=dev) if return_depth else None
         pix = torch.empty((n, size, size), dtype=torch.int32, device=dev) if return_faces else None
         check(L.icon_render_turntable(_lib.ptr(v), C.c_int64(v.shape[0]), _lib.ptr(f), C.c_int64(f.shape[0]), C.c_int(1 if f.dtype == torch.int64 else 0),
                                       _lib.ptr(cos_sin), C.c_int(n), C.c_int(size), _lib.ptr(frames), C.c_int64(frames.shape[2]), C.c_int64(int(x0)),
-                                      _lib.ptr(images), _lib.ptr(depth), _lib.ptr(pix), _lib.ptr(scratch), C.c_int64(scratch.numel()), _stream()),
+                                      _lib.ptr(images), _lib.ptr(depth), _lib.ptr(pix), _lib.ptr(scratch), C.c_int64(scratch.numel()), stream()),
               "icon_render_turntable")
     res = (frames,) + tuple(t for t in (images, depth, pix) if t is not None)
     return res if len(res) > 1 else frames
 
 
 def _sil_scratch(v, f, cams, size):
-    nbytes = C.c_int64(0)
-    check(_lib.lib().icon_silhouette_bytes(C.c_int64(v.shape[0]), C.c_int64(f.shape[0]), C.c_int(size), C.c_int(len(cams)), C.byref(nbytes)),
-          "icon_silhouette_bytes")
-    return _rn_scratch(v.device, nbytes.value)
+    return scratch_for(v.device, "icon_silhouette_bytes", C.c_int64(v.shape[0]), C.c_int64(f.shape[0]), C.c_int(size), C.c_int(len(cams)))
 
 
 class _Silhouette(torch.autograd.Function):
@@ -256,19 +206,17 @@ class _Silhouette(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, v, f, cams, size):
-        from .engine import _stream
         with torch.cuda.device(v.device):
             scratch = _sil_scratch(v, f, cams, size)
             alpha = torch.empty((len(cams), size, size), dtype=torch.float32, device=v.device)
             check(_lib.lib().icon_silhouette_forward(*_mesh_args(v, f, cams, size), _lib.ptr(alpha), _lib.ptr(scratch),
-                                                     C.c_int64(scratch.numel()), _stream()), "icon_silhouette_forward")
+                                                     C.c_int64(scratch.numel()), stream()), "icon_silhouette_forward")
         ctx.save_for_backward(v, f, alpha)
         ctx.cams, ctx.size = cams, size
         return alpha
 
     @staticmethod
     def backward(ctx, grad_alpha):
-        from .engine import _stream
         v, f, alpha = ctx.saved_tensors
         cams, size = ctx.cams, ctx.size
         g = grad_alpha.to(torch.float32).contiguous()
@@ -276,7 +224,7 @@ class _Silhouette(torch.autograd.Function):
             scratch = _sil_scratch(v, f, cams, size)                          # this thread's and this stream's: autograd has its own
             grad_verts = torch.empty_like(v)
             check(_lib.lib().icon_silhouette_backward(*_mesh_args(v, f, cams, size), _lib.ptr(alpha), _lib.ptr(g), _lib.ptr(grad_verts),
-                                                      _lib.ptr(scratch), C.c_int64(scratch.numel()), _stream()), "icon_silhouette_backward")
+                                                      _lib.ptr(scratch), C.c_int64(scratch.numel()), stream()), "icon_silhouette_backward")
         return grad_verts, None, None, None
 
 

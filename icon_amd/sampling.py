@@ -21,7 +21,8 @@ import torch
 
 from . import _lib
 from ._lib import IconAmdError, check
-from .garment import _check_device, _check_points, _scratch
+from ._native import scratch_for, stream
+from .garment import _check_device, _check_points
 
 
 class ScanMesh:
@@ -88,7 +89,6 @@ def sample_geo_device(scan: ScanMesh, calib, num_sample_geo: int, sigma_geo: flo
     equal bytes.  ``return_all``: a fourth value, dict(all_samples [n,3] f32, all_inside [n] bool, source [n] int32 - the
     source index ``perm(i)`` of slot i -, vertex [n] int32 - the vertex drawn for it, -1 for a space sample): the shuffled list
     before balancing.  Nothing is waited for; the scratch is cached per (thread, device, stream)."""
-    from .engine import _stream
     what = "sample_geo_device"
     if not isinstance(scan, ScanMesh):
         raise IconAmdError(f"{what}: scan must be a ScanMesh, got {type(scan).__name__}")
@@ -108,9 +108,7 @@ def sample_geo_device(scan: ScanMesh, calib, num_sample_geo: int, sigma_geo: flo
     dev = scan.device
     L = _lib.lib()
     with torch.cuda.device(dev):
-        nbytes = C.c_int64(0)
-        check(L.icon_sample_geo_bytes(C.c_int64(n), C.byref(nbytes)), "icon_sample_geo_bytes")
-        scratch = _scratch(dev, nbytes.value)
+        scratch = scratch_for(dev, "icon_sample_geo_bytes", C.c_int64(n))
         samples = torch.empty((N, 3), dtype=torch.float32, device=dev)
         labels = torch.empty(N, dtype=torch.float32, device=dev)
         counts = torch.empty(2, dtype=torch.int32, device=dev)
@@ -124,7 +122,7 @@ def sample_geo_device(scan: ScanMesh, calib, num_sample_geo: int, sigma_geo: flo
                                 cal.ctypes.data_as(C.POINTER(C.c_double)), cal_inv.ctypes.data_as(C.POINTER(C.c_double)),
                                 C.c_int64(N), C.c_double(sigma), C.c_int(int(zray)), C.c_int(R), C.c_uint64(int(seed) % 2 ** 64),
                                 _lib.ptr(samples), _lib.ptr(labels), _lib.ptr(counts), *opt,
-                                _lib.ptr(scratch), C.c_int64(scratch.numel()), _stream()), "icon_sample_geo")
+                                _lib.ptr(scratch), C.c_int64(scratch.numel()), stream()), "icon_sample_geo")
     if extra:
         extra["all_inside"] = extra["all_inside"].bool()
         return samples, labels, counts, extra

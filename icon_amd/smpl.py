@@ -21,6 +21,7 @@ import torch
 
 from . import _lib
 from ._lib import IconAmdError, check
+from ._native import need_device, scratch_for, stream
 
 MAX_JOINTS, MAX_BETAS = 64, 512                                            # include/icon_amd.h: the limits of icon_smpl_*
 BUFFERS = ("v_template", "shapedirs", "posedirs", "J_regressor", "parents", "lbs_weights")
@@ -137,7 +138,6 @@ class _SmplLbsFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, betas, rot, model):
-        from .engine import _stream
         ctx.set_materialize_grads(False)                                   # an output nobody uses: a null pointer, not a tensor of zeros
         B = rot.shape[0]
         with torch.cuda.device(rot.device):
@@ -145,15 +145,13 @@ class _SmplLbsFn(torch.autograd.Function):
             joints = torch.empty((B, model.J, 3), dtype=torch.float32, device=rot.device)
             A = torch.empty((B, model.J, 3, 4), dtype=torch.float32, device=rot.device)   # this call's own: a second forward must not overwrite it
             check(_lib.lib().icon_smpl_forward(C.byref(model._tables()), _lib.ptr(betas), _lib.ptr(rot), C.c_int64(B), _lib.ptr(verts),
-                                               _lib.ptr(joints), _lib.ptr(A), _stream()), "icon_smpl_forward")
+                                               _lib.ptr(joints), _lib.ptr(A), stream()), "icon_smpl_forward")
         ctx.save_for_backward(betas, rot, A)
         ctx.model = model
         return verts, joints
 
     @staticmethod
     def backward(ctx, g_verts, g_joints):
-        from .engine import _stream
-        from .render import _rn_scratch                                   # one pool per (thread, device, stream), shared with the renderer
         betas, rot, A = ctx.saved_tensors
         model = ctx.model
         if g_verts is None and g_joints is None:
@@ -162,14 +160,12 @@ class _SmplLbsFn(torch.autograd.Function):
         g_verts, g_joints = (None if g is None else g.to(torch.float32).contiguous() for g in (g_verts, g_joints))
         L = _lib.lib()
         with torch.cuda.device(rot.device):
-            nbytes = C.c_int64(0)
-            check(L.icon_smpl_bytes(C.c_int64(B), C.c_int64(model.V), C.c_int(model.J), C.c_int(model.NB), C.c_int(model.K), C.byref(nbytes)),
-                  "icon_smpl_bytes")
-            scratch = _rn_scratch(rot.device, nbytes.value)
+            scratch = scratch_for(rot.device, "icon_smpl_bytes", C.c_int64(B), C.c_int64(model.V), C.c_int(model.J), C.c_int(model.NB),
+                                  C.c_int(model.K))                            # this thread's and this stream's: autograd has its own
             g_betas, g_rot = torch.empty_like(betas), torch.empty_like(rot)
             check(L.icon_smpl_backward(C.byref(model._tables()), _lib.ptr(betas), _lib.ptr(rot), C.c_int64(B), _lib.ptr(A), _lib.ptr(g_verts),
                                        _lib.ptr(g_joints), _lib.ptr(g_betas), _lib.ptr(g_rot), _lib.ptr(scratch), C.c_int64(scratch.numel()),
-                                       _stream()), "icon_smpl_backward")
+                                       stream()), "icon_smpl_backward")
         return g_betas, g_rot, None
 
 
@@ -190,8 +186,7 @@ def smpl_lbs_device(betas: torch.Tensor, rot_mats: torch.Tensor, model: SmplMode
     B = rot_mats.shape[0]
     if tuple(betas.shape) != (B, model.NB):
         raise IconAmdError(f"{what}: betas must be [{B},{model.NB}] (NB = {model.NB} shape coefficients), got {tuple(betas.shape)}")
-    if not torch.cuda.is_available():
-        raise IconAmdError(f"{what} needs the HIP device (there is no CPU fallback)")
+    need_device(what)
     if not (betas.is_cuda and rot_mats.is_cuda and betas.device == rot_mats.device) or model.device != rot_mats.device:
         raise IconAmdError(f"{what}: betas, rot_mats and the model must live on one HIP device (SmplModel.to(device) moves it)")
     return _SmplLbsFn.apply(betas.contiguous(), rot_mats.contiguous(), model)

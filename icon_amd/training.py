@@ -21,13 +21,13 @@ import torch
 
 from . import _lib
 from ._lib import IconAmdError, check
+from ._native import scratch_for, stream
 
 _WHAT = "point_features_device"
 
 
 def _native_forward(eng, stacks, pts, calib12):
     """(rows [S,B,Cin,N], in_cube [B,1,N], taps [B*N,4] int32) of contiguous float32 device tensors: one native call"""
-    from .engine import _stream
     S = len(stacks)
     B, Cc, H, W = (int(x) for x in stacks[0].shape)
     N = int(pts.shape[1])
@@ -46,26 +46,21 @@ def _native_forward(eng, stacks, pts, calib12):
         mb.h if mb is not None else C.c_void_p(0), C.c_int(_lib.PRIOR[eng.prior_type]), C.c_float(np.float32(eng.sdf_clip)),
         C.c_int(_lib.CMAP[eng.cmap_mode]), C.c_int(int("vis" in feats)), C.c_int(int("cmap" in feats)), C.c_int(int("norm" in feats)),
         ptrs, shapes, C.c_int(S), _lib.ptr(calib12), _lib.ptr(pts), C.c_int64(N), _lib.ptr(rows), _lib.ptr(in_cube), _lib.ptr(taps),
-        C.c_int(_lib.SEARCH[eng.search]), eng._work().h, _stream()), "icon_train_rows_forward")
+        C.c_int(_lib.SEARCH[eng.search]), eng._work().h, stream()), "icon_train_rows_forward")
     return rows, in_cube, taps
 
 
 def _native_backward(grad_rows, taps, shape, n_select: int, mask: int, out=None):
     """grad_planes [S,B,C,H,W]: the stacks whose bit of ``mask`` is set are written, element by element (``out``: into this tensor)"""
-    from .engine import _stream
-    from .garment import _scratch                                     # one pool per (thread, device, stream): autograd has its own
     S, B, Cc, H, W = shape
     cin, N = int(grad_rows.shape[2]), int(grad_rows.shape[3])
     dev = grad_rows.device
     L = _lib.lib()
-    nbytes = C.c_int64(0)
-    check(L.icon_train_rows_bytes(C.c_int(B), C.c_int64(N), C.c_int(S), C.c_int(Cc), C.c_int(H), C.c_int(W), C.byref(nbytes)),
-          "icon_train_rows_bytes")
-    scratch = _scratch(dev, nbytes.value)
+    scratch = scratch_for(dev, "icon_train_rows_bytes", C.c_int(B), C.c_int64(N), C.c_int(S), C.c_int(Cc), C.c_int(H), C.c_int(W))   # autograd's thread has its own
     grad_planes = torch.empty((S, B, Cc, H, W), dtype=torch.float32, device=dev) if out is None else out
     check(L.icon_train_rows_backward(_lib.ptr(grad_rows), _lib.ptr(taps), C.c_int(S), C.c_uint32(mask), C.c_int(B), C.c_int(cin),
                                      C.c_int(Cc), C.c_int(H), C.c_int(W), C.c_int(n_select), C.c_int64(N), _lib.ptr(grad_planes),
-                                     _lib.ptr(scratch), C.c_int64(scratch.numel()), _stream()), "icon_train_rows_backward")
+                                     _lib.ptr(scratch), C.c_int64(scratch.numel()), stream()), "icon_train_rows_backward")
     return grad_planes
 
 

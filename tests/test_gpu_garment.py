@@ -320,7 +320,8 @@ def test_determinism_and_streams():
     again = gm.extract_cloth_device(v, f, polys, s, r, return_index=True)
     assert all(a.equal(b) for a, b in zip(first, again))
     _same(again, o)
-    pool = gm._tls.pool
+    from icon_amd import _native
+    pool = _native._tls.pool
     before = set(pool)
     streams = [torch.cuda.Stream(), torch.cuda.Stream()]
     outs = []

@@ -160,11 +160,11 @@ def test_gpu_turntable_replays_from_a_captured_graph():
 
 def test_gpu_turntable_bad_mesh_renders_as_ico():
     """the C entry's count of the faces it skipped, too: the first word of the scratch after the call"""
-    from icon_amd.render import _rn_scratch
+    from icon_amd._native import scratch
     v, f, S, _ = tc.case("bad")
     got = _render(v, f, tc.ANGLES, S)
     torch.cuda.synchronize()
-    assert int(_rn_scratch(torch.device("cuda", torch.cuda.current_device()), 4)[:4].view(torch.int32).item()) == 1
+    assert int(scratch(torch.device("cuda", torch.cuda.current_device()), 4)[:4].view(torch.int32).item()) == 1
     assert _same(got, tc.case("ico")[3])
     vi, fi = tc.CASES["ico"][0]()
     assert _same(got, _render(vi, fi, tc.ANGLES, S))

@@ -100,7 +100,7 @@ def main():
         return reference_cpu(args.reference_cpu)
     import numpy as np
     import torch
-    from icon_amd import _lib, garment as gm, synth
+    from icon_amd import _lib, _native, garment as gm, synth
     from icon_amd.engine import IconQueryEngine
     from icon_amd.recon import clean_mesh, export_mesh_device
 
@@ -168,7 +168,7 @@ def main():
         fn()
         torch.cuda.synchronize()
         peak = torch.cuda.max_memory_allocated() - base
-        pool = sum(b.numel() for b in gm._tls.pool.values()) if name == "native" else 0
+        pool = sum(b.numel() for b in _native._tls.pool.values()) if name == "native" else 0
         say(f"{name:9s} {len(kernels)} kernel launches, {len(ev) - len(kernels)} copies / memsets per call; peak extra memory {peak / 2 ** 20:.1f} MiB"
             + (f" (outputs at the input sizes included) + {pool / 2 ** 20:.2f} MiB pooled scratch" if name == "native" else " (chunked)"))
     if args.out:

@@ -30,7 +30,7 @@ def main():
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import torch
-    from icon_amd import _lib, render
+    from icon_amd import _lib, _native, render
     import normal_grad_oracle as ngo
     import silhouette_oracle as so
 
@@ -61,7 +61,7 @@ def main():
                     vv = torch.from_numpy(v).to(dev).requires_grad_(True)
                     images, depth, pix = render.render_normal_device(vv, ff, cams, S, return_depth=True, return_faces=True, differentiable=True)
                     torch.cuda.synchronize()
-                    deferred = int(render._rn_scratch(dev, 0)[:16].view(torch.int32)[1])      # the header: bad_faces, n_big, n_long, pad
+                    deferred = int(_native.scratch(dev, 0)[:16].view(torch.int32)[1])      # the header: bad_faces, n_big, n_long, pad
                     images.backward(g)
                     if lanes and deferred and name not in both[lanes]:
                         both[lanes].append(name)

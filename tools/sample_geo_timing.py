@@ -56,7 +56,7 @@ def main():
     args = ap.parse_args()
     import numpy as np
     import torch
-    from icon_amd import _lib, garment as gm, synth
+    from icon_amd import _lib, _native, synth
     from icon_amd.engine import IconQueryEngine
     from icon_amd.recon import clean_mesh, export_mesh_device
     from icon_amd.sampling import ScanMesh, sample_geo_device
@@ -125,7 +125,7 @@ def main():
             fn()
             torch.cuda.synchronize()
             peak = torch.cuda.max_memory_allocated() - base
-            pool = sum(b.numel() for b in gm._tls.pool.values()) if name == "native" else 0
+            pool = sum(b.numel() for b in _native._tls.pool.values()) if name == "native" else 0
             say(f"  {name:9s} {len(kernels)} kernel launches, {len(ev) - len(kernels)} copies / memsets per call; peak extra memory {peak / 2 ** 20:.2f} MiB"
                 + (f" + {pool / 2 ** 20:.2f} MiB pooled scratch" if name == "native" else ""))
     if args.out:
