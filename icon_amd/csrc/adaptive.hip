@@ -22,6 +22,7 @@
 #pragma clang fp contract(off)
 
 #include "geom_device.h"
+#include "sign_list_device.h"
 
 #include <algorithm>
 #include <vector>
@@ -589,11 +590,9 @@ static int adaptive_eval_impl(const icon_mesh_t *mesh, const icon_feat_t *feat, 
             ICON_HIP(hipGetLastError());
             debug_sync("adaptive: k_ad_nearest", st);
             if ((rc = launch_sign(mesh, cal, r, 0, a->pts, n, sdf_clip, work, false, st))) return rc;
-            if (needs_list && (rc = outlier_list_dev(work, a->counters + l, n, st))) return rc;
+            if (needs_list && (rc = outlier_list(work, n, a->counters + l, work->d_signs, true, st))) return rc;
         }
-        FusedSigns fs{};
-        fs.mode = needs_list ? kSignSelf : kSignNone;
-        fs.list = work->d_signs; fs.k_dev = work->d_total;
+        const SignSrc fs = self_signs(work, needs_list);
         LatticeMap L{};
         rc = launch_fused_f16x3(mesh, feat, mlp, prior_type, cal, L, 0, 0, a->pts, n, sdf_clip, cmap_mode == ICON_CMAP_LOCAL ? 1 : 0, work, fs,
                                 a->occ[l], false, st);

@@ -99,7 +99,7 @@ int batch_geometry(const icon_mesh_batch *mb, const BatchDev &bd, const float *d
     debug_sync("nearest (batch)", st);
     if ((rc = launch_sign(mesh0, Calib{}, 0, 0, d_points, NB, sdf_clip, work, false, st, &bd))) return rc;
     debug_sync("k_sign_wide<batch>", st);
-    if (needs_patch && (rc = outlier_list(work, NB, work->d_signs, true, st))) return rc;
+    if (needs_patch && (rc = outlier_list(work, NB, nullptr, work->d_signs, true, st))) return rc;
     return ICON_OK;
 }
 
@@ -220,9 +220,7 @@ extern "C" int icon_query_points_batch(const icon_mesh_batch_t *mb, const icon_f
     mark(work, 0, st);
     if (prior_type == ICON_PRIOR_ICON && (rc = batch_geometry(mb, bd, d_points, N, B, sdf_clip, needs_patch, work, st))) return rc;
     mark(work, 1, st);
-    FusedSigns fs{};
-    fs.mode = needs_patch ? kSignSelf : kSignNone;
-    fs.list = work->d_signs; fs.k_dev = work->d_total;
+    const SignSrc fs = self_signs(work, needs_patch);
     if (want_fused(precision, search)) {
         mark(work, 2, st);
         rc = launch_fused_f16x3(mesh0, feat, mlp, prior_type, Calib{}, LatticeMap{}, 0, 0, d_points, NB, sdf_clip, local, work, fs, d_occ,
@@ -239,7 +237,7 @@ extern "C" int icon_query_points_batch(const icon_mesh_batch_t *mb, const icon_f
     else ICON_LAUNCH(ICON_PRIOR_PIFU);
 #undef ICON_LAUNCH
     ICON_HIP(hipGetLastError());
-    if (needs_patch && (rc = patch_self(work, NB, f.csel + 1, st))) return rc;
+    if ((rc = outlier_patch(work, NB, f.csel + 1, fs, st))) return rc;
     mark(work, 2, st);
     rc = mlp_launch(mlp, work->d_x, NB, d_occ, precision, st);
     mark(work, 3, st);

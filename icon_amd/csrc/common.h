@@ -264,17 +264,7 @@ __device__ __forceinline__ float apply_last_op(float y, int last_op)
 // point i = map[i] (its [z][y][x] linear index); null: entry of point i = i.
 struct NearRef { uint16_t *lo; uint8_t *hi; float *d2; const int32_t *map; };
 
-// where the fused kernel / the patch kernels find the outlier signs of the whole call (HGPIFuNet.py:303-305)
-enum { kSignNone = 0, kSignSelf = 1, kSignGlobal = 2, kSignSeg = 3 };
-struct FusedSigns {
-    int mode;
-    const int8_t *list;           // SELF / GLOBAL: signs in point order
-    const int64_t *k_dev;         // SELF: device scalar K
-    int64_t k_host, rank_offset;  // GLOBAL
-    const int8_t *gathered;       // SEG: all_gather output, message r = [int64 count][2-bit packed signs]
-    int64_t stride;
-    int world, rank;
-};
+struct SignSrc;                   // sign_list_device.h: where the outlier signs of the whole call are (HGPIFuNet.py:303-305)
 
 // Batched point-mode calls (icon_query_points_batch): the B*N points of a call in subject-major order, point i of subject
 // i / n.  What differs per subject is looked up through this descriptor; the per-call structs (MeshDev, FeatDev, Calib,
@@ -367,9 +357,7 @@ inline int lattice_packet()
     static const int pk_env = getenv("ICON_AMD_PACKET") ? atoi(getenv("ICON_AMD_PACKET")) : 0;
     return pk_env == 2 ? 2 : 4;
 }
-// query_kernels.hip: the outlier sign list of a point-mode call whose size is known on the device only (*n_dev <= n_max)
-int outlier_list_dev(icon_work *w, const int *n_dev, int64_t n_max, hipStream_t st);
-int ensure_work_points(icon_work *w, int64_t n_points);
+int ensure_work_points(icon_work *w, int64_t n_points);                               // work.hip
 // mc_device.hip
 struct McDevState;
 void mc_destroy(McDevState *s);
@@ -399,7 +387,7 @@ int launch_sign(const icon_mesh *mesh, const Calib &cal, int res, int z0, const 
 // bd: a batched point-mode call (icon_query_points_batch) - mesh, planes and calibration per subject
 int launch_fused_f16x3(const icon_mesh *mesh, const icon_feat *feat, const icon_mlp *mlp, int prior, const Calib &cal,
                        const LatticeMap &L, int za, int zb, const float *d_points, int64_t N, float sdf_clip, int cmap_local,
-                       const icon_work *work, const FusedSigns &fs, float *d_occ, bool lattice, hipStream_t st,
+                       const icon_work *work, const SignSrc &fs, float *d_occ, bool lattice, hipStream_t st,
                        const BatchDev *bd = nullptr);
 // sort_points.hip: Morton order of a batched call's B*n points, subject first: subject b's points are the sorted positions
 // [b n, (b + 1) n) (the key carries the subject above the Morton bits)
@@ -407,12 +395,19 @@ int morton_order_batch(icon_work *w, const float *d_points, const float *d_calib
 // batch_query.hip: search + sign pass + (needs_patch) batch-global outlier list of a batched icon call; ensure_work(N * B) came first
 int batch_geometry(const icon_mesh_batch *mb, const BatchDev &bd, const float *d_points, int64_t N, int B, float sdf_clip,
                    bool needs_patch, icon_work *work, hipStream_t st);
-// query_kernels.hip: pieces of the point-mode pipeline the batched call (batch_query.hip) shares
+// work.hip: the workspace's scratch and profiling events
 int ensure_work(icon_work *w, int64_t n_points, bool need_x);                          // scratch for n_points (need_x: the 64-byte input rows too)
-int outlier_list(icon_work *w, int64_t N, int8_t *signs, bool counted, hipStream_t st);   // counted: k_sign left the block counts
-int patch_self(icon_work *w, int64_t N, int cmap_slot, hipStream_t st);
-bool want_fused(int precision, int search);
 void mark(icon_work *w, int k, hipStream_t st);                                       // profiling event k of the call
+bool want_fused(int precision, int search);                                           // query_kernels.hip
+// outlier_list.hip: the call's outlier sign list (reference cmap mode) - count + scan + compact over the code bytes of points
+// [0, N) into `signs`, w->d_block_offsets and w->d_total (counted: k_sign left the block counts; n_dev: the call's size lives
+// on the device, *n_dev <= N); the SignSrc of a call whose own list is the whole list; what a launch reading a SignSrc needs
+// first (SEG: the segment offsets); the cmap patch of the rows in w->d_x; the packed message of the multi-GPU exchange
+int outlier_list(icon_work *w, int64_t N, const int *n_dev, int8_t *signs, bool counted, hipStream_t st);
+SignSrc self_signs(const icon_work *work, bool needs);
+int resolve_signs(const icon_work *work, SignSrc *sg, hipStream_t st);
+int outlier_patch(icon_work *w, int64_t N, int cmap_slot, const SignSrc &sg, hipStream_t st);
+int pack_sign_message(const icon_work *w, const int8_t *signs, void *d_msg, int64_t cap, hipStream_t st);
 // per-device launch facts (CU count; one-off kernel attributes): a process may drive several devices
 int device_cu_count(int *n_cu);
 int once_per_device(int kernel_id, const std::function<hipError_t()> &set);   // runs `set` once per (kernel_id, current device), under a mutex
@@ -431,7 +426,7 @@ extern int g_qc_lanes;                // query_color.hip: lanes per face of the 
 extern int g_rn_lanes;                // render_normal.hip: lanes per face of the renderer's rasteriser ("rn_lanes"; 0 = default)
 extern int g_tt_chunk;                // turntable.hip: views per chunk of the turntable call ("tt_chunk"; 0 = default)
 extern int g_ev_lanes;                // evaluator.hip: lanes per face of the evaluator's rasteriser ("ev_lanes"; 0 = default)
-// the process-wide test / A-B switches (query_kernels.hip: the table with their keys, environment variables and defaults)
+// the process-wide test / A-B switches (work.hip: the table with their keys, environment variables and defaults)
 enum Opt { kOptPairBox, kOptNodeBox, kOptBoxClamp, kOptLatticeFast, kOptUnfused, kOptShellSkip, kOptShareWaves, kOptShareRing, kOptShareLose,
            kOptShareSpinLog2, kOptCount };
 int option(Opt o);

@@ -6,7 +6,7 @@
 //     k_nearest            -> (slot, d^2)                  8 B  w
 //     k_features           -> X row [16] f32 + code      8 r + 65 w
 //     count / scan / compact over the codes                2 r + <=1 w
-//     k_outlier_patch_self -> X rows rewritten         1 + 64 r + 64 w     (reference cmap mode)
+//     k_outlier_patch      -> X rows rewritten         1 + 64 r + 64 w     (reference cmap mode)
 //     k_mlp_f16x3          <- X rows                      64 r + 4 w      => ~280 B/pt, 4.8 GB per 257^3
 //   now
 //     k_nearest            -> slot 4 B + d^2 4 B (structure of arrays)        8 B  w
@@ -39,6 +39,7 @@
 #include "batch_device.h"
 #include "mlp_f16x3_device.h"
 #include "mlp_plain_device.h"
+#include "sign_list_device.h"
 
 #include <algorithm>
 #include <mutex>
@@ -49,17 +50,6 @@ constexpr int kTilePts = kF16Pts;                     // 256 points per tile
 // LDS map: [2 x 40 KiB weight buffers][W0 32 KiB][side arrays][point tile 16 KiB][wave sums]
 constexpr int kXsOff = kSideOff + 4352;               // point tile [256][16] f32 behind the side arrays
 constexpr int kFusedLds = kXsOff + kTilePts * kXRow * 4;
-
-struct SignSrc {
-    int mode;
-    const int8_t *list;          // SELF / GLOBAL: the outlier signs of the call in point order
-    const int64_t *k_dev;        // SELF: device scalar K
-    int64_t k_host, rank_offset; // GLOBAL: K and the number of outliers in lower slabs
-    const int8_t *gathered;      // SEG: all_gather output, message r = [int64 count][signs, 2 bits each: sign + 1]
-    int64_t stride;
-    int world, rank;
-    const int64_t *seg;          // SEG: [world + 1] exclusive prefix of the counts (k_seg_offsets)
-};
 
 struct FusedGeom {
     MeshDev m;
@@ -77,7 +67,7 @@ struct FusedGeom {
     const uint8_t *code8;        // icon prior: outlier / sign / inside / in_cube (k_nearest<.., SIGN> or k_sign)
     const int64_t *block_offsets;        // exclusive scan of the outlier counts per 256 points of the linear order
     const unsigned long long *grp_mask;  // outlier ballot of every 64-point group of the linear order (4 per block)
-    SignSrc sg;
+    SignSrc sg;                  // where the call's outlier signs are (sign_list_device.h)
     // profiling (icon_work_profile): workgroup 0 brackets its run with the shader-cycle counter and the constant-rate wall
     // counter - [0] s_memtime, [1] s_memrealtime at the start, [2], [3] at the end: cycles / wall time = the EFFECTIVE clock
     // the matrix pipe ran at under this launch's load (bench.py roofline.effective_clock_mhz: separates a slow box from a slow build).
@@ -287,26 +277,6 @@ __global__ __launch_bounds__(256) void k_shell_zero(float *__restrict__ out, int
 // ---------------------------------------------------------------------------------------------
 // the fused kernel
 // ---------------------------------------------------------------------------------------------
-// SEG mode: `off` = exclusive prefix of the per-rank counts (world + 1 entries, global memory written by
-// k_seg_offsets, read here through wave-uniform scalar loads): segment of mm = number of boundaries <= mm
-__device__ __forceinline__ float sign_at(const SignSrc &sg, int64_t mm)
-{
-    if (sg.mode == kSignSeg) {
-        int r = 0;
-        int64_t base = 0;
-        for (int q = 1; q < sg.world; ++q) {
-            const int64_t o = sg.seg[q];
-            const bool ge = mm >= o;
-            r += ge ? 1 : 0;
-            base = ge ? o : base;
-        }
-        const int64_t e = mm - base;                             // 2 bits per sign (sign + 1), four to a byte
-        const uint32_t byte = (uint8_t)sg.gathered[(int64_t)r * sg.stride + 8 + (e >> 2)];
-        return (float)((int)((byte >> (2 * (int)(e & 3))) & 3u) - 1);
-    }
-    return (float)sg.list[mm];
-}
-
 // lattice mode: work item q -> lattice indices and the point's index in the linear order of the slab
 __device__ __forceinline__ int64_t lattice_item(const FusedGeom &G, int64_t q, int &ix, int &iy, int &iz)
 {
@@ -338,7 +308,7 @@ __device__ __forceinline__ void icon_row(const FusedGeom &G, const MeshDev &m, c
     float s = o.sdf;
     f3 cmv = o.cm;
     if (code & kCodeOutlier) {                      // HGPIFuNet.py:298-305
-        s = (float)((int)((code >> kCodeSignShift) & 3u) - 1);
+        s = (float)code_sign(code);
         if (G.cmap_local) cmv = mk3(s, s, s);
         else if (K > 0 && (f.smpl_mask & kSmplCmap)) {
             // rank among the call's outliers: scan over 256-point blocks + ballots of the 64-point groups
@@ -351,13 +321,7 @@ __device__ __forceinline__ void icon_row(const FusedGeom &G, const MeshDev &m, c
             if (g > 2) before += __popcll(mk[2]);
             const int64_t jr = rank0 + G.block_offsets[blk] + before;
             float c3[3];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                int64_t mm = 3 * jr + k;            // jr < K  =>  mm < 3K
-                if (mm >= K) mm -= K;
-                if (mm >= K) mm -= K;
-                c3[k] = sign_at(G.sg, mm);
-            }
+            outlier_cmap(G.sg, K, jr, c3);
             cmv = mk3(c3[0], c3[1], c3[2]);
         }
     }
@@ -406,14 +370,14 @@ __device__ __forceinline__ void build_row(const FusedGeom &G, const BatchDev &bd
     }
 }
 
-// the sign-list geometry of the launch (reference cmap mode): K outliers in the call, rank0 = rank of this slab's first
-__device__ __forceinline__ void sign_list_extent(const FusedGeom &G, int64_t &K, int64_t &rank0)
+// the sign-list geometry of the launch: sign_list_extent in reference cmap mode, no list in local mode.  (A function of its
+// own with the early return: written as `if (!G.cmap_local) sign_list_extent(...)` at the two call sites the fused kernels
+// come out as another instruction stream - profiles/sign_list_kernels.txt.)
+__device__ __forceinline__ void launch_sign_extent(const FusedGeom &G, int64_t &K, int64_t &rank0)
 {
     K = 0; rank0 = 0;
     if (G.cmap_local) return;
-    if (G.sg.mode == kSignSelf) K = *G.sg.k_dev;
-    else if (G.sg.mode == kSignGlobal) { K = G.sg.k_host; rank0 = G.sg.rank_offset; }
-    else if (G.sg.mode == kSignSeg) { K = G.sg.seg[G.sg.world]; rank0 = G.sg.seg[G.sg.rank]; }
+    sign_list_extent(G.sg, K, rank0);
 }
 
 // SMALL (calls of at most 262,144 points: the levels of the reference's schedule, ordinary query() batches): a 256-point tile is
@@ -439,7 +403,7 @@ __global__ __launch_bounds__(kF16Block, 2) void k_fused_f16x3(FusedGeom G, float
     for (int i = threadIdx.x; i < kSideFloats; i += kF16Block) side[i] = w.side[i];
     const float *sb0 = side, *sb1 = side + 512, *sb2 = side + 768, *sw3 = side + kW3Float;
     int64_t K = 0, rank0 = 0;
-    if (PRIOR == ICON_PRIOR_ICON) sign_list_extent(G, K, rank0);
+    if (PRIOR == ICON_PRIOR_ICON) launch_sign_extent(G, K, rank0);
     // wave-uniform 64-bit values that live across the whole MLP body: keep them in SGPRs, not in the
     // 250-register vector budget of the MFMA chain
     K = uniform64(K); rank0 = uniform64(rank0);
@@ -602,7 +566,7 @@ __global__ __launch_bounds__(64) void k_rescue_fused(FusedGeom G, float *__restr
     if (SRC != Src::Batch && G.n_dev) G.N = *G.n_dev;
     const int lane = threadIdx.x;
     int64_t K = 0, rank0 = 0;
-    if (PRIOR == ICON_PRIOR_ICON) sign_list_extent(G, K, rank0);
+    if (PRIOR == ICON_PRIOR_ICON) launch_sign_extent(G, K, rank0);
     for (int64_t base = (int64_t)blockIdx.x * 64; base < G.N; base += (int64_t)gridDim.x * 64) {
         const int64_t q = base + lane;
         int ix, iy, iz;
@@ -625,15 +589,6 @@ __global__ __launch_bounds__(64) void k_rescue_fused(FusedGeom G, float *__restr
             __builtin_amdgcn_wave_barrier();
         }
     }
-}
-
-// exclusive prefix of the per-rank outlier counts found in the headers of the gathered messages
-__global__ void k_seg_offsets(const int8_t *__restrict__ gathered, int64_t stride, int world, int64_t *__restrict__ seg)
-{
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    int64_t a = 0;
-    for (int r = 0; r < world; ++r) { seg[r] = a; a += *reinterpret_cast<const int64_t *>(gathered + (int64_t)r * stride); }
-    seg[world] = a;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -706,7 +661,7 @@ int once_per_device(int kernel_id, const std::function<hipError_t()> &set)
 
 int launch_fused_f16x3(const icon_mesh *mesh, const icon_feat *feat, const icon_mlp *mlp, int prior, const Calib &cal,
                        const LatticeMap &L, int za, int zb, const float *d_points, int64_t N, float sdf_clip, int cmap_local,
-                       const icon_work *work, const FusedSigns &fs, float *d_occ, bool lattice, hipStream_t st, const BatchDev *bd)
+                       const icon_work *work, const SignSrc &fs, float *d_occ, bool lattice, hipStream_t st, const BatchDev *bd)
 {
     FusedGeom G{};
     if (mesh) G.m = mesh->dev;
@@ -731,13 +686,9 @@ int launch_fused_f16x3(const icon_mesh *mesh, const icon_feat *feat, const icon_
     G.clock = work->prof ? work->d_clock : nullptr;
     G.steal = nullptr; G.steal_static = 0; G.steal_grp = 1; G.steal_ngrp = 0;
     G.block_offsets = work->d_block_offsets; G.grp_mask = (const unsigned long long *)work->d_grp_mask;
-    G.sg.mode = fs.mode; G.sg.list = fs.list; G.sg.k_dev = fs.k_dev; G.sg.k_host = fs.k_host; G.sg.rank_offset = fs.rank_offset;
-    G.sg.gathered = fs.gathered; G.sg.stride = fs.stride; G.sg.world = fs.world; G.sg.rank = fs.rank; G.sg.seg = nullptr;
-    if (fs.mode == kSignSeg) {
-        if (!work->d_seg) return fail(ICON_ERR_STATE, "fused: segment offsets buffer missing");
-        hipLaunchKernelGGL(k_seg_offsets, dim3(1), dim3(64), 0, st, fs.gathered, fs.stride, fs.world, work->d_seg);
-        G.sg.seg = work->d_seg;
-    }
+    G.sg = fs;
+    int rc = resolve_signs(work, &G.sg, st);
+    if (rc) return rc;
     MlpF16Dev w;
     w.image = mlp->d_f16;
     w.side = reinterpret_cast<const float *>(mlp->d_f16 + kImageBytes);
@@ -749,8 +700,7 @@ int launch_fused_f16x3(const icon_mesh *mesh, const icon_feat *feat, const icon_
     if (defer) w.flag = work->defer_range_flag;
 
     int n_cu = 0;
-    int rc = device_cu_count(&n_cu);
-    if (rc) return rc;
+    if ((rc = device_cu_count(&n_cu))) return rc;
     if (defer) {}                                                // (the schedule zeroed its word once)
     else if (work->d_flag) { if (!work->flag_clean) ICON_HIP(hipMemsetAsync(work->d_flag, 0, sizeof(int), st)); }    // (k_sign of this call cleared it)
     else if ((rc = mlp_flag_reset(mlp, st))) return rc;

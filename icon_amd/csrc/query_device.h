@@ -5,6 +5,7 @@
 #pragma clang fp contract(off)
 
 #include "batch_device.h"
+#include "sign_list_device.h"
 
 namespace icon {
 
@@ -104,7 +105,7 @@ __global__ __launch_bounds__(kBlock) void k_features(MeshDev m, FeatDev f, Calib
         s = o.sdf;
         cmv = o.cm;
         if (code & kCodeOutlier) {            // HGPIFuNet.py:298-305
-            s = (float)((int)((code >> kCodeSignShift) & 3u) - 1);
+            s = (float)code_sign(code);
             if (cmap_local) cmv = mk3(s, s, s);   // reference mode: patched later from the sign list
         }
         float g[16];

@@ -13,7 +13,7 @@
 #pragma clang fp contract(off)
 
 #include "query_device.h"
-#include "scan_device.h"
+#include "sign_list_device.h"
 
 namespace icon {
 
@@ -211,31 +211,6 @@ __global__ __launch_bounds__(kBlock) void k_row_crossings(MeshDev m, LatticeMap 
     row_count[row] = (n <= kRowCap) ? n : -1;
 }
 
-// ---------------------------------------------------------------------------------------------
-// outlier sign list (reference cmap mode): count -> scan -> compact -> patch, all in the linear
-// point order of the call.
-// ---------------------------------------------------------------------------------------------
-
-__device__ __forceinline__ uint32_t row_code(const float *X, int64_t i)
-{
-    return (uint32_t)__float_as_int(X[i * kXRow + kCodeSlot]);
-}
-
-__global__ __launch_bounds__(kScanBlock) void k_outlier_count(const uint8_t *__restrict__ code8, int64_t N, int32_t *block_counts)
-{
-    __shared__ int wsum[kScanBlock / 64];
-    const int64_t i = (int64_t)blockIdx.x * kScanBlock + threadIdx.x;
-    const bool o = (i < N) && (code8[i] & kCodeOutlier);
-    const unsigned long long b = __ballot(o);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = __popcll(b);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int s = 0;
-        for (int w = 0; w < kScanBlock / 64; ++w) s += wsum[w];
-        block_counts[blockIdx.x] = s;
-    }
-}
-
 // The same with 16 lanes per row (slabs of few rows - the coarse lattices: 33^2 = 1,089 threads walking ~100-entry bin lists one
 // after the other were a 28 us launch of pure latency): the lanes of a group take every 16th entry of the bin list, the hits are
 // appended in list order through a ballot (the same row_slots as the one-thread version, entry for entry).
@@ -275,189 +250,11 @@ __global__ __launch_bounds__(kBlock) void k_row_crossings_wide(MeshDev m, Lattic
     if (have && s == 0) row_count[row] = (n <= kRowCap) ? n : -1;
 }
 
-// Exclusive scan of the per-tile outlier counts (66,308 entries for a 257^3 call; int64 offsets: a 513^3
-// lattice has 1.35e8 points) in two coalesced passes: k_scan_local scans 1,024 consecutive counts per
-// workgroup (scan_device.h: wave shuffles + one LDS hop) and records the chunk total, k_scan_apply adds the sum of the
-// preceding chunk totals.  (A single workgroup walking 65 strided entries per thread was latency-bound:
-// 0.12 ms - more than k_sign, the count and the compaction together.)
-// n_points_dev (adaptive levels): the call's size lives on the device - n = its number of 256-point blocks
-__global__ __launch_bounds__(1024) void k_scan_local(const int32_t *__restrict__ counts, int64_t n, int32_t *__restrict__ local, int64_t *__restrict__ part,
-                                                     const int *__restrict__ n_points_dev)
+// The f16x3 precision (the default) with the BVH search runs FUSED: no input rows in HBM (fused_f16x3.hip).
+// ICON_AMD_UNFUSED=1 forces the materialising path (tests compare the two bit for bit).
+bool want_fused(int precision, int search)
 {
-    __shared__ int64_t wtot[16];
-    if (n_points_dev) n = ((int64_t)*n_points_dev + kScanBlock - 1) / kScanBlock;
-    const int64_t i = (int64_t)blockIdx.x * 1024 + threadIdx.x;
-    const int64_t v = (i < n) ? counts[i] : 0;
-    int64_t total;
-    const int64_t ex = block_excl_scan<16>(v, wtot, total);
-    if (i < n) local[i] = (int32_t)ex;
-    if (threadIdx.x == 0) part[blockIdx.x] = total;
-}
-
-__global__ __launch_bounds__(1024) void k_scan_apply(const int32_t *__restrict__ local, const int64_t *__restrict__ part, int64_t nchunks, int64_t n,
-                                                     int64_t *__restrict__ offsets, int64_t *__restrict__ total, const int *__restrict__ n_points_dev)
-{
-    __shared__ int64_t wtot[16];
-    if (n_points_dev) n = ((int64_t)*n_points_dev + kScanBlock - 1) / kScanBlock;
-    // sum of the chunk totals before this chunk (and of all chunks, for *total): nchunks <= a few hundred
-    int64_t before = 0, all = 0;
-    for (int64_t k = threadIdx.x; k < nchunks; k += 1024) { const int64_t t = part[k]; all += t; if (k < blockIdx.x) before += t; }
-    int64_t sum_all, sum_before;
-    (void)block_excl_scan<16>(all, wtot, sum_all);
-    __syncthreads();
-    (void)block_excl_scan<16>(before, wtot, sum_before);
-    const int64_t i = (int64_t)blockIdx.x * 1024 + threadIdx.x;
-    if (i < n) offsets[i] = sum_before + local[i];
-    if (blockIdx.x == 0 && threadIdx.x == 0) *total = sum_all;
-}
-
-__device__ __forceinline__ int64_t outlier_rank(bool o, const int64_t *block_offsets, int *wsum)
-{
-    // exclusive rank of this thread's outlier among the outliers of the call (linear order)
-    const unsigned long long b = __ballot(o);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) wsum[w] = __popcll(b);
-    __syncthreads();
-    int before = 0;
-    for (int k = 0; k < w; ++k) before += wsum[k];
-    before += __popcll(b & ((1ull << lane) - 1ull));
-    return block_offsets[blockIdx.x] + before;
-}
-
-__global__ __launch_bounds__(kScanBlock) void k_outlier_compact(const uint8_t *__restrict__ code8, int64_t N,
-                                                                const int64_t *block_offsets, int8_t *signs, const int *__restrict__ n_dev)
-{
-    __shared__ int wsum[kScanBlock / 64];
-    if (n_dev) { N = *n_dev; if ((int64_t)blockIdx.x * kScanBlock >= N) return; }
-    const int64_t i = (int64_t)blockIdx.x * kScanBlock + threadIdx.x;
-    const uint32_t code = (i < N) ? code8[i] : 0u;
-    const bool o = code & kCodeOutlier;
-    const int64_t r = outlier_rank(o, block_offsets, wsum);
-    if (o) signs[r] = (int8_t)((int)((code >> kCodeSignShift) & 3u) - 1);
-}
-
-// scan + compact in ONE launch for calls of few blocks (the levels of the reference's schedule: 20,000 - 60,000 points, 80 - 250
-// blocks): every workgroup sums the counts before its own block itself (a few hundred ints from L2) instead of waiting for two
-// scan launches - three launches of ~5 us each were the launch floor, not work.  O(blocks^2) reads: the host picks it by size.
-__global__ __launch_bounds__(kScanBlock) void k_outlier_small(const int32_t *__restrict__ counts, const uint8_t *__restrict__ code8, int64_t N,
-                                                              int64_t *__restrict__ block_offsets, int64_t *__restrict__ total, int8_t *__restrict__ signs,
-                                                              const int *__restrict__ n_dev)
-{
-    __shared__ int wsum[kScanBlock / 64];
-    __shared__ int64_t red[2][kScanBlock / 64];
-    if (n_dev) N = *n_dev;
-    const int64_t nblk = (N + kScanBlock - 1) / kScanBlock;
-    if (blockIdx.x == 0 && threadIdx.x == 0 && nblk == 0) *total = 0;
-    if ((int64_t)blockIdx.x >= nblk) return;
-    int64_t before = 0, all = 0;
-    const bool want_all = blockIdx.x == 0;                       // block 0 also publishes the call's total
-    for (int64_t k = threadIdx.x; k < (want_all ? nblk : (int64_t)blockIdx.x); k += kScanBlock) { const int64_t t = counts[k]; all += t; if (k < blockIdx.x) before += t; }
-    for (int d = 32; d >= 1; d >>= 1) { before += __shfl_xor(before, d); all += __shfl_xor(all, d); }
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) { red[0][w] = before; red[1][w] = all; }
-    __syncthreads();
-    before = 0; all = 0;
-    for (int k = 0; k < kScanBlock / 64; ++k) { before += red[0][k]; all += red[1][k]; }
-    if (threadIdx.x == 0) { block_offsets[blockIdx.x] = before; if (want_all) *total = all; }
-    const int64_t i = (int64_t)blockIdx.x * kScanBlock + threadIdx.x;
-    const uint32_t code = (i < N) ? code8[i] : 0u;
-    const bool o = code & kCodeOutlier;
-    const unsigned long long b = __ballot(o);
-    if (lane == 0) wsum[w] = __popcll(b);
-    __syncthreads();
-    int64_t r = before + __popcll(b & ((1ull << lane) - 1ull));
-    for (int k = 0; k < w; ++k) r += wsum[k];
-    if (o) signs[r] = (int8_t)((int)((code >> kCodeSignShift) & 3u) - 1);
-}
-constexpr int64_t kSmallListBlocks = 16384;      // up to this many blocks (4.2 M points) the one-launch list; worst case 1 GB of L2 reads
-
-// cmap[j][k] = s[(3j + k) mod K]  with j = global outlier rank = rank_offset + local rank
-__global__ __launch_bounds__(kScanBlock) void k_outlier_patch(float *__restrict__ X, const uint8_t *__restrict__ code8, int64_t N, int cmap_slot,
-                                                              const int64_t *block_offsets, const int8_t *signs_global,
-                                                              int64_t k_total, int64_t rank_offset)
-{
-    __shared__ int wsum[kScanBlock / 64];
-    const int64_t i = (int64_t)blockIdx.x * kScanBlock + threadIdx.x;
-    const uint32_t code = (i < N) ? code8[i] : 0u;
-    const bool o = code & kCodeOutlier;
-    const int64_t j = rank_offset + outlier_rank(o, block_offsets, wsum);
-    if (o) {
-        float *row = X + i * kXRow + cmap_slot;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            int64_t mm = 3 * j + k;                 // j < K  =>  mm < 3K
-            if (mm >= k_total) mm -= k_total;
-            if (mm >= k_total) mm -= k_total;
-            row[k] = (float)signs_global[mm];
-        }
-    }
-}
-
-// The same patch with the global sign list left where the all_gather put it: rank r's message is
-// gathered + r * stride = [int64 count_r][int8 signs_r ...] (multi-GPU path, recon.py).  K, this
-// rank's offset and the segment of every index are derived on the device from the headers, so the
-// host never has to read the counts (no synchronisation between the exchange and the MLP launch).
-__global__ __launch_bounds__(kScanBlock) void k_outlier_patch_seg(float *__restrict__ X, const uint8_t *__restrict__ code8, int64_t N, int cmap_slot,
-                                                                  const int64_t *block_offsets, const int8_t *__restrict__ gathered,
-                                                                  int64_t stride, int world, int rank)
-{
-    __shared__ int wsum[kScanBlock / 64];
-    __shared__ int64_t off[kMaxWorld + 1];
-    if (threadIdx.x == 0) {
-        int64_t a = 0;
-        for (int r = 0; r < world; ++r) { off[r] = a; a += *reinterpret_cast<const int64_t *>(gathered + (int64_t)r * stride); }
-        off[world] = a;
-    }
-    __syncthreads();
-    const int64_t K = off[world];
-    const int64_t i = (int64_t)blockIdx.x * kScanBlock + threadIdx.x;
-    const uint32_t code = (i < N) ? code8[i] : 0u;
-    const bool o = code & kCodeOutlier;
-    const int64_t j = off[rank] + outlier_rank(o, block_offsets, wsum);
-    if (o && K > 0) {
-        float *row = X + i * kXRow + cmap_slot;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            int64_t mm = 3 * j + k;                 // j < K  =>  mm < 3K
-            if (mm >= K) mm -= K;
-            if (mm >= K) mm -= K;
-            int r = 0;
-            while (mm >= off[r + 1]) ++r;
-            const int64_t e = mm - off[r];                      // 2 bits per sign (sign + 1), four to a byte
-            const uint32_t byte = (uint8_t)gathered[(int64_t)r * stride + 8 + (e >> 2)];
-            row[k] = (float)((int)((byte >> (2 * (int)(e & 3))) & 3u) - 1);
-        }
-    }
-}
-
-// sign message of the multi-GPU exchange: [int64 K][K signs, 2 bits each (sign + 1), four to a byte, zero padded]
-__global__ __launch_bounds__(256) void k_pack_signs(const int8_t *__restrict__ signs, const int64_t *__restrict__ k_dev, uint8_t *__restrict__ msg, int64_t cap_bytes)
-{
-    const int64_t K = *k_dev;
-    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (t == 0) *reinterpret_cast<int64_t *>(msg) = K;
-    if (t >= cap_bytes || 4 * t >= K) return;
-    uint32_t b = 0;
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-        if (4 * t + j < K) b |= (uint32_t)(signs[4 * t + j] + 1) << (2 * j);
-    msg[8 + t] = (uint8_t)b;
-}
-
-// repack B feature stacks [B][C][H][W] -> B plane sets [n_select][H][W][cpad] (channel-last, zero padded), `stride` floats
-// apart; grid z = subject
-__global__ void k_pack_planes(const float *__restrict__ src, int C, int H, int W, int n_select, int csel, int cpad, int64_t stride,
-                              float *__restrict__ dst)
-{
-    const int64_t n = (int64_t)n_select * H * W * cpad;
-    const float *s = src + (int64_t)blockIdx.z * C * H * W;
-    float *d = dst + (int64_t)blockIdx.z * stride;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const int c = (int)(i % cpad);
-        const int64_t pix = (i / cpad) % ((int64_t)H * W);
-        const int sel = (int)(i / ((int64_t)cpad * H * W));
-        d[i] = (c < csel) ? s[((int64_t)(sel * csel + c)) * H * W + pix] : 0.0f;
-    }
+    return !option(kOptUnfused) && precision == ICON_PRECISION_F16X3 && search != ICON_SEARCH_BRUTE;
 }
 
 }  // namespace icon
@@ -501,413 +298,6 @@ extern "C" int icon_sdf_query(const icon_mesh_t *mesh, const float *d_points, in
     ICON_HIP(hipGetLastError());
     return ICON_OK;
 }
-
-// ---- feature handles: B plane sets (and, pamir prior, B volumes) at a fixed stride; icon_feat_create is B = 1 ----------------
-namespace {
-
-// allocates *dst and packs B stacks into it in one launch (B = 1: the grid of 1024 workgroups a single stack always had)
-int pack_planes(const float *d_src, int B, int C, int H, int W, int n_select, int cpad, hipStream_t st, const char *what, float **dst, int64_t *stride)
-{
-    *stride = (int64_t)n_select * H * W * cpad;
-    hipError_t e = hipMalloc((void **)dst, (size_t)*stride * B * sizeof(float));
-    if (e != hipSuccess) return fail(ICON_ERR_HIP, std::string("hipMalloc ") + what + ": " + hipGetErrorString(e));
-    hipLaunchKernelGGL(k_pack_planes, dim3((unsigned)std::max(1, 1024 / B), 1, (unsigned)B), dim3(256), 0, st, d_src, C, H, W, n_select,
-                       C / n_select, cpad, *stride, *dst);
-    e = hipGetLastError();
-    if (e != hipSuccess) { (void)hipFree(*dst); *dst = nullptr; return fail(ICON_ERR_HIP, std::string("pack ") + what + ": " + hipGetErrorString(e)); }
-    return ICON_OK;
-}
-
-// (the exported entry points have checked the arguments, each under its own name)
-int feat_create(const float *d_planes, int B, int C, int H, int W, int n_select, hipStream_t st, icon_feat_t **out)
-{
-    icon_feat *f = new icon_feat();
-    FeatDev &d = f->dev;
-    d.C = C; d.H = H; d.W = W; d.n_select = n_select; d.csel = C / n_select; d.cpad = (d.csel + 3) & ~3;
-    d.smpl_mask = kSmplCmap | kSmplNorm;
-    d.vol = nullptr; d.Cv = 0; d.Dv = d.Hv = d.Wv = 0; d.vpad = 0;
-    f->batch = B;
-    const int rc = pack_planes(d_planes, B, C, H, W, n_select, d.cpad, st, "planes", &f->d_planes, &f->plane_stride);
-    if (rc) { delete f; return rc; }
-    d.planes = f->d_planes;
-    *out = f;
-    return ICON_OK;
-}
-
-// a volume is a "plane" of H' = D*H rows: same channel-last repack, zero padded to vpad
-int feat_set_volume(icon_feat *f, const float *d_vol, int Cv, int Dv, int Hv, int Wv, hipStream_t st)
-{
-    const int vpad = (Cv + 3) & ~3;
-    const int rc = pack_planes(d_vol, f->batch, Cv, Dv * Hv, Wv, 1, vpad, st, "volume", &f->d_vol, &f->vol_stride);
-    if (rc) return rc;
-    FeatDev &d = f->dev;
-    d.vol = f->d_vol; d.Cv = Cv; d.Dv = Dv; d.Hv = Hv; d.Wv = Wv; d.vpad = vpad;
-    return ICON_OK;
-}
-
-}  // namespace
-
-extern "C" int icon_feat_create(const float *d_planes, int C, int H, int W, int n_select,
-                                const float *d_vol, int Cv, int Dv, int Hv, int Wv,
-                                void *stream, icon_feat_t **out)
-{
-    ICON_ARG(out != nullptr, "icon_feat_create: out is null");
-    *out = nullptr;
-    ICON_ARG(d_planes && C > 0 && H > 1 && W > 1, "icon_feat_create: bad planes");
-    ICON_ARG(n_select == 1 || n_select == 2, "icon_feat_create: n_select must be 1 or 2");
-    ICON_ARG(C % n_select == 0, "icon_feat_create: C not divisible by n_select");
-    if (C / n_select > 16) return fail(ICON_ERR_UNSUPPORTED, "icon_feat_create: more than 16 channels per tap");
-    if (d_vol) {
-        ICON_ARG(Cv > 0 && Dv > 1 && Hv > 1 && Wv > 1, "icon_feat_create: bad volume");
-        if (Cv > 8) return fail(ICON_ERR_UNSUPPORTED, "icon_feat_create: more than 8 volume channels");
-    }
-    icon_feat *f = nullptr;
-    int rc = feat_create(d_planes, 1, C, H, W, n_select, (hipStream_t)stream, &f);
-    if (!rc && d_vol && (rc = feat_set_volume(f, d_vol, Cv, Dv, Hv, Wv, (hipStream_t)stream))) icon_feat_destroy(f);
-    if (!rc) *out = f;
-    return rc;
-}
-
-extern "C" int icon_feat_create_batch(const float *d_planes, int B, int C, int H, int W, int n_select, void *stream, icon_feat_t **out)
-{
-    ICON_ARG(out != nullptr, "icon_feat_create_batch: out is null");
-    *out = nullptr;
-    ICON_ARG(d_planes && B >= 1 && C > 0 && H > 1 && W > 1, "icon_feat_create_batch: bad planes");
-    ICON_ARG(n_select == 1 || n_select == 2, "icon_feat_create_batch: n_select must be 1 or 2");
-    ICON_ARG(C % n_select == 0, "icon_feat_create_batch: C not divisible by n_select");
-    ICON_ARG(B <= 65535, "icon_feat_create_batch: more than 65,535 subjects");
-    if (C / n_select > 16) return fail(ICON_ERR_UNSUPPORTED, "icon_feat_create_batch: more than 16 channels per tap");
-    return feat_create(d_planes, B, C, H, W, n_select, (hipStream_t)stream, out);
-}
-
-extern "C" int icon_feat_batch_set_volume(icon_feat_t *feat, const float *d_vol, int B, int Cv, int Dv, int Hv, int Wv, void *stream)
-{
-    ICON_ARG(feat != nullptr && d_vol != nullptr, "icon_feat_batch_set_volume: null argument");
-    ICON_ARG(B == feat->batch, "icon_feat_batch_set_volume: the volume holds another number of subjects than the feature handle");
-    ICON_ARG(feat->dev.vol == nullptr, "icon_feat_batch_set_volume: the handle already holds a volume");
-    ICON_ARG(Cv > 0 && Dv > 1 && Hv > 1 && Wv > 1, "icon_feat_batch_set_volume: bad volume");
-    if (Cv > 8) return fail(ICON_ERR_UNSUPPORTED, "icon_feat_batch_set_volume: more than 8 volume channels");
-    return feat_set_volume(feat, d_vol, Cv, Dv, Hv, Wv, (hipStream_t)stream);
-}
-
-extern "C" int icon_feat_set_smpl_feats(icon_feat_t *f, int has_cmap, int has_norm)
-{
-    ICON_ARG(f != nullptr, "icon_feat_set_smpl_feats: feat is null");
-    f->dev.smpl_mask = (has_cmap ? kSmplCmap : 0) | (has_norm ? kSmplNorm : 0);
-    return ICON_OK;
-}
-
-extern "C" int icon_feat_destroy(icon_feat_t *f)
-{
-    if (!f) return ICON_OK;
-    (void)hipFree(f->d_planes); (void)hipFree(f->d_vol);
-    delete f;
-    return ICON_OK;
-}
-
-extern "C" int icon_work_create(icon_work_t **out)
-{
-    ICON_ARG(out != nullptr, "icon_work_create: out is null");
-    *out = new icon_work();
-    return ICON_OK;
-}
-
-extern "C" int icon_work_destroy(icon_work_t *w)
-{
-    if (!w) return ICON_OK;
-    (void)hipFree(w->d_x); (void)hipFree(w->d_grp_mask); (void)hipFree(w->d_block_counts); (void)hipFree(w->d_block_offsets); (void)hipFree(w->d_scan_local); (void)hipFree(w->d_scan_part);
-    (void)hipFree(w->d_signs); (void)hipFree(w->d_total); (void)hipFree(w->d_flag); (void)hipFree(w->d_seg); (void)hipFree(w->d_row_count); (void)hipFree(w->d_row_slots); (void)hipFree(w->d_lfast); if (w->h_err) (void)hipHostFree(w->h_err); if (w->h_any) (void)hipHostFree(w->h_any); (void)hipFree(w->d_near16); (void)hipFree(w->d_near_hi); (void)hipFree(w->d_near_d2); (void)hipFree(w->d_code8);
-    (void)hipFree(w->d_sort_keys); (void)hipFree(w->d_sort_idx); (void)hipFree(w->d_sort_tmp);
-    for (int k = 0; k < 6; ++k) if (w->ev[k]) (void)hipEventDestroy(w->ev[k]);
-    (void)hipFree(w->d_clock); (void)hipFree(w->d_steal);
-    icon::mc_destroy(w->mc);
-    icon::clean_destroy(w->clean);
-    icon::adaptive_destroy(w->ad);
-    delete w;
-    return ICON_OK;
-}
-
-// out[0] = the nearest-triangle search kernel alone (ms; 0 when the call had none), out[1] = shader cycles and out[2] = wall
-// time (ms) of the fused kernel's workgroup 0 (s_memtime / s_memrealtime stamps), out[3] = out[1] / out[2] as MHz - the
-// EFFECTIVE clock under that launch's load.  Synchronises (on the call's last event).
-extern "C" int icon_work_profile_detail(icon_work_t *w, double out[4])
-{
-    ICON_ARG(w != nullptr && out != nullptr, "icon_work_profile_detail: null argument");
-    if (!w->prof || !w->ev_valid) return fail(ICON_ERR_STATE, "icon_work_profile_detail: no profiled call on this workspace");
-    ICON_HIP(hipEventSynchronize(w->ev[3]));
-    out[0] = out[1] = out[2] = out[3] = 0.0;
-    if (w->ev_search) {
-        float ms = 0.0f;
-        ICON_HIP(hipEventElapsedTime(&ms, w->ev[4], w->ev[5]));
-        out[0] = ms;
-    }
-    unsigned long long c[4] = {0, 0, 0, 0};
-    ICON_HIP(hipMemcpy(c, w->d_clock, sizeof(c), hipMemcpyDeviceToHost));
-    int dev = 0, khz = 0;
-    ICON_HIP(hipGetDevice(&dev));
-    ICON_HIP(hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev));
-    if (c[2] > c[0] && c[3] > c[1] && khz > 0) {
-        out[1] = (double)(c[2] - c[0]);
-        out[2] = (double)(c[3] - c[1]) / (double)khz;
-        out[3] = out[1] / out[2] * 1e-3;
-    }
-    return ICON_OK;
-}
-
-// The workgroup records of the most recent profiled launch of the fused kernel.  rec[5 * b + ...] for workgroup b:
-// [0] XCC id, [1] start (ms after the earliest workgroup's start), [2] span (ms, constant-rate counter), [3] shader cycles,
-// [4] tiles evaluated.  *n = workgroups of that launch (at most cap are written).  Synchronises like icon_work_stage_ms.
-extern "C" int icon_work_profile_workgroups(icon_work_t *w, double *rec, int cap, int *n)
-{
-    ICON_ARG(w != nullptr && rec != nullptr && n != nullptr && cap >= 0, "icon_work_profile_workgroups: bad argument");
-    if (!w->prof || !w->ev_valid) return fail(ICON_ERR_STATE, "icon_work_profile_workgroups: no profiled call on this workspace");
-    ICON_HIP(hipEventSynchronize(w->ev[3]));
-    const int g = std::min(w->clock_grid, kMaxProfGrid);
-    *n = g;
-    if (g <= 0) return ICON_OK;
-    std::vector<unsigned long long> c((size_t)kWgRec * g);
-    ICON_HIP(hipMemcpy(c.data(), w->d_clock + 4, c.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    int dev = 0, khz = 0;
-    ICON_HIP(hipGetDevice(&dev));
-    ICON_HIP(hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev));
-    ICON_ARG(khz > 0, "icon_work_profile_workgroups: the device reports no wall clock rate");
-    unsigned long long t0 = ~0ull;
-    for (int b = 0; b < g; ++b) t0 = std::min(t0, c[(size_t)kWgRec * b + 1]);
-    for (int b = 0; b < g && b < cap; ++b) {
-        const unsigned long long *r = &c[(size_t)kWgRec * b];
-        rec[5 * b + 0] = (double)(r[4] >> 32);
-        rec[5 * b + 1] = (double)(r[1] - t0) / (double)khz;
-        rec[5 * b + 2] = (double)(r[3] - r[1]) / (double)khz;
-        rec[5 * b + 3] = (double)(r[2] - r[0]);
-        rec[5 * b + 4] = (double)r[5];
-    }
-    return ICON_OK;
-}
-
-// permille of every workgroup's span of tiles that is drawn dynamically (0 = the static partition of rounds 1-5), in contiguous
-// groups of `group` tiles (<= 127), own XCD's spans first.  Any setting gives the same volume bit for bit (a tile's result does not depend on who evaluates it).
-extern "C" int icon_work_set_steal(icon_work_t *w, int permille, int group)
-{
-    ICON_ARG(w != nullptr && permille >= 0 && permille <= 1000 && group >= 1 && group <= 127, "icon_work_set_steal: bad argument");
-    w->steal_permille = permille; w->steal_grp = group;
-    return ICON_OK;
-}
-
-namespace icon {
-// the stride-(sx, sy, sz) sub-lattice of a [res]^3 volume: one thread per point, one store per wavefront that finds a value above
-// the level into a HOST-MAPPED word (visible to the host once the stream has drained: no copy, no second launch)
-__global__ __launch_bounds__(256) void k_any_above(const float *__restrict__ occ, int res, int sx, int sy, int sz, int nx, int ny, int nz, float level, int *flag)
-{
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    bool pos = false;
-    if (i < (int64_t)nx * ny * nz) {
-        const int x = (int)(i % nx), y = (int)((i / nx) % ny), z = (int)(i / ((int64_t)nx * ny));
-        pos = occ[((int64_t)z * sz * res + (int64_t)y * sy) * res + (int64_t)x * sx] > level;
-    }
-    if (__any(pos) && (threadIdx.x & 63) == 0) *flag = 1;
-}
-}  // namespace icon
-
-// Seg3dLossless._forward_faster's None test (lib/common/seg3d_lossless.py:173-177: nothing above 0.5 on the COARSEST lattice) on a
-// dense device volume: *h_any = 1 when some point of the stride-(sx, sy, sz) sub-lattice exceeds `level`.  One kernel, then the
-// call waits for the stream (as the reference's `.sum() == 0` does) - four torch operators, a device-to-host copy and ~35 us of
-// GPU time before.
-extern "C" int icon_volume_any_above(const float *d_occ, int res, int sx, int sy, int sz, float level, icon_work_t *w, void *stream, int *h_any)
-{
-    ICON_ARG(d_occ && w && h_any && res >= 1 && sx >= 1 && sy >= 1 && sz >= 1, "icon_volume_any_above: bad argument");
-    if (!w->h_any) {
-        ICON_HIP(hipHostMalloc((void **)&w->h_any, sizeof(int), hipHostMallocMapped | hipHostMallocPortable));
-    }
-    void *dev = nullptr;
-    ICON_HIP(hipHostGetDevicePointer(&dev, w->h_any, 0));
-    *(volatile int *)w->h_any = 0;
-    const int nx = (res - 1) / sx + 1, ny = (res - 1) / sy + 1, nz = (res - 1) / sz + 1;
-    const int64_t n = (int64_t)nx * ny * nz;
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(icon::k_any_above, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_occ, res, sx, sy, sz, nx, ny, nz, level, (int *)dev);
-    ICON_HIP(hipGetLastError());
-    ICON_HIP(hipStreamSynchronize(st));
-    *h_any = *(volatile int *)w->h_any;
-    return ICON_OK;
-}
-
-extern "C" int icon_work_set_reserve_cus(icon_work_t *w, int n)
-{
-    ICON_ARG(w != nullptr && n >= 0, "icon_work_set_reserve_cus: bad argument");
-    w->reserve_cus = n;
-    return ICON_OK;
-}
-
-extern "C" int icon_work_profile(icon_work_t *w, int enable)
-{
-    ICON_ARG(w != nullptr, "icon_work_profile: work is null");
-    if (enable && !w->ev[0])
-        for (int k = 0; k < 6; ++k) ICON_HIP(hipEventCreate(&w->ev[k]));
-    if (enable && !w->d_clock) {
-        const size_t bytes = (size_t)(4 + kWgRec * kMaxProfGrid) * sizeof(unsigned long long);
-        ICON_HIP(hipMalloc((void **)&w->d_clock, bytes));
-        ICON_HIP(hipMemset(w->d_clock, 0, bytes));
-    }
-    w->clock_grid = 0;
-    w->ev_search = false;
-    w->prof = enable != 0;
-    w->ev_valid = false;
-    return ICON_OK;
-}
-
-extern "C" int icon_work_stage_ms(icon_work_t *w, float out_ms[3])
-{
-    ICON_ARG(w && out_ms, "icon_work_stage_ms: null argument");
-    if (!w->prof || !w->ev_valid) return fail(ICON_ERR_STATE, "icon_work_stage_ms: no profiled call on this workspace");
-    ICON_HIP(hipEventSynchronize(w->ev[3]));
-    for (int k = 0; k < 3; ++k) ICON_HIP(hipEventElapsedTime(&out_ms[k], w->ev[k], w->ev[k + 1]));
-    return ICON_OK;
-}
-
-namespace icon {
-// device-side K: same as k_outlier_patch but K and the list come from this call's own scan
-__global__ __launch_bounds__(kScanBlock) void k_outlier_patch_self(float *__restrict__ X, const uint8_t *__restrict__ code8, int64_t N, int cmap_slot,
-                                                                   const int64_t *block_offsets, const int8_t *signs,
-                                                                   const int64_t *k_total_dev)
-{
-    __shared__ int wsum[kScanBlock / 64];
-    const int64_t K = *k_total_dev;
-    const int64_t i = (int64_t)blockIdx.x * kScanBlock + threadIdx.x;
-    const uint32_t code = (i < N) ? code8[i] : 0u;
-    const bool o = code & kCodeOutlier;
-    const int64_t j = outlier_rank(o, block_offsets, wsum);
-    if (o) {
-        float *row = X + i * kXRow + cmap_slot;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            int64_t mm = 3 * j + k;
-            if (mm >= K) mm -= K;
-            if (mm >= K) mm -= K;
-            row[k] = (float)signs[mm];
-        }
-    }
-}
-}  // namespace icon
-
-namespace icon {
-// ---- the process-wide switches (test / A-B; production leaves all of them alone) ------------------------------------------------
-// id: the row's place, checked below against enum Opt (common.h); key: the name icon_debug_set_option knows it by (null: an ABI
-// function of its own sets it); env: the variable read ONCE, at the first use, unless a set came first; ok: the values a set
-// accepts (null: a flag - anything non-zero is 1, from the variable too)
-struct Option { Opt id; const char *key, *env; int def; bool (*ok)(int); const char *accepts; };
-static constexpr Option kOptions[kOptCount] = {
-    {kOptPairBox, "pair_box", "ICON_AMD_PAIR_BOX", 1},              // the packet walk culls leaf pairs by their oriented boxes    } meshes and mesh
-    {kOptNodeBox, "node_box", "ICON_AMD_NODE_BOX", 1},              // ... tests the children of the bottom inner nodes by them    } batches created
-    {kOptBoxClamp, "box_clamp", "ICON_AMD_BOX_CLAMP", 1},           // the lattice launches evaluate them in half units, clamped   } AFTERWARDS
-    {kOptLatticeFast, "lattice_fast", "ICON_AMD_LATTICE_FAST", 1},  // 0: every packet derives its own set-up (A/B runs)
-    {kOptUnfused, nullptr, "ICON_AMD_UNFUSED", 0},                  // icon_debug_set_unfused: 1 forces the materialising path
-    {kOptShellSkip, nullptr, "ICON_AMD_SHELL_SKIP", 1},             // icon_debug_set_shell_skip: 0 evaluates and masks the in_cube shell
-    {kOptShareWaves, "share_waves", "ICON_AMD_SHARE", -1,           // wavefronts per shared walk (4: the adaptive schedule's searches only)
-     [](int v) { return v == -1 || v == 1 || v == 4 || v == 8 || v == 16; }, "-1 (by launch size), 1, 4, 8 or 16"},
-    {kOptShareRing, "share_ring", nullptr, 0,                       // forced ring size of the shared walks (0 = 64)
-     [](int v) { return v == 0 || (v >= 2 && v <= 64 && (v & (v - 1)) == 0); }, "0 or a power of two in 2..64"},
-    {kOptShareLose, "share_lose_push", nullptr, 0,                  // the ticket of the push that is announced but never stored (0 = none)
-     [](int v) { return v >= 0; }, "a ticket >= 1, or 0"},
-    {kOptShareSpinLog2, "share_spin_log2", nullptr, 0,              // wait bound 2^n polls (0 = 2^18)
-     [](int v) { return v >= 0 && v < 30; }, "0..29"},
-};
-constexpr bool options_in_enum_order(int o = 0) { return o == kOptCount || (kOptions[o].id == o && options_in_enum_order(o + 1)); }
-static_assert(options_in_enum_order(), "kOptions[] must list the switches in the order of enum Opt");
-static int g_opt_value[kOptCount];
-static bool g_opt_known[kOptCount];          // the value was set, or read from the environment
-int option(Opt o)
-{
-    if (!g_opt_known[o]) {
-        const Option &e = kOptions[o];
-        const char *v = e.env ? getenv(e.env) : nullptr;
-        g_opt_value[o] = !v ? e.def : (e.ok ? atoi(v) : atoi(v) != 0);
-        g_opt_known[o] = true;
-    }
-    return g_opt_value[o];
-}
-static void set_option(Opt o, int value) { g_opt_value[o] = kOptions[o].ok ? value : (value != 0); g_opt_known[o] = true; }
-
-int work_share_dbg(icon_work *w, ShareDbg *out)
-{
-    if (!w->h_err) {
-        ICON_HIP(hipHostMalloc((void **)&w->h_err, 8 * sizeof(int), hipHostMallocMapped | hipHostMallocPortable));   // (portable: a process may drive several devices)
-        memset(w->h_err, 0, 8 * sizeof(int));
-    }
-    void *dev = nullptr;
-    ICON_HIP(hipHostGetDevicePointer(&dev, w->h_err, 0));
-    out->err = (int *)dev;
-    out->ring = option(kOptShareRing); out->lose = option(kOptShareLose); out->spin_log2 = option(kOptShareSpinLog2);
-    return ICON_OK;
-}
-
-int work_check_err(icon_work *w)
-{
-    if (!w || !w->h_err) return ICON_OK;
-    volatile int *e = w->h_err;
-    const int code = e[0];
-    if (code == 0 || code == kShareErrClaimed) return ICON_OK;     // (claimed: a wave is still writing the details - the next look reports it)
-    char buf[320];
-    static const char *what[] = {"", "a wave waited in vain for the node of its queue ticket (lost or abandoned push)",
-                                 "a wave waited in vain for its ring slot to be cleared (ring a full turn behind)",
-                                 "an idle wave outlasted its bound while the workgroup was still active"};
-    snprintf(buf, sizeof(buf), "shared-walk search: %s [code %d, workgroup %d, wave %d, ticket %d, head %d, tail %d, avail %d, active %d]; the results of "
-             "that launch are not to be trusted", what[code >= 1 && code <= 3 ? code : 0], code, e[1], e[7], e[2], e[3], e[4], e[5], e[6]);
-    for (int k = 0; k < 8; ++k) e[k] = 0;
-    return fail(ICON_ERR_STATE, buf);
-}
-
-
-void mark(icon_work *w, int k, hipStream_t st)
-{
-    if (w->prof) { (void)hipEventRecord(w->ev[k], st); if (k == 3) w->ev_valid = true; }
-}
-
-// scratch for n_points: (slot, d^2) + 1-byte codes + scan arrays + sign list; the 64-byte input rows only
-// for the paths that still materialise them (need_x: precision f32 and the brute-force search)
-int ensure_work(icon_work *w, int64_t n_points, bool need_x)
-{
-    { const int rc = work_check_err(w); if (rc) return rc; }      // an earlier launch on this workspace reported: no new work on its results
-    if (n_points > w->cap_points) {
-        (void)hipFree(w->d_near16); (void)hipFree(w->d_near_d2); w->d_near16 = nullptr; w->d_near_d2 = nullptr; w->cap_points = 0;
-        ICON_HIP(hipMalloc((void **)&w->d_near16, (size_t)n_points * sizeof(uint16_t)));
-        ICON_HIP(hipMalloc((void **)&w->d_near_d2, (size_t)n_points * sizeof(float)));
-        (void)hipFree(w->d_code8); w->d_code8 = nullptr;
-        ICON_HIP(hipMalloc((void **)&w->d_code8, (size_t)n_points));
-        w->cap_points = n_points;
-    }
-    if (need_x && n_points > w->cap_x) {
-        (void)hipFree(w->d_x); w->d_x = nullptr; w->cap_x = 0;
-        ICON_HIP(hipMalloc((void **)&w->d_x, (size_t)n_points * kXRow * sizeof(float)));
-        w->cap_x = n_points;
-    }
-    const int64_t nblk = (n_points + kScanBlock - 1) / kScanBlock;
-    if (nblk > w->cap_blocks) {
-        (void)hipFree(w->d_block_counts); (void)hipFree(w->d_block_offsets); (void)hipFree(w->d_scan_local); (void)hipFree(w->d_scan_part);
-        w->d_block_counts = nullptr; w->d_block_offsets = nullptr; w->d_scan_local = nullptr; w->d_scan_part = nullptr; w->cap_blocks = 0;
-        (void)hipFree(w->d_grp_mask); w->d_grp_mask = nullptr;
-        ICON_HIP(hipMalloc((void **)&w->d_grp_mask, (size_t)nblk * 4 * sizeof(uint64_t)));
-        ICON_HIP(hipMalloc((void **)&w->d_block_counts, (size_t)nblk * sizeof(int32_t)));
-        ICON_HIP(hipMalloc((void **)&w->d_block_offsets, (size_t)nblk * sizeof(int64_t)));
-        ICON_HIP(hipMalloc((void **)&w->d_scan_local, (size_t)nblk * sizeof(int32_t)));
-        ICON_HIP(hipMalloc((void **)&w->d_scan_part, (size_t)((nblk + 1023) / 1024) * sizeof(int64_t)));
-        w->cap_blocks = nblk;
-    }
-    if (n_points > w->cap_signs) {
-        (void)hipFree(w->d_signs); w->d_signs = nullptr; w->cap_signs = 0;
-        ICON_HIP(hipMalloc((void **)&w->d_signs, (size_t)n_points));
-        w->cap_signs = n_points;
-    }
-    if (!w->d_total) ICON_HIP(hipMalloc((void **)&w->d_total, sizeof(int64_t)));
-    if (!w->d_flag) ICON_HIP(hipMalloc((void **)&w->d_flag, sizeof(int)));
-    if (!w->d_steal) {
-        ICON_HIP(hipMalloc((void **)&w->d_steal, 9 * sizeof(unsigned int)));
-        ICON_HIP(hipMemset(w->d_steal, 0, 9 * sizeof(unsigned int)));     // (synchronous with respect to the host: ordered before any launch)
-    }
-    if (!w->d_seg) ICON_HIP(hipMalloc((void **)&w->d_seg, (kMaxWorld + 1) * sizeof(int64_t)));
-    return ICON_OK;
-}
-
-}  // namespace icon
 
 namespace {
 
@@ -1030,69 +420,6 @@ int launch_features(const icon_mesh_t *mesh, const icon_feat_t *feat, int prior,
     return ICON_OK;
 }
 
-}  // namespace
-
-namespace icon {
-// count + scan + compact over the codes of points [0, N): fills w->d_block_offsets, w->d_total, and `signs`
-int outlier_list(icon_work *w, int64_t N, int8_t *signs, bool counted, hipStream_t st)
-{
-    const int64_t nblk = (N + kScanBlock - 1) / kScanBlock;
-    // `counted`: k_sign already left the outlier count of every 256-point block in d_block_counts
-    if (!counted) hipLaunchKernelGGL(k_outlier_count, dim3((unsigned)nblk), dim3(kScanBlock), 0, st, w->d_code8, N, w->d_block_counts);
-    if (nblk <= 1024) {                           // a small call (host-known size): one launch
-        hipLaunchKernelGGL(k_outlier_small, dim3((unsigned)std::max<int64_t>(nblk, 1)), dim3(kScanBlock), 0, st, w->d_block_counts, w->d_code8, N, w->d_block_offsets, w->d_total,
-                           signs, (const int *)nullptr);
-        ICON_HIP(hipGetLastError());
-        debug_sync("outlier list (one launch)", st);
-        return ICON_OK;
-    }
-    const int64_t nchunks = (nblk + 1023) / 1024;
-    hipLaunchKernelGGL(k_scan_local, dim3((unsigned)nchunks), dim3(1024), 0, st, w->d_block_counts, nblk, w->d_scan_local, w->d_scan_part, (const int *)nullptr);
-    hipLaunchKernelGGL(k_scan_apply, dim3((unsigned)nchunks), dim3(1024), 0, st, w->d_scan_local, w->d_scan_part, nchunks, nblk, w->d_block_offsets, w->d_total, (const int *)nullptr);
-    hipLaunchKernelGGL(k_outlier_compact, dim3((unsigned)nblk), dim3(kScanBlock), 0, st, w->d_code8, N, w->d_block_offsets, signs, (const int *)nullptr);
-    ICON_HIP(hipGetLastError());
-    debug_sync("outlier scan + compact", st);
-    return ICON_OK;
-}
-
-// the call's outlier sign list when its size is known on the device only (k_sign left the block counts): w->d_signs, w->d_total
-int outlier_list_dev(icon_work *w, const int *n_dev, int64_t n_max, hipStream_t st)
-{
-    const int64_t nblk = (n_max + kScanBlock - 1) / kScanBlock;
-    if (nblk <= kSmallListBlocks) {               // (the size on the device is a few percent of n_max: see k_outlier_small)
-        hipLaunchKernelGGL(k_outlier_small, dim3((unsigned)std::max<int64_t>(nblk, 1)), dim3(kScanBlock), 0, st, w->d_block_counts, w->d_code8, n_max, w->d_block_offsets,
-                           w->d_total, w->d_signs, n_dev);
-        ICON_HIP(hipGetLastError());
-        return ICON_OK;
-    }
-    const int64_t nchunks = (nblk + 1023) / 1024;
-    hipLaunchKernelGGL(k_scan_local, dim3((unsigned)nchunks), dim3(1024), 0, st, w->d_block_counts, nblk, w->d_scan_local, w->d_scan_part, n_dev);
-    hipLaunchKernelGGL(k_scan_apply, dim3((unsigned)nchunks), dim3(1024), 0, st, w->d_scan_local, w->d_scan_part, nchunks, nblk, w->d_block_offsets, w->d_total, n_dev);
-    hipLaunchKernelGGL(k_outlier_compact, dim3((unsigned)nblk), dim3(kScanBlock), 0, st, w->d_code8, n_max, w->d_block_offsets, w->d_signs, n_dev);
-    ICON_HIP(hipGetLastError());
-    return ICON_OK;
-}
-int ensure_work_points(icon_work *w, int64_t n_points) { return ensure_work(w, n_points, false); }
-
-int patch_self(icon_work *w, int64_t N, int cmap_slot, hipStream_t st)
-{
-    const int64_t nblk = (N + kScanBlock - 1) / kScanBlock;
-    hipLaunchKernelGGL(k_outlier_patch_self, dim3((unsigned)nblk), dim3(kScanBlock), 0, st, w->d_x, w->d_code8, N, cmap_slot,
-                       w->d_block_offsets, w->d_signs, w->d_total);
-    ICON_HIP(hipGetLastError());
-    return ICON_OK;
-}
-
-// The f16x3 precision (the default) with the BVH search runs FUSED: no input rows in HBM (fused_f16x3.hip).
-// ICON_AMD_UNFUSED=1 forces the materialising path (tests compare the two bit for bit).
-bool want_fused(int precision, int search)
-{
-    return !option(kOptUnfused) && precision == ICON_PRECISION_F16X3 && search != ICON_SEARCH_BRUTE;
-}
-}  // namespace icon
-
-namespace {
-
 // Phase 1 of every query: what can be done before the outlier sign list of the whole call is known.
 //   icon prior, BVH: nearest search + k_sign (+ the call's own sign list in reference cmap mode); no rows yet
 //   icon prior, brute force: k_features (rows + codes) + sign list
@@ -1118,14 +445,14 @@ int phase1(const icon_mesh_t *mesh, const icon_feat_t *feat, int prior, float sd
     }
     if (work->slab_needs_patch) {
         int8_t *signs = d_signs_out ? d_signs_out : work->d_signs;
-        if ((rc = outlier_list(work, N, signs, search != ICON_SEARCH_BRUTE, st))) return rc;
+        if ((rc = outlier_list(work, N, nullptr, signs, search != ICON_SEARCH_BRUTE, st))) return rc;
     }
     return ICON_OK;
 }
 
 // The MLP input rows of the prepared call in work->d_x ([N, kXRow], reference channel order, slot kCodeSlot = code word),
 // the reference-mode outlier cmap patched in from wherever the call's sign list is.  Idempotent per prepared call.
-int materialise_rows(icon_work *work, const FusedSigns &fs, hipStream_t st)
+int materialise_rows(icon_work *work, const SignSrc &fs, hipStream_t st)
 {
     int rc;
     const int prior = work->q_prior;
@@ -1140,18 +467,7 @@ int materialise_rows(icon_work *work, const FusedSigns &fs, hipStream_t st)
         work->q_rows_ready = true;
     }
     if (work->slab_needs_patch && !work->slab_patched) {
-        const int64_t nblk = (N + kScanBlock - 1) / kScanBlock;
-        if (fs.mode == kSignSelf) {
-            if ((rc = patch_self(work, N, work->slab_cmap_slot, st))) return rc;
-        } else if (fs.mode == kSignGlobal) {
-            if (fs.k_host > 0)
-                hipLaunchKernelGGL(k_outlier_patch, dim3((unsigned)nblk), dim3(kScanBlock), 0, st, work->d_x, work->d_code8, N, work->slab_cmap_slot,
-                                   work->d_block_offsets, fs.list, fs.k_host, fs.rank_offset);
-        } else if (fs.mode == kSignSeg) {
-            hipLaunchKernelGGL(k_outlier_patch_seg, dim3((unsigned)nblk), dim3(kScanBlock), 0, st, work->d_x, work->d_code8, N, work->slab_cmap_slot,
-                               work->d_block_offsets, fs.gathered, fs.stride, fs.world, fs.rank);
-        }
-        ICON_HIP(hipGetLastError());
+        if ((rc = outlier_patch(work, N, work->slab_cmap_slot, fs, st))) return rc;
         work->slab_patched = true;
     }
     return ICON_OK;
@@ -1160,7 +476,7 @@ int materialise_rows(icon_work *work, const FusedSigns &fs, hipStream_t st)
 // Phase 2: the MLP input of every point and the MLP itself, given where the call's outlier signs are.
 // Lattice calls evaluate the planes [za, zb) of the prepared slab into the SLAB's buffer d_occ (several calls may
 // cover a slab piece by piece: the multi-GPU driver gathers the first half while the second is computed).
-int phase2(const icon_mlp_t *mlp, const FusedSigns &fs, float *d_occ, int precision, icon_work *work, hipStream_t st, int za = 0, int zb = 0)
+int phase2(const icon_mlp_t *mlp, const SignSrc &fs, float *d_occ, int precision, icon_work *work, hipStream_t st, int za = 0, int zb = 0)
 {
     int rc;
     const int prior = work->q_prior;
@@ -1188,21 +504,7 @@ int phase2(const icon_mlp_t *mlp, const FusedSigns &fs, float *d_occ, int precis
     return rc;
 }
 
-FusedSigns self_signs(const icon_work *work)
-{
-    FusedSigns fs{};
-    fs.mode = work->slab_needs_patch ? kSignSelf : kSignNone;
-    fs.list = work->d_signs; fs.k_dev = work->d_total;
-    return fs;
-}
-
 }  // namespace
-
-extern "C" int icon_debug_set_unfused(int on)
-{
-    set_option(kOptUnfused, on);
-    return ICON_OK;
-}
 
 static int query_points_impl(const icon_mesh_t *mesh, const icon_feat_t *feat, const icon_mlp_t *mlp,
                              int prior_type, float sdf_clip, int cmap_mode, const float *h_calib, const float *d_calib,
@@ -1227,7 +529,7 @@ static int query_points_impl(const icon_mesh_t *mesh, const icon_feat_t *feat, c
     mark(work, 0, st);
     if ((rc = phase1<false>(mesh, feat, prior_type, sdf_clip, cmap_mode, cal, L, d_points, N, search, nullptr, work, st))) return rc;
     mark(work, 1, st);
-    return phase2(mlp, self_signs(work), d_occ, precision, work, st);
+    return phase2(mlp, self_signs(work, work->slab_needs_patch), d_occ, precision, work, st);
 }
 
 extern "C" int icon_query_points(const icon_mesh_t *mesh, const icon_feat_t *feat, const icon_mlp_t *mlp,
@@ -1306,10 +608,7 @@ static int slab_features_impl(const icon_mesh_t *mesh, const icon_feat_t *feat, 
         const int64_t cap = msg_bytes - 8;                 // packed bytes available
         ICON_ARG(msg_bytes >= 8 && cap * 4 >= N, "icon_grid_slab_features_msg: message buffer too small (8 + ceil(points / 4) bytes)");
         if (work->slab_needs_patch) {
-            const int64_t nb = (std::max<int64_t>(cap, 1) + 255) / 256;
-            hipLaunchKernelGGL(k_pack_signs, dim3((unsigned)nb), dim3(256), 0, st, d_signs_local ? d_signs_local : work->d_signs, work->d_total,
-                               (uint8_t *)d_msg, cap);
-            ICON_HIP(hipGetLastError());
+            if ((rc = pack_sign_message(work, d_signs_local ? d_signs_local : work->d_signs, d_msg, cap, st))) return rc;
         } else {
             ICON_HIP(hipMemsetAsync(d_msg, 0, sizeof(int64_t), st));
         }
@@ -1344,7 +643,7 @@ extern "C" int icon_grid_slab_finish(const icon_mlp_t *mlp, int res, int z0, int
     if (!work->slab_ready || work->slab_res != res || work->slab_z0 != z0 || work->slab_z1 != z1)
         return fail(ICON_ERR_STATE, "icon_grid_slab_finish: no matching icon_grid_slab_features call on this workspace");
     ICON_ARG(work->slab_c0 == mlp->c0, "icon_grid_slab_finish: MLP input width does not match the feature layout");
-    FusedSigns fs{};
+    SignSrc fs{};
     if (work->slab_needs_patch) {
         ICON_ARG(k_total == 0 || d_signs_global != nullptr, "icon_grid_slab_finish: sign list is null");
         fs.mode = kSignGlobal; fs.list = d_signs_global; fs.k_host = k_total; fs.rank_offset = rank_offset;
@@ -1362,14 +661,14 @@ extern "C" int icon_grid_slab_finish_gathered(const icon_mlp_t *mlp, int res, in
         return fail(ICON_ERR_STATE, "icon_grid_slab_finish_gathered: no matching icon_grid_slab_features call on this workspace");
     ICON_ARG(za >= z0 && zb > za && zb <= z1, "icon_grid_slab_finish_gathered: planes [za, zb) must lie inside the slab");
     ICON_ARG(work->slab_c0 == mlp->c0, "icon_grid_slab_finish_gathered: MLP input width does not match the feature layout");
-    FusedSigns fs{};
+    SignSrc fs{};
     if (work->slab_needs_patch) {
         if (d_gathered) {
             ICON_ARG(world >= 1 && world <= kMaxWorld && rank >= 0 && rank < world, "icon_grid_slab_finish_gathered: bad world / rank");
             ICON_ARG(stride >= 8 && (stride & 7) == 0, "icon_grid_slab_finish_gathered: stride must be a multiple of 8 (int64 header)");
             fs.mode = kSignSeg; fs.gathered = (const int8_t *)d_gathered; fs.stride = stride; fs.world = world; fs.rank = rank;
         } else {
-            fs = self_signs(work);              // no exchange: the slab's own list is the whole list
+            fs = self_signs(work, work->slab_needs_patch);              // no exchange: the slab's own list is the whole list
         }
     }
     // the slab stays prepared: its planes may be finished piece by piece (the next icon_grid_slab_features replaces it)
@@ -1379,7 +678,7 @@ extern "C" int icon_grid_slab_finish_gathered(const icon_mlp_t *mlp, int res, in
 // ---- the MLP input rows of a call, handed out (regressors whose normalisation runs over the points of the call) ----
 static int copy_rows_out(icon_work *work, float *d_rows, hipStream_t st)
 {
-    int rc = materialise_rows(work, self_signs(work), st);
+    int rc = materialise_rows(work, self_signs(work, work->slab_needs_patch), st);
     if (rc) return rc;
     ICON_HIP(hipMemcpyAsync(d_rows, work->d_x, (size_t)work->q_N * kXRow * sizeof(float), hipMemcpyDeviceToDevice, st));
     return ICON_OK;
@@ -1487,50 +786,7 @@ extern "C" int icon_grid_eval_slab(const icon_mesh_t *mesh, const icon_feat_t *f
     ICON_ARG(work->slab_c0 == mlp->c0, "icon_grid_eval_slab: MLP input width does not match the feature layout");
     // the slab's own sign list is the whole list (single call == whole lattice or caller's choice)
     work->slab_ready = false;
-    return phase2(mlp, self_signs(work), d_occ, precision, work, (hipStream_t)stream, z0, z1);
-}
-
-// the shared walks' error record (see work_check_err): ICON_ERR_STATE once per reported error, then clear again.  Does not
-// synchronise - a caller that wants the verdict on a particular launch synchronises its stream first.
-extern "C" int icon_work_status(icon_work_t *work)
-{
-    ICON_ARG(work != nullptr, "icon_work_status: work is null");
-    return work_check_err(work);
-}
-
-// the switches of the table above by name, and the two that live with their own code
-extern "C" int icon_debug_set_option(const char *key, int value)
-{
-    ICON_ARG(key != nullptr, "icon_debug_set_option: key is null");
-    const std::string k(key);
-    for (int o = 0; o < kOptCount; ++o) {
-        const Option &e = kOptions[o];
-        if (!e.key || k != e.key) continue;
-        ICON_ARG(!e.ok || e.ok(value), k + ": " + e.accepts);
-        set_option((Opt)o, value);
-        return ICON_OK;
-    }
-    if (k == "qc_lanes") { ICON_ARG(value == 0 || value == 64, "qc_lanes: 0 (default) or 64"); g_qc_lanes = value; }
-    else if (k == "rn_lanes") { ICON_ARG(value == 0 || value == 1 || value == 8, "rn_lanes: 0 (default), 1 or 8"); g_rn_lanes = value; }
-    else if (k == "tt_chunk") { ICON_ARG(value >= 0 && value <= 32, "tt_chunk: 0 (default) or 1..32"); g_tt_chunk = value; }
-    else if (k == "ev_lanes") { ICON_ARG(value == 0 || value == 1 || value == 8, "ev_lanes: 0 (default), 1 or 8"); g_ev_lanes = value; }
-    else return fail(ICON_ERR_ARG, "icon_debug_set_option: unknown key " + k);
-    return ICON_OK;
-}
-
-extern "C" int icon_debug_set_shell_skip(int on)
-{
-    set_option(kOptShellSkip, on);
-    return ICON_OK;
-}
-
-extern "C" int icon_work_set_tie_rule(icon_work_t *work, int rule, int ulps)
-{
-    ICON_ARG(work != nullptr, "icon_work_set_tie_rule: work is null");
-    ICON_ARG(rule == 0 || rule == 1, "icon_work_set_tie_rule: rule must be 0 (definition) or 1 (highest index within ulps)");
-    ICON_ARG(ulps >= 0 && ulps <= 255, "icon_work_set_tie_rule: ulps must be 0..255");
-    work->tie_rule = rule; work->tie_ulps = ulps;
-    return ICON_OK;
+    return phase2(mlp, self_signs(work, work->slab_needs_patch), d_occ, precision, work, (hipStream_t)stream, z0, z1);
 }
 
 extern "C" int icon_sdf_query_ties(const icon_mesh_t *mesh, const float *d_points, int64_t N,

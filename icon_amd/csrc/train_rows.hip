@@ -5,9 +5,9 @@
 // Forward (icon_train_rows_forward): the B*N points in subject-major order, as the batched query takes them.
 //   icon : batch_geometry (batch_query.hip: search, sign pass, batch-global outlier list - the launches of icon_query_points_batch),
 //          k_tr_point (SMPL channels of a point by sdf_attrs, its in_cube flag, its tap record), the existing cmap patch over those
-//          channels (patch_self), k_tr_rows (a lane per point and stack: the bilinear tap of S7 from the caller's [B,C,H,W] planes)
+//          channels (outlier_patch), k_tr_rows (a lane per point and stack: the bilinear tap of S7 from the caller's [B,C,H,W] planes)
 //   pifu : k_tr_point (z, in_cube, tap record), k_tr_rows
-// The SMPL channels live in the workspace's row buffer ([B*N][16], slots 0 .. 6 = sdf | cmap | norm), which is what patch_self
+// The SMPL channels live in the workspace's row buffer ([B*N][16], slots 0 .. 6 = sdf | cmap | norm), which is what outlier_patch
 // patches; every stack's rows copy them, so two stacks share them bit for bit.
 //
 // Backward (icon_train_rows_backward): no floating-point atomics.  k_tr_keys gives every point the key of its north-west cell
@@ -68,8 +68,8 @@ __global__ __launch_bounds__(kBlock) void k_tr_point(TrShape q, BatchDev bd, con
         float s = o.sdf;
         f3 cmv = o.cm;
         if (code & kCodeOutlier) {            // HGPIFuNet.py:298-305
-            s = (float)((int)((code >> kCodeSignShift) & 3u) - 1);
-            if (cmap_local) cmv = mk3(s, s, s);   // reference mode: patched from the sign list (patch_self)
+            s = (float)code_sign(code);
+            if (cmap_local) cmv = mk3(s, s, s);   // reference mode: patched from the sign list (outlier_patch)
         }
         half = (q.n_select == 2 && o.vis == 0.0f) ? 1u : 0u;     // feat_select: vis == 1 -> front half
         row[0] = s;
@@ -286,7 +286,7 @@ extern "C" int icon_train_rows_forward(const icon_mesh_batch_t *mb, int prior_ty
         hipLaunchKernelGGL(k_tr_point<ICON_PRIOR_PIFU>, dim3(nb), dim3(kBlock), 0, st, q, bd, d_points, sdf_clip, local, near,
                            (const uint8_t *)work->d_code8, work->d_x, d_in_cube, taps);
     ICON_HIP(hipGetLastError());
-    if (needs_patch && (rc = patch_self(work, NB, 1, st))) return rc;
+    if ((rc = outlier_patch(work, NB, 1, self_signs(work, needs_patch), st))) return rc;
     if (icon_prior)
         hipLaunchKernelGGL(k_tr_rows<ICON_PRIOR_ICON>, dim3(nb, (unsigned)S), dim3(kBlock), 0, st, q, stacks, (const TrTap *)taps, (const float *)work->d_x, d_rows);
     else

@@ -634,7 +634,7 @@ class IconQueryEngine:
         """Raise if a shared-walk search launched on one of this engine's workspaces gave up on a hand-over (icon_work_status:
         a host read of each workspace's error record).  Like poll_mesh_status, for callers that have just synchronised: the
         volume of THAT call is the suspect one - without this the record would only surface when the next call on the
-        workspace refuses to start (query_kernels.hip: ensure_work), one image late."""
+        workspace refuses to start (work.hip: ensure_work), one image late."""
         works = [self.work] + list(self.__dict__.get("_extra_works", {}).values())
         for w in works:
             if w is not None and w.h:

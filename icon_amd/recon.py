@@ -58,6 +58,13 @@ def slab_bounds(res: int, world_size: int, rank: int, weights=None):
     return z0, z1, max(b - a for a, b in parts)
 
 
+def sign_message_bytes(points: int) -> int:
+    """Bytes of a rank's message of the sign exchange for a slab of ``points`` lattice points:
+    [int64 count][2 bits per outlier sign, four to a byte], padded to a multiple of 8 (the int64 headers of the
+    gathered buffer stay aligned)."""
+    return 8 + ((points + 3) // 4 + 7) // 8 * 8
+
+
 def plane_weights(res: int, z_lo: float, z_hi: float, far_cost: float = 1.04) -> np.ndarray:
     """Relative cost of the lattice planes for a body whose vertices span [z_lo, z_hi] in world z: planes farther
     than the clip band from the body are pure far-field, where the exact nearest-triangle search visits more
@@ -389,7 +396,7 @@ class DenseReconEngine(nn.Module):
         z0, z1 = parts[rank]
         per = max(b - a for a, b in parts)
         # message of the sign exchange: [int64 count][2 bits per outlier sign, padded to the largest slab], 8-byte aligned
-        stride = 8 + ((per * res * res + 3) // 4 + 7) // 8 * 8
+        stride = sign_message_bytes(per * res * res)
         slab, msg = self._shard_buffers((res, world, rank, str(dev), per), per, res, stride, dev)
         need_exchange = (getattr(be, "cmap_mode", "local") == "reference" and getattr(be, "prior_type", "icon") == "icon"
                          and "cmap" in getattr(be, "smpl_feats", ("cmap",)))   # the tiled cmap rule is what couples the ranks
@@ -418,7 +425,7 @@ class DenseReconEngine(nn.Module):
         split = bool(pieces and need_exchange and per_a < per and getattr(be, "split_features", False) and 2 * world <= 64)
         order = []                                           # what was enqueued, in order (tests read it)
         if split:
-            stride_h = 8 + ((per_a * res * res + 3) // 4 + 7) // 8 * 8
+            stride_h = sign_message_bytes(per_a * res * res)
             hkey = (res, world, rank, str(dev), per_a)
             if getattr(self, "_shard_half_key", None) != hkey:
                 self._shard_half_msg = torch.zeros((2, stride_h), dtype=torch.int8, device=dev)
@@ -551,7 +558,7 @@ class DenseReconEngine(nn.Module):
             raise IconAmdError(f"gather_to={dst}: no such rank in a group of {world}")
         key = (res, world, rank, str(dev), "ab")
         if getattr(self, "_ab_key", None) != key:
-            stride = 8 + ((pa * res * res + 3) // 4 + 7) // 8 * 8
+            stride = sign_message_bytes(pa * res * res)
             self._ab_slab = [torch.zeros((pa, res, res), dtype=torch.float32, device=dev), torch.zeros((max(pb, 1), res, res), dtype=torch.float32, device=dev)]
             self._ab_msg = torch.zeros((2, stride), dtype=torch.int8, device=dev)
             self._ab_stride = stride

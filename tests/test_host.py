@@ -363,6 +363,25 @@ def test_hot_kernels_do_not_spill():
         assert v["ScratchSize [bytes/lane]"] == 0 and v["Occupancy [waves/SIMD]"] == 8, (k, v)
 
 
+def test_sign_message_bytes():
+    """the size of a rank's sign message (recon.sign_message_bytes): a multiple of 8 - the int64 headers of the gathered buffer
+    stay aligned - that holds the header and 2 bits per point, which is what icon_grid_slab_features_msg checks; and, for the
+    three sizes _forward_sharded / _forward_sharded_ab derive at res 257 in a world of 8 (a whole slab, its first half, an
+    'ab' piece), the value the formula written out at those sites gave"""
+    from icon_amd.recon import DenseReconEngine, sign_message_bytes, slab_partition
+    for n in (0, 1, 3, 4, 5, 31, 32, 33, 257 * 257 * 33):
+        b = sign_message_bytes(n)
+        assert b % 8 == 0 and b >= 8 + -(-n // 4), (n, b)
+    res, world = 257, 8
+    per = max(b - a for a, b in slab_partition(res, world, None))
+    per_a = (per + 1) // 2
+    pa = DenseReconEngine.ab_pieces(res, world)[0]
+    assert (per, per_a, pa) == (33, 17, 17)
+    for planes in (per, per_a, pa):
+        assert sign_message_bytes(planes * res * res) == 8 + ((planes * res * res + 3) // 4 + 7) // 8 * 8
+    assert sign_message_bytes(33 * 257 * 257) == 544920 and sign_message_bytes(17 * 257 * 257) == 280720
+
+
 @pytest.mark.parametrize("mesh", ["ico", "body", "dup"])
 def test_host_mesh_builder_invariants(mesh):
     """the host builder (icon_amd/csrc/mesh_build.cpp, the checker of the device build) through icon_debug_host_mesh_build - pure

@@ -3,7 +3,7 @@
 usage: tools/kernel_resources.py fused_f16x3.hip [filter]"""
 import os, re, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EXACT = {"fused_f16x3.hip", "query_kernels.hip", "batch_query.hip", "adaptive.hip", "mesh_device.hip", "mc_device.hip", "vox_kernels.hip", "vis_kernels.hip", "query_color.hip", "render_normal.hip", "silhouette.hip", "render_normal_bwd.hip"}
+EXACT = {"fused_f16x3.hip", "query_kernels.hip", "outlier_list.hip", "feat.hip", "work.hip", "batch_query.hip", "adaptive.hip", "mesh_device.hip", "mc_device.hip", "vox_kernels.hip", "vis_kernels.hip", "query_color.hip", "render_normal.hip", "silhouette.hip", "render_normal_bwd.hip"}
 
 
 def remarks(src):
