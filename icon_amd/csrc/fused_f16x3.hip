@@ -57,6 +57,7 @@ struct FusedGeom {
     Calib cal;
     int res, z0;                 // lattice mode: resolution, first plane of the slab (linear index i is relative to it)
     int off, nx, zs;             //   work item q -> (off + q % nx, off + (q / nx) % nx, zs + q / nx^2), nx = res - 2 off
+    uint32_t nx_magic;           //   udiv_magic(nx): the two divisions are a multiply-high each (geom_device.h), exact for every q
     const float *pts;            // point mode
     int64_t N;                   // work items of this launch
     const int *n_dev;            // point mode, adaptive levels: the number of work items lives on the device (N is its upper bound)
@@ -281,7 +282,7 @@ __global__ __launch_bounds__(256) void k_shell_zero(float *__restrict__ out, int
 __device__ __forceinline__ int64_t lattice_item(const FusedGeom &G, int64_t q, int &ix, int &iy, int &iz)
 {
     const uint32_t nx = (uint32_t)G.nx, qq = (uint32_t)q;          // N < 2^31 (checked by the launcher)
-    const uint32_t r = qq / nx, lx = qq - r * nx, lz = r / nx, ly = r - lz * nx;
+    const uint32_t r = udiv_fast(qq, nx, G.nx_magic), lx = qq - r * nx, lz = udiv_fast(r, nx, G.nx_magic), ly = r - lz * nx;
     ix = G.off + (int)lx; iy = G.off + (int)ly; iz = G.zs + (int)lz;
     return ((int64_t)(iz - G.z0) * G.res + iy) * G.res + ix;
 }
@@ -463,17 +464,25 @@ __global__ __launch_bounds__(kF16Block, 2) void k_fused_f16x3(FusedGeom G, float
         const bool more = tile + 1 < tile_end || nb >= 0;       // the first chunks of the next tile ride on the last ones
         if (SMALL && wave >= (tp >> 5)) {
             // a wave without points (128-point tiles): its share of the weight stream, the same barriers as the body below
-            for (int c = 0; c < 16; ++c) {
-                issue_chunk(w.image, smem + ((c + 1) & 1) * kBufBytes, c + 1, wave, lane);
+            // (two chunks per iteration like layer01: odd chunks into the second buffer, even ones into the first)
+#pragma nounroll
+            for (int c = 0; c < 14; c += 2) {
+                issue_chunk_units<32>(w.image, smem + kBufBytes, c + 1, wave, lane);
+                ICON_CHUNK_BARRIER();
+                issue_chunk_units<32>(w.image, smem, c + 2, wave, lane);
                 ICON_CHUNK_BARRIER();
             }
-            issue_chunk(w.image, smem + kBufBytes, 17, wave, lane);
+            issue_chunk_units<32>(w.image, smem + kBufBytes, 15, wave, lane);
             ICON_CHUNK_BARRIER();
-            issue_chunk(w.image, smem, 18, wave, lane);
+            issue_chunk_units<40>(w.image, smem, 16, wave, lane);
             ICON_CHUNK_BARRIER();
-            issue_chunk(w.image, smem + kBufBytes, 19, wave, lane);
+            issue_chunk_units<32>(w.image, smem + kBufBytes, 17, wave, lane);
             ICON_CHUNK_BARRIER();
-            if (more) issue_chunk(w.image, smem, 0, wave, lane);
+            issue_chunk_units<32>(w.image, smem, 18, wave, lane);
+            ICON_CHUNK_BARRIER();
+            issue_chunk_units<32>(w.image, smem + kBufBytes, 19, wave, lane);
+            ICON_CHUNK_BARRIER();
+            if (more) issue_chunk_units<32>(w.image, smem, 0, wave, lane);
             ++tile;
             continue;
         }
@@ -489,19 +498,8 @@ __global__ __launch_bounds__(kF16Block, 2) void k_fused_f16x3(FusedGeom G, float
         for (int m = 0; m < 16; ++m) acc1[m][0] = acc1[m][1] = *reinterpret_cast<const f32x4 *>(sb1 + m * 16 + 4 * g);
         half8 bh[2], bl[2];
         const LeakyK k0{w.inv0, w.p0, w.q0}, k1{w.inv1, w.p1, w.q1};
-        {
-            f32x4 h0[2][2];
-            l0_tiles(smem + kW0Off, sb0, 0, xb, g, lane, h0);
-            activate_split(h0[0][0], h0[0][1], h0[1][0], h0[1][1], k0, bh, bl);
-        }
         f32x4 acc2[8][2];
-        for (int c = 0; c < 15; ++c) {
-            l01_chunk<false>(smem + (c & 1) * kBufBytes, smem + ((c + 1) & 1) * kBufBytes, smem + kW0Off, sb0, w.image, c, acc1, xb,
-                             k0, g, lane, wave, bh, bl);
-            ICON_CHUNK_BARRIER();
-        }
-        l01_chunk<true>(smem + kBufBytes, smem, smem + kW0Off, sb0, w.image, 15, acc1, xb, k0, g, lane, wave, bh, bl);
-        ICON_CHUNK_BARRIER();
+        layer01(smem, sb0, w.image, acc1, xb, k0, g, lane, wave, bh, bl);
 #pragma unroll
         for (int m2 = 0; m2 < 8; ++m2) acc2[m2][0] = acc2[m2][1] = *reinterpret_cast<const f32x4 *>(sb2 + m2 * 16 + 4 * g);
         activate_split(acc1[0][0], acc1[1][0], acc1[0][1], acc1[1][1], k1, bh, bl);
@@ -511,7 +509,7 @@ __global__ __launch_bounds__(kF16Block, 2) void k_fused_f16x3(FusedGeom G, float
         ICON_CHUNK_BARRIER();
         l2_chunk<2>(smem, smem + kBufBytes, w.image, acc1, acc2, xb, k1, g, lane, wave, bh, bl);
         ICON_CHUNK_BARRIER();
-        l2_chunk<3>(smem + kBufBytes, smem, w.image, acc1, acc2, xb, k1, g, lane, wave, bh, bl, more ? 0 : -1);
+        l2_chunk<3>(smem + kBufBytes, smem, w.image, acc1, acc2, xb, k1, g, lane, wave, bh, bl, more);
 
         // ---- layer 3 on the VALU (f32) ---------------------------------------------------------------------
         float y2[2];
@@ -676,6 +674,7 @@ int launch_fused_f16x3(const icon_mesh *mesh, const icon_feat *feat, const icon_
             if (rows > 0) hipLaunchKernelGGL(k_shell_zero, dim3((unsigned)(row_wgs + (face_rows + 3) / 4)), dim3(256), 0, st, d_occ, L.res, L.z0, za, zb, row_wgs);
         }
         G.res = L.res; G.z0 = L.z0; G.off = L.off; G.nx = L.res - 2 * L.off; G.zs = zs;
+        G.nx_magic = udiv_magic((uint32_t)std::max(G.nx, 1));
         N = (ze > zs) ? (int64_t)(ze - zs) * G.nx * G.nx : 0;
     }
     if (N <= 0) { ICON_HIP(hipGetLastError()); return ICON_OK; }

@@ -69,18 +69,7 @@ __global__ __launch_bounds__(kF16Block, 2) void k_mlp_f16x3(const float *__restr
     // ---- layers 0 + 1: one chunk = 32 hidden channels ------------------------------------------
     half8 bh[2], bl[2];
     const LeakyK k0{w.inv0, w.p0, w.q0}, k1{w.inv1, w.p1, w.q1};
-    {
-        f32x4 h0[2][2];
-        l0_tiles(smem + kW0Off, sb0, 0, xb, g, lane, h0);
-        activate_split(h0[0][0], h0[0][1], h0[1][0], h0[1][1], k0, bh, bl);
-    }
-    for (int c = 0; c < 15; ++c) {
-        l01_chunk<false>(smem + (c & 1) * kBufBytes, smem + ((c + 1) & 1) * kBufBytes, smem + kW0Off, sb0, w.image, c, acc1, xb,
-                         k0, g, lane, wave, bh, bl);
-        ICON_CHUNK_BARRIER();   // all waves done with this buffer AND the next chunk has landed
-    }
-    l01_chunk<true>(smem + kBufBytes, smem, smem + kW0Off, sb0, w.image, 15, acc1, xb, k0, g, lane, wave, bh, bl);
-    ICON_CHUNK_BARRIER();
+    layer01(smem, sb0, w.image, acc1, xb, k0, g, lane, wave, bh, bl);
 
     // ---- layer 2: K = 256 (registers) + 16 (raw input) ---------------------------------------------
     f32x4 acc2[8][2];

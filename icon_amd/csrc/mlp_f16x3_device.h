@@ -112,6 +112,18 @@ __device__ __forceinline__ half8 lds_op(const char *buf, int slot, int lane)
 {
     return *reinterpret_cast<const half8 *>(buf + slot * 1024 + lane * 16);
 }
+// A lane's LDS address as ONE 32-bit register the optimiser cannot take apart again (base of the LDS map + lane part): what
+// the bodies below add to it are immediates of the ds_read.  Left transparent, such an address is re-derived at every use as
+// lane part + base + constant - two or three vector instructions in front of the read.
+typedef __attribute__((address_space(3))) const char *lds_cptr;
+typedef __attribute__((address_space(3))) const half8 *lds_half8;
+typedef __attribute__((address_space(3))) const f32x4 *lds_f32x4;
+__device__ __forceinline__ lds_cptr lds_lane_address(const void *p)
+{
+    unsigned a = (unsigned)(size_t)(__attribute__((address_space(3))) const void *)p;
+    asm("" : "+v"(a));
+    return (lds_cptr)(size_t)a;
+}
 
 // (The timing-only variants of round 3 - builds that remove one component of these bodies and give WRONG results by
 //  construction - live in tools/probes/exp_r03/, a snapshot of this header with its ICON_EXP_* switches; the product
@@ -128,6 +140,33 @@ __device__ __forceinline__ void issue_units(const char *src, char *buf, int unit
 __device__ __forceinline__ void issue_chunk(const char *image, char *buf, int k, int wave, int lane)
 {
     issue_units(image + (size_t)chunk_offset(k) * 1024, buf, chunk_units(k), wave, lane);
+}
+// The same pieces in the same order for a unit count known at compile time (the chunks inside the tile loop: 32 units, 40 for
+// chunk 16 - 4 or 5 per wave): straight-line, `src` / `dst` = the wave's FIRST piece (wave-uniform: the scalar unit adds the
+// 8 KiB between a wave's pieces), the lane's 16 bytes the only vector operand - the run-time form above costs a branch and a
+// 64-bit vector add per piece.  (The piece's base goes through an empty asm with a scalar constraint: left to itself the
+// compiler folds the lane's offset into a 64-bit VECTOR base outside the chunk loop and adds the piece offsets to that.)
+// lane_off: lane * 16, a register of the caller's that passes through an empty asm HERE, in the block of the loads - the
+// scalar-base form is only chosen with the 32-bit offset in sight, not with a 64-bit copy of it hoisted out of the chunk loop.
+template <int UNITS>
+__device__ __forceinline__ void issue_wave_units(const char *src, char *dst, unsigned &lane_off)
+{
+    constexpr int kWaves = kF16Block / 64;
+    static_assert(UNITS % kWaves == 0, "every wave issues the same number of pieces");
+    asm volatile("" : "+v"(lane_off));
+#pragma unroll
+    for (int j = 0; j < UNITS / kWaves; ++j) {
+        const char *piece = src + j * kWaves * 1024;
+        asm volatile("" : "+s"(piece));
+        __builtin_amdgcn_global_load_lds((gvoid_t *)(piece + lane_off), (lvoid_t *)(dst + j * kWaves * 1024), 16, 0, 0);
+    }
+}
+// chunk k (a constant, or one of a run of equally sized chunks: layer 1) -> buf
+template <int UNITS>
+__device__ __forceinline__ void issue_chunk_units(const char *image, char *buf, int k, int wave, int lane)
+{
+    unsigned lane_off = (unsigned)lane * 16u;
+    issue_wave_units<UNITS>(image + (size_t)(chunk_offset(k) + wave) * 1024, buf + wave * 1024, lane_off);
 }
 
 // The per-chunk bodies take the buffer being READ, the buffer being FILLED and the side arrays as
@@ -185,16 +224,31 @@ __device__ __forceinline__ void raw_operands(const char *__restrict__ base, int 
     a2 = *reinterpret_cast<const half8 *>(base + lo_off + tile * lo_mul);
 }
 
-// layer 0, hidden channels 32c..32c+31 of both point blocks (h0[b][t]: channel tile 2c + t): 8 MFMAs from the resident W0 region
-__device__ __forceinline__ void l0_tiles(const char *__restrict__ W0, const float *__restrict__ sb0, int c, const half8 (&xb)[2],
-                                         int g, int lane, f32x4 (&h0)[2][2])
+// Where a lane reads the layer-0 operands of the channel tiles not yet multiplied: running LDS addresses, advanced by layer01
+// once per PAIR of chunks (the four tiles of a pair are immediates on them) - a tile index times 1024 / 64 re-derived per
+// chunk was eight vector instructions of shifts, a multiplication and adds.  Only the [W_lo | 0] operand moves per tile: lanes
+// g >= 2 stay on the zeros (step 0), which no immediate can say.  Set up per TILE from the opaque thread index like every
+// lane-dependent address (fused_f16x3.hip).
+struct L0At { lds_cptr hi, lo, bias; int lo_step; };
+__device__ __forceinline__ L0At l0_begin(const char *W0, const float *sb0, int g, int lane)
+{
+    const int col = (lane & 31) * 16;
+    return L0At{lds_lane_address(W0 + col), lds_lane_address(W0 + (g < 2 ? 512 + col : kZeroFromW0)), lds_lane_address(sb0 + 4 * g), g < 2 ? 1024 : 0};
+}
+
+// layer 0, 32 hidden channels of both point blocks (h0[b][t]: channel tile T + K + t, T = the tile hi / bias stand at, lo at
+// T + K): 8 MFMAs from the resident W0 region; operands as raw_operands() names them.  The addresses are __restrict__
+// parameters BY VALUE: the reads stay provably apart from the LDS-DMA destination of the chunk body they are inlined into.
+template <int K>
+__device__ __forceinline__ void l0_tiles(lds_cptr __restrict__ hi, lds_cptr __restrict__ lo, int lo_step, lds_cptr __restrict__ bias,
+                                         const half8 (&xb)[2], f32x4 (&h0)[2][2])
 {
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
-        const f32x4 bias = *reinterpret_cast<const f32x4 *>(sb0 + (2 * c + t) * 16 + 4 * g);
-        half8 a1, a2;
-        raw_operands(W0, 2 * c + t, kZeroFromW0, g, lane, a1, a2);
-        h0[0][t] = MFMA32(a1, xb[0], bias); h0[1][t] = MFMA32(a1, xb[1], bias);
+        const f32x4 b = *(lds_f32x4)(bias + (K + t) * 64);
+        const half8 a1 = *(lds_half8)(hi + (K + t) * 1024);
+        const half8 a2 = *(lds_half8)(lo + t * lo_step);
+        h0[0][t] = MFMA32(a1, xb[0], b); h0[1][t] = MFMA32(a1, xb[1], b);
         h0[0][t] = MFMA32(a2, xb[0], h0[0][t]); h0[1][t] = MFMA32(a2, xb[1], h0[1][t]);
     }
 }
@@ -226,33 +280,73 @@ __device__ __forceinline__ void activate_split(const f32x4 &ta0, const f32x4 &tb
     for (int k = 0; k < 8; ++k) act_part(ta0, tb0, ta1, tb1, k, inv, bh, bl);
 }
 
-// layer 1, chunk c (K = hidden channels 32c..32c+31 = ONE k-step, B operands bh/bl prepared one iteration
-// earlier) SOFTWARE-PIPELINED with layer 0 of chunk c+1: its eight MFMAs are issued first; its
+// layer 1, one chunk (K = 32 hidden channels = ONE k-step, B operands bh/bl prepared one chunk
+// earlier) SOFTWARE-PIPELINED with layer 0 of the next chunk: its eight MFMAs are issued first; its
 // LeakyReLU + hi/lo split (pure VALU, 8 parts) is slotted behind every second of the sixteen 6-MFMA groups of this
 // chunk, and the LDS reads of group t+1 are issued ahead of the MFMAs of group t.  sched_barrier
 // pins that interleave so the matrix pipe and the VALU run side by side instead of alternating.
-// The last chunk has no successor: it runs without the layer-0 part.  Tile t: hi in slot 2t, lo in 2t + 1.
-template <bool LAST>
-__device__ __forceinline__ void l01_chunk(const char *__restrict__ L, char *__restrict__ nxt, const char *__restrict__ W0,
-                                          const float *__restrict__ sb0, const char *image, int c, f32x4 (&acc1)[16][2],
-                                          const half8 (&xb)[2], const LeakyK &inv0, int g4, int lane, int wave,
-                                          half8 (&bh)[2], half8 (&bl)[2])
+// The next chunk's B operands are built in nh/nl - registers of their own: the caller swaps the two sets from chunk to chunk
+// (layer01), there is no hand-over copy.  The last chunk has no successor: it runs without the layer-0 part and DMAs
+// chunk 16 (40 units).  Tile t: hi in slot 2t, lo in 2t + 1.  next_src: the wave's first piece of the next chunk;
+// K0: the next chunk's layer-0 tiles as l0_tiles<K0> counts them.  L: the LANE's 16 bytes of slot 0 of the buffer read.
+template <bool LAST, int K0>
+__device__ __forceinline__ void l01_chunk(lds_cptr __restrict__ L, char *__restrict__ nxt, lds_cptr __restrict__ w_hi,
+                                          lds_cptr __restrict__ w_lo, int lo_step, lds_cptr __restrict__ bias, const char *next_src,
+                                          f32x4 (&acc1)[16][2], const half8 (&xb)[2], const LeakyK &inv0, unsigned &lane_off, int wave,
+                                          const half8 (&bh)[2], const half8 (&bl)[2], half8 (&nh)[2], half8 (&nl)[2])
 {
-    issue_chunk(image, nxt, c + 1, wave, lane);
+    issue_wave_units<LAST ? 40 : 32>(next_src, nxt + wave * 1024, lane_off);
     f32x4 h0n[2][2];
-    if (!LAST) l0_tiles(W0, sb0, c + 1, xb, g4, lane, h0n);
-    half8 nh[2], nl[2];
+    if (!LAST) l0_tiles<K0>(w_hi, w_lo, lo_step, bias, xb, h0n);
     half8 a[2][2];
-    a[0][0] = lds_op(L, 0, lane); a[0][1] = lds_op(L, 1, lane);
+    a[0][0] = *(lds_half8)L; a[0][1] = *(lds_half8)(L + 1024);
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int t = 0; t < 16; ++t) {
-        if (t + 1 < 16) { a[(t + 1) & 1][0] = lds_op(L, 2 * t + 2, lane); a[(t + 1) & 1][1] = lds_op(L, 2 * t + 3, lane); }
+        if (t + 1 < 16) { a[(t + 1) & 1][0] = *(lds_half8)(L + (2 * t + 2) * 1024); a[(t + 1) & 1][1] = *(lds_half8)(L + (2 * t + 3) * 1024); }
         GROUP6(acc1, t, a[t & 1][0], a[t & 1][1], bh, bl)
         if (!LAST && (t & 1)) act_part(h0n[0][0], h0n[0][1], h0n[1][0], h0n[1][1], t >> 1, inv0, nh, nl);
         __builtin_amdgcn_sched_barrier(0);
     }
-    if (!LAST) { bh[0] = nh[0]; bh[1] = nh[1]; bl[0] = nl[0]; bl[1] = nl[1]; }
+}
+
+// layers 0 + 1 of a tile: layer 0 of hidden tiles 0, 1, then chunks 0..15 TWO per loop iteration, so that the buffer a chunk
+// reads and the one it fills are constants (every LDS address of the body is the lane's offset plus an immediate) and the two
+// sets of B-operand registers swap roles instead of being copied: the even chunk reads bh/bl from the first buffer and fills
+// nh/nl, the odd chunk the reverse.  7 pairs + the pair (14, 15-LAST); chunk 16 lands in the first buffer.  One barrier per
+// chunk: all waves done with the buffer AND the next chunk has landed.  bh/bl: scratch registers of the caller (layer 2's).
+__device__ __forceinline__ void layer01(char *smem, const float *sb0, const char *image, f32x4 (&acc1)[16][2], const half8 (&xb)[2],
+                                        const LeakyK &inv0, int g, int lane, int wave, half8 (&bh)[2], half8 (&bl)[2])
+{
+    char *const buf0 = smem, *const buf1 = smem + kBufBytes;
+    // the lane's column of the two buffers: a register each (the second buffer ends 6 KiB beyond the reach of an immediate)
+    const lds_cptr col0 = lds_lane_address(buf0 + lane * 16), col1 = lds_lane_address(buf1 + lane * 16);
+    unsigned lane_off = (unsigned)lane * 16u;
+    L0At at = l0_begin(smem + kW0Off, sb0, g, lane);
+    {
+        f32x4 h0[2][2];
+        l0_tiles<0>(at.hi, at.lo, at.lo_step, at.bias, xb, h0);
+        activate_split(h0[0][0], h0[0][1], h0[1][0], h0[1][1], inv0, bh, bl);
+    }
+    // `at` stands at tile 0: the even chunk 2p multiplies layer 0 of tiles 4p + 2, 4p + 3, the odd one 4p + 4, 4p + 5
+    at.lo += 2 * at.lo_step;
+    const char *src = image + (size_t)(chunk_offset(1) + wave) * 1024;      // chunk c + 1, this wave's first piece (scalar)
+    half8 nh[2], nl[2];
+#pragma nounroll
+    for (int p = 0; p < 7; ++p) {
+        l01_chunk<false, 2>(col0, buf1, at.hi, at.lo, at.lo_step, at.bias, src, acc1, xb, inv0, lane_off, wave, bh, bl, nh, nl);
+        at.lo += 2 * at.lo_step;
+        ICON_CHUNK_BARRIER();
+        l01_chunk<false, 4>(col1, buf0, at.hi, at.lo, at.lo_step, at.bias, src + 32 * 1024, acc1, xb, inv0, lane_off, wave, nh, nl, bh, bl);
+        at.lo += 2 * at.lo_step;
+        ICON_CHUNK_BARRIER();
+        at.hi += 4 * 1024; at.bias += 4 * 64;
+        src += 64 * 1024;
+    }
+    l01_chunk<false, 2>(col0, buf1, at.hi, at.lo, at.lo_step, at.bias, src, acc1, xb, inv0, lane_off, wave, bh, bl, nh, nl);
+    ICON_CHUNK_BARRIER();
+    l01_chunk<true, 0>(col1, buf0, at.hi, at.lo, at.lo_step, at.bias, src + 32 * 1024, acc1, xb, inv0, lane_off, wave, nh, nl, bh, bl);
+    ICON_CHUNK_BARRIER();
 }
 
 // layer 2, chunk 16+Q: k-steps 2Q, 2Q+1 = hidden tiles 4Q..4Q+3 (+ the raw-input k-step in front of the first chunk).
@@ -261,11 +355,11 @@ __device__ __forceinline__ void l01_chunk(const char *__restrict__ L, char *__re
 template <int Q>
 __device__ __forceinline__ void l2_chunk(const char *__restrict__ L, char *__restrict__ nxt, const char *image,
                                          f32x4 (&acc1)[16][2], f32x4 (&acc2)[8][2], const half8 (&xb)[2], const LeakyK &inv1,
-                                         int g4, int lane, int wave, half8 (&bh)[2], half8 (&bl)[2], int next_chunk = (Q < 3) ? 17 + Q : -1)
+                                         int g4, int lane, int wave, half8 (&bh)[2], half8 (&bl)[2], bool issue_next = Q < 3)
 {
-    // next_chunk: the chunk DMA'd into `nxt` while this one is multiplied; the persistent kernel passes 0 for
-    // Q == 3 (chunk 0 of its NEXT tile) - issued from inside this body so that it shares the alias scopes
-    if (next_chunk >= 0) issue_chunk(image, nxt, next_chunk, wave, lane);
+    // the chunk DMA'd into `nxt` while this one is multiplied: 17 + Q; behind Q == 3 the persistent kernel asks for chunk 0
+    // of its NEXT tile - issued from inside this body so that it shares the alias scopes
+    if (issue_next) issue_chunk_units<32>(image, nxt, Q < 3 ? 17 + Q : 0, wave, lane);
     if (Q == 0) {
         // raw inputs first: tiles of 1 KiB behind the 32 KiB of hidden k-steps (chunk 16 always lands in the FIRST buffer)
 #pragma unroll

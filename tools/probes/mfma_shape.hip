@@ -199,19 +199,8 @@ __global__ __launch_bounds__(kF16Block, 2) void k_probe(ProbeArgs w)
             f32x4 acc1[16][2];
 #pragma unroll
             for (int m = 0; m < 16; ++m) acc1[m][0] = acc1[m][1] = *reinterpret_cast<const f32x4 *>(sb1 + m * 16 + 4 * g4);
-            {
-                f32x4 h0[2][2];
-                l0_tiles(smem + kW0Off, sb0, 0, xb, g4, lane, h0);
-                activate_split(h0[0][0], h0[0][1], h0[1][0], h0[1][1], inv0, bh, bl);
-            }
-            for (int c = 0; c < 16; ++c) {
-                // (the product's last chunk runs without the layer-0 part; the probe keeps the steady-state body: at chunk 15 it
-                //  reads layer-0 tiles 32 and 33 = the first 2 KiB behind the 32 KiB W0 region, i.e. of the 4.25 KiB side arrays,
-                //  and their "bias" at side floats 512..543 - in bounds, and random numbers like everything else here)
-                l01_chunk<false>(smem + (c & 1) * kBufBytes, smem + ((c + 1) & 1) * kBufBytes, smem + kW0Off, sb0, chunks, c, acc1, xb,
-                                 inv0, g4, lane, wave, bh, bl);
-                ICON_CHUNK_BARRIER();
-            }
+            // the product's layers 0 + 1 as they are (the last chunk runs without the layer-0 part and DMAs chunk 16)
+            layer01(smem, sb0, chunks, acc1, xb, inv0, g4, lane, wave, bh, bl);
 #pragma unroll
             for (int m = 0; m < 16; ++m)
 #pragma unroll
