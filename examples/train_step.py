@@ -4,13 +4,16 @@ from ``sample_geo_device``, a one-convolution stand-in for the hourglass filter 
 ``icon_amd.training.attach`` as the network's ``query``, MSE against the labels and Adam - the shape of ``ICON.training_step``
 (apps/ICON.py:178-236): ``netG.train()``, ``netG(in_tensor_dict)`` = filter -> query -> get_error, backward, step.
 
-    python examples/train_step.py [--steps 40] [--batch 2] [--points 2000] [--prior icon|pifu]
+    python examples/train_step.py [--steps 40] [--batch 2] [--points 2000] [--prior icon|pifu|pamir]
 
 Needs an MI355X (there is no CPU path).  ``StandInNet`` follows HGPIFuNet's interface as far as the step uses it; its regressor
-is lib/net/MLP.py restated (Conv1d stack, norm per ``norm``, LeakyReLU, the input re-concatenated before ``res_layers``)."""
+is lib/net/MLP.py restated (Conv1d stack, norm per ``norm``, LeakyReLU, the input re-concatenated before ``res_layers``).
+``PamirStandInNet`` adds what the pamir prior's step uses: the voxel tensors in ``smpl_feat_dict``, a small volume encoder ``ve`` whose
+parameters the optimizer owns, and the ``voxelization`` attributes the semantic voxeliser reads."""
 import argparse
 import os
 import sys
+from types import SimpleNamespace
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
@@ -91,6 +94,42 @@ class StandInNet(nn.Module):
         return preds[-1], self.get_error(preds, in_tensor_dict["label"])
 
 
+class SmallVolumeEncoder(nn.Module):
+    """A volume encoder of VolumeEncoder's call contract (``ve(vol, intermediate_output)`` -> one [B,Cv,res/4,res/4,res/4] volume per
+    stack, or the last one alone): two stride-2 Conv3d + BatchNorm3d + ReLU, then per stack a residual Conv3d + BatchNorm3d block.
+    Every parameter takes part in the output of the last stack."""
+
+    def __init__(self, num_in=3, num_out=7, num_stack=2, width=8):
+        super().__init__()
+        self.conv1, self.bn1 = nn.Conv3d(num_in, width, 3, stride=2, padding=1), nn.BatchNorm3d(width)
+        self.conv2, self.bn2 = nn.Conv3d(width, num_out, 3, stride=2, padding=1), nn.BatchNorm3d(num_out)
+        self.res = nn.ModuleList(nn.Sequential(nn.Conv3d(num_out, num_out, 3, padding=1), nn.BatchNorm3d(num_out)) for _ in range(num_stack))
+
+    def forward(self, x, intermediate_output=True):
+        out = F.relu(self.bn2(self.conv2(F.relu(self.bn1(self.conv1(x))))))
+        outs = []
+        for block in self.res:
+            out = out + torch.tanh(block(out))
+            outs.append(out)
+        return outs if intermediate_output else outs[-1:]
+
+
+class PamirStandInNet(StandInNet):
+    """StandInNet for ``prior_type='pamir'`` (configs/train/pamir.yaml: hourglass_dim 6, voxel_dim 7, num_stack 2): ``filter`` also
+    binds the four voxel tensors, ``ve`` is a SmallVolumeEncoder, ``voxelization`` carries what the semantic voxeliser reads (the
+    surface vertices' code, the volume's resolution, sigma) and the regressor takes ``[img | vol]`` = channels + vol_channels."""
+
+    def __init__(self, vertex_code, channels=6, vol_channels=7, num_stack=2, volume_res=128, sigma=0.05, norm="batch", in_channels=6):
+        super().__init__(prior_type="pamir", smpl_feats=(), channels=channels, num_stack=num_stack, norm=norm, in_channels=in_channels)
+        self.if_regressor = Regressor((channels + vol_channels, 512, 256, 128, 1), norm=norm, last_op=nn.Sigmoid())
+        self.ve = SmallVolumeEncoder(3, vol_channels, num_stack)
+        self.voxelization = SimpleNamespace(smpl_vertex_code=np.asarray(vertex_code, np.float32), volume_res=volume_res, sigma=sigma)
+
+    def filter(self, in_tensor_dict):
+        self.smpl_feat_dict = {k: in_tensor_dict[k] for k in ("voxel_verts", "voxel_faces", "pad_v_num", "pad_f_num")}
+        return super().filter(in_tensor_dict)
+
+
 def _rot(axis, a):
     c, s = np.cos(a), np.sin(a)
     i, j = [(1, 2), (2, 0), (0, 1)][axis]
@@ -99,9 +138,11 @@ def _rot(axis, a):
     return R
 
 
-def make_batch(B, N, device, seed=0, size=128, in_channels=6):
+def make_batch(B, N, device, seed=0, size=128, in_channels=6, prior="icon"):
     """B synthetic subjects (the synthetic body moved, scaled and re-lit per subject, its own calibration), N samples each with
-    labels from ``sample_geo_device`` (the body is its own scan here), smooth random input maps -> the step's ``in_tensor_dict``"""
+    labels from ``sample_geo_device`` (the body is its own scan here), smooth random input maps -> the step's ``in_tensor_dict``.
+    ``prior='pamir'``: also the tetrahedralised body of every subject (``synth.make_tetra_body``) padded as a batch delivers it -
+    ``voxel_verts`` / ``voxel_faces`` with pad counts that differ across subjects - and ``vertex_code``, the surface code table"""
     from icon_amd import synth
     from icon_amd.sampling import ScanMesh, sample_geo_device
     v0, f = synth.load_body_mesh()
@@ -109,6 +150,7 @@ def make_batch(B, N, device, seed=0, size=128, in_channels=6):
     c = 0.5 * (v0.min(0) + v0.max(0))
     rng = np.random.RandomState(seed + 4242)
     d = {k: [] for k in ("smpl_verts", "smpl_faces", "smpl_vis", "smpl_cmap", "calib", "sample", "label", "image")}
+    tetra = []
     T = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(device)
     for b in range(B):
         ay, s, t = rng.uniform(-0.6, 0.6), rng.uniform(0.85, 1.05), rng.uniform(-0.06, 0.06, 3)
@@ -125,7 +167,17 @@ def make_batch(B, N, device, seed=0, size=128, in_channels=6):
         d["smpl_verts"].append(T(v)); d["smpl_faces"].append(T(f)); d["smpl_vis"].append(T(vis)); d["smpl_cmap"].append(T(cmap))
         d["calib"].append(T(K.astype(np.float32))); d["sample"].append(samples.t().contiguous()); d["label"].append(labels[None])
         d["image"].append(T(synth.make_feature_planes(in_channels, size, synth.SEED + 97 * b + seed)[0]))
-    return {k: torch.stack(v) for k, v in d.items()}
+        if prior == "pamir":
+            tetra.append(synth.make_tetra_body(v, f, cmap))
+    out = {k: torch.stack(v) for k, v in d.items()}
+    if prior == "pamir":
+        # subject b carries pad counts of its own; the reference strips every subject with subject 0's (lib/net/HGPIFuNet.py:316-319)
+        pad_v, pad_f = [5 + 2 * (b % 3) for b in range(B)], [9 - 3 * (b % 3) for b in range(B)]
+        vv = np.stack([np.concatenate([t[0], np.zeros((pad_v[0], 3), np.float32)]) for t in tetra]).astype(np.float32)
+        tets = np.concatenate([tetra[0][1], np.zeros((pad_f[0], 4), np.int64)])
+        out.update(voxel_verts=T(vv), voxel_faces=T(np.repeat(tets[None], B, 0)), pad_v_num=T(np.asarray(pad_v, np.int64)),
+                   pad_f_num=T(np.asarray(pad_f, np.int64)), vertex_code=T(tetra[0][2]))
+    return out
 
 
 def train_step(netG, optimizer, batch):
@@ -143,17 +195,21 @@ def main():
     ap.add_argument("--steps", type=int, default=40)
     ap.add_argument("--batch", type=int, default=2)
     ap.add_argument("--points", type=int, default=2000)
-    ap.add_argument("--prior", default="icon", choices=("icon", "pifu"))
+    ap.add_argument("--prior", default="icon", choices=("icon", "pifu", "pamir"))
     ap.add_argument("--lr", type=float, default=1e-3)
     args = ap.parse_args()
     from icon_amd import _lib, training
     _lib.require_device()
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
-    netG = StandInNet(prior_type=args.prior).to(dev)
-    training.attach(netG)
+    batch = make_batch(args.batch, args.points, dev, prior=args.prior)
+    if args.prior == "pamir":
+        netG = PamirStandInNet(batch["vertex_code"].cpu().numpy()).to(dev)
+        training.attach(netG, voxelizer="hip")
+    else:
+        netG = StandInNet(prior_type=args.prior).to(dev)
+        training.attach(netG)
     opt = torch.optim.Adam(netG.parameters(), lr=args.lr)
-    batch = make_batch(args.batch, args.points, dev)
     print(f"{args.prior}: B = {args.batch}, N = {args.points}, inside {float(batch['label'].mean()):.3f}")
     errors = [train_step(netG, opt, batch) for _ in range(args.steps)]
     for k, e in enumerate(torch.stack(errors).tolist()):

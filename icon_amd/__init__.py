@@ -4,7 +4,7 @@ Public surface (mirrors the reference's query interface, see icon_amd/engine.py)
     IconQueryEngine.query      == HGPIFuNet.query        (lib/net/HGPIFuNet.py:268-367)
     query_func                 == lib/common/train_util.py:324-348
     DenseReconEngine           == the reconEngine object (lib/common/seg3d_lossless.py:36)
-    training.attach            == HGPIFuNet.query in train mode: native rows of every stack + their gradient (icon_amd/training.py)
+    training.attach            == HGPIFuNet.query in train mode: native rows of every stack + their gradient (icon_amd/training.py; icon, pifu and pamir)
 The compute path is libicon_amd.so (include/icon_amd.h); there is no CPU fallback.
 """
 __version__ = "0.1.0"

@@ -48,6 +48,7 @@ SYMBOLS = [
     "icon_normal_consistency_bytes", "icon_normal_consistency",
     "icon_sample_geo_bytes", "icon_sample_geo",
     "icon_train_rows_bytes", "icon_train_rows_forward", "icon_train_rows_backward",
+    "icon_train_pamir_forward", "icon_train_vol_bytes", "icon_train_vol_backward",
 ]
 
 _lib = None

@@ -209,6 +209,53 @@ __device__ __forceinline__ BilinearTaps bilinear_taps(float x, float y, int H, i
     return t;
 }
 
+// The same for one 5-D grid_sample position (trilinear, zeros padding, align_corners=True) in a [D][H][W] volume: x indexes W, y
+// H, z D - ATen's grid_sampler_3d statement.  Corner k = 4 dz + 2 dy + dx (z0 before z1; inside a z: y0x0, y0x1, y1x0, y1x1); its
+// weight is (x-term * y-term) * z-term with the terms (x1 - ix) for the lower and (ix - x0) for the upper corner of an axis; in[k]:
+// the corner lies inside the volume.  The sample of a channel is the eight products t_k * w[k] added left to right in corner
+// order, an outside corner contributing the float 0 (trilinear_sample).  Callers are compiled with -ffp-contract=off.  The
+// training rows and their gradient (train_rows.hip) use it; inference keeps gather_volume (geom_device.h).
+struct TrilinearTaps {
+    int x0, y0, z0;             // the north-west-front corner; the others are + 1 per axis
+    float w[8];
+    bool in[8];
+    bool any;                   // some corner lies inside: then x0 in [-1, W - 1], y0 in [-1, H - 1], z0 in [-1, D - 1]
+};
+__device__ __forceinline__ TrilinearTaps trilinear_taps(float x, float y, float z, int D, int H, int W)
+{
+    TrilinearTaps t;
+    const float ix = ((x + 1.0f) / 2.0f) * (float)(W - 1);
+    const float iy = ((y + 1.0f) / 2.0f) * (float)(H - 1);
+    const float iz = ((z + 1.0f) / 2.0f) * (float)(D - 1);
+    t.x0 = (int)floorf(ix); t.y0 = (int)floorf(iy); t.z0 = (int)floorf(iz);
+    const int x1 = t.x0 + 1, y1 = t.y0 + 1, z1 = t.z0 + 1;
+    const float wx[2] = {(float)x1 - ix, ix - (float)t.x0};
+    const float wy[2] = {(float)y1 - iy, iy - (float)t.y0};
+    const float wz[2] = {(float)z1 - iz, iz - (float)t.z0};
+    const bool bx[2] = {t.x0 >= 0 && t.x0 < W, x1 >= 0 && x1 < W};
+    const bool by[2] = {t.y0 >= 0 && t.y0 < H, y1 >= 0 && y1 < H};
+    const bool bz[2] = {t.z0 >= 0 && t.z0 < D, z1 >= 0 && z1 < D};
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        t.w[k] = (wx[k & 1] * wy[(k >> 1) & 1]) * wz[k >> 2];
+        t.in[k] = bx[k & 1] && by[(k >> 1) & 1] && bz[k >> 2];
+    }
+    t.any = (bx[0] || bx[1]) && (by[0] || by[1]) && (bz[0] || bz[1]);
+    return t;
+}
+// one channel's sample: vol = that channel's [D][H][W] floats
+__device__ __forceinline__ float trilinear_sample(const TrilinearTaps &t, const float *__restrict__ vol, int H, int W)
+{
+    float acc = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const float v = t.in[k] ? vol[((int64_t)(t.z0 + (k >> 2)) * H + (t.y0 + ((k >> 1) & 1))) * W + (t.x0 + (k & 1))] : 0.0f;
+        const float prod = v * t.w[k];
+        acc = k == 0 ? prod : acc + prod;
+    }
+    return acc;
+}
+
 // affine calibration (rot | trans), row-major [3][4]; when `d` is set the 12 floats are read from
 // device memory by the kernel itself (wave-uniform scalar loads), so a caller holding the calibration
 // on the device never has to copy it to the host (no stream synchronisation in query())

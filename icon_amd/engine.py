@@ -686,22 +686,7 @@ class IconQueryEngine:
         src = (d["voxel_verts"], d["voxel_faces"])
         k = _key(*src)
         if k != (self._volb_key if batched else self._vol_key):
-            if batched and any(t.dim() != 3 or int(t.shape[0]) != B for t in src):
-                raise IconAmdError(f"voxel_verts {tuple(src[0].shape)} / voxel_faces {tuple(src[1].shape)} do not hold the {B} "
-                                   "subjects of the points")
-            vv = src[0][:, :-int(d["pad_v_num"][0]), :]          # subject 0's counts for every subject (:316-319)
-            vf = src[1][:, :-int(d["pad_f_num"][0]), :]
-            vox = netG.voxelization
-            if self._use_reference_voxelizer():
-                # the reference's own leaf (lib/net/voxelize.py:119-137 -> voxelize_cuda wheel), exactly as
-                # HGPIFuNet.query calls it (lib/net/HGPIFuNet.py:320) - still once per image, not per query()
-                with torch.no_grad():
-                    vox.update_param(batch_size=vf.shape[0], smpl_tetra=vf[0].detach().cpu().numpy())   # HGPIFuNet.py:321-323
-                    vol = vox(vv)                                                                        # :324, vol ~ [0,1]
-            else:
-                kw = dict(res=int(getattr(vox, "volume_res", 128)), sigma=float(getattr(vox, "sigma", 0.05)))
-                vol = (semantic_voxelization_batch(vv, vf[0], vox.smpl_vertex_code, **kw) if batched
-                       else semantic_voxelization(vv, vf, vox.smpl_vertex_code, **kw))
+            vol = self._semantic_volume(B)
             with torch.no_grad():
                 out = netG.ve(vol, intermediate_output=False)[-1]                  # eval: [out_lst[-1]] (VE.py:166-183)
             if batched:
@@ -709,6 +694,34 @@ class IconQueryEngine:
             else:
                 self._vol_cached, self._vol_key, self._vol_src = out, k, src
         return self._volb_cached if batched else self._vol_cached
+
+    def _semantic_volume(self, B: Optional[int] = None) -> torch.Tensor:
+        """The semantic volume ``netG.ve`` takes (lib/net/HGPIFuNet.py:314-324) from the bound network's voxel tensors: the padding
+        stripped with subject 0's counts, every subject voxelised with subject 0's tetrahedra, on the voxeliser ``voxelizer=``
+        names.  B = None: the unbatched call's [1,3,res,res,res]; B: the batched one's, the tensors must hold B subjects.  Not
+        cached here: the eval path (_pamir_volume) caches the ENCODED volume, the training path (training.TrainQuery) encodes
+        anew every step.  Reading the pad counts from device tensors waits for the device."""
+        batched = B is not None
+        netG = self.netG
+        d = netG.smpl_feat_dict
+        src = (d["voxel_verts"], d["voxel_faces"])
+        if batched and any(t.dim() != 3 or int(t.shape[0]) != B for t in src):
+            raise IconAmdError(f"voxel_verts {tuple(src[0].shape)} / voxel_faces {tuple(src[1].shape)} do not hold the {B} "
+                               "subjects of the points")
+        vv = src[0][:, :-int(d["pad_v_num"][0]), :]          # subject 0's counts for every subject (:316-319)
+        vf = src[1][:, :-int(d["pad_f_num"][0]), :]
+        vox = netG.voxelization
+        if self._use_reference_voxelizer():
+            # the reference's own leaf (lib/net/voxelize.py:119-137 -> voxelize_cuda wheel), exactly as
+            # HGPIFuNet.query calls it (lib/net/HGPIFuNet.py:320) - still once per image, not per query()
+            with torch.no_grad():
+                vox.update_param(batch_size=vf.shape[0], smpl_tetra=vf[0].detach().cpu().numpy())   # HGPIFuNet.py:321-323
+                vol = vox(vv)                                                                        # :324, vol ~ [0,1]
+        else:
+            kw = dict(res=int(getattr(vox, "volume_res", 128)), sigma=float(getattr(vox, "sigma", 0.05)))
+            vol = (semantic_voxelization_batch(vv, vf[0], vox.smpl_vertex_code, **kw) if batched
+                   else semantic_voxelization(vv, vf, vox.smpl_vertex_code, **kw))
+        return vol
 
     def _use_reference_voxelizer(self) -> bool:
         """voxelizer='reference': always netG.voxelization (needs the voxelize_cuda wheel); 'hip': always the HIP

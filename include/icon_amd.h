@@ -825,6 +825,31 @@ int icon_train_rows_backward(const float *d_grad_rows, const void *d_taps, int S
                              int H, int W, int n_select, int64_t N, float *d_grad_planes, void *d_scratch,
                              int64_t scratch_bytes, void *stream);
 
+/* ---- training, pamir prior: rows [img | vol] of every stack, and their gradient into the volumes ----------
+ * HGPIFuNet.query in training mode (lib/net/HGPIFuNet.py:348-359): point_feat = cat(index(im_feat, xy), index(vol_feat, xyz)) per
+ * pair of (feature stack, volume of that stack).  d_stacks / stack_shapes as above; d_vols: HOST array of S device pointers to
+ * float32 [B,Cv,D,H,W] volumes (VolumeEncoder's outputs, read in place, channel first), vol_shapes: HOST int32 [S][5] - all must
+ * agree, and hold the planes' B.  d_rows float32 [S,B,C+Cv,N]: channels 0 .. C-1 the bilinear tap of the planes, C .. C+Cv-1 the
+ * trilinear tap of the volume: grid_sample's statement in float32 (x -> W, y -> H, z -> D; corners z0 before z1, inside a z y0x0,
+ * y0x1, y1x0, y1x1; weight (x-term * y-term) * z-term; the eight products added left to right; zeros padding, align_corners).
+ * d_in_cube, d_taps as above (the record's fourth word carries the projected z).  Two launches, no workspace, no allocation, no
+ * synchronisation.  The gradient into the PLANES is icon_train_rows_backward with Cin = C + Cv, n_select = 1.
+ * icon_train_vol_backward: d_grad_rows [S,B,Cin,N] -> d_grad_vols [S,B,Cv,D,H,W], every element of every stack whose bit of
+ * stack_mask is set written (+0 where no tap reaches): voxel (s,b,c,z,y,x) = sum over the points of subject b that have it among
+ * their eight taps of weight * grad_rows[s,b,C+c,p]; weight and product in float32 (the forward's statement), the sum in float64
+ * in a fixed order - the eight source cells in corner order, ascending point index inside a cell, dealt to four lanes (term j of
+ * a cell to lane j mod 4, each lane running through all eight cells) and combined as (l0 + l1) + (l2 + l3) - rounded once.  No
+ * floating-point atomics: equal bytes from run to run.  d_scratch: icon_train_vol_bytes bytes, 256-byte aligned, the caller's;
+ * launches only (key kernel, one radix sort, cell-start table, gather kernel).  ICON_ERR_UNSUPPORTED: S > 8, B (D+1) (H+1) (W+1)
+ * >= 2^32 - 1; ICON_ERR_ARG: null pointers, differing shapes, another B in the volumes than in the planes, B * N >= 2^31. */
+int icon_train_pamir_forward(const float *const *d_stacks, const int32_t *stack_shapes, const float *const *d_vols,
+                             const int32_t *vol_shapes, int S, const float *d_calibs, const float *d_points, int64_t N,
+                             float *d_rows, float *d_in_cube, void *d_taps, void *stream);
+int icon_train_vol_bytes(int B, int64_t N, int S, int Cv, int D, int H, int W, int64_t *bytes);
+int icon_train_vol_backward(const float *d_grad_rows, const void *d_taps, int S, uint32_t stack_mask, int B, int Cin, int C,
+                            int Cv, int D, int H, int W, int64_t N, float *d_grad_vols, void *d_scratch,
+                            int64_t scratch_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

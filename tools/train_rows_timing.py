@@ -14,6 +14,11 @@ copies / memsets and synchronising API calls per call are counted by torch.profi
 caching allocator's high-water mark over one call.
 
     python tools/train_rows_timing.py [--reps 30] [--out profiles/train_rows_timing.txt]
+
+``--prior pamir`` (written to profiles/train_rows_pamir_timing.txt): the rows [img | vol] and their gradients into
+the planes AND the volumes at configs/train/pamir.yaml's size - B = 8 x N = 8000, S = 2, planes [8,6,128,128], volumes
+[8,7,32,32,32] - native (icon_train_pamir_forward, icon_train_rows_backward, icon_train_vol_backward) against the same rule from
+torch operators (two F.grid_sample per stack, autograd with float32 atomics), timed and counted the same way.
 """
 import argparse
 import importlib.util
@@ -24,11 +29,96 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 
 
+def main_pamir(args):
+    import numpy as np
+    import torch
+    import torch.nn.functional as F
+    import batch_pamir as bp
+    from icon_amd import _lib, training
+    from icon_amd.engine import IconQueryEngine
+    from torch.profiler import ProfilerActivity, profile
+
+    _lib.require_device()
+    dev = torch.device("cuda:0")
+    T = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)
+    B, N, S, C, size, Cv, D = 8, 8000, 2, 6, 128, 7, 32
+    Sj = bp.subjects(B)
+    eng = IconQueryEngine(prior_type="pamir")
+    pts = T(bp.candidate_points(Sj, N).transpose(0, 2, 1))                     # [B,3,N]
+    calibs = T(Sj["calibs"])
+    torch.manual_seed(0)
+    planes = [torch.randn(B, C, size, size, device=dev).requires_grad_(True) for _ in range(S)]
+    vols = [torch.randn(B, Cv, D, D, D, device=dev).requires_grad_(True) for _ in range(S)]
+    g_rows = [torch.randn(B, C + Cv, N, device=dev) for _ in range(S)]
+
+    def native_rows():
+        return training.point_features_device(eng, planes, pts, calibs, vol_feats=vols)[0]
+
+    def composed_rows():
+        uv = torch.baddbmm(calibs[:, :3, 3:4], calibs[:, :3, :3], pts).transpose(1, 2)
+        return [torch.cat([F.grid_sample(f, uv[:, :, None, :2], align_corners=True)[..., 0],
+                           F.grid_sample(v, uv[:, :, None, None, :], align_corners=True)[:, :, :, 0, 0]], 1) for f, v in zip(planes, vols)]
+
+    def fwd_bwd(rows_fn):
+        return torch.autograd.grad(rows_fn(), planes + vols, grad_outputs=g_rows)
+
+    lines = []
+
+    def say(s=""):
+        print(s, flush=True)
+        lines.append(s)
+
+    say(f"pamir training rows [img | vol] and their gradients into planes and volumes, {torch.cuda.get_device_name(0)}; records of ONE run, not promises")
+    say(f"B = {B} subjects x N = {N} points, S = {S} stacks: planes [{B},{C},{size},{size}], volumes [{B},{Cv},{D},{D},{D}]")
+    rn, rc = native_rows(), composed_rows()
+    gn, gc = fwd_bwd(native_rows), fwd_bwd(composed_rows)
+    say(f"agreement: max |rows native - composed| = {max(float((a - b).detach().abs().max()) for a, b in zip(rn, rc)):.3e}, "
+        f"max |grad native - composed| = {max(float((a - b).abs().max()) for a, b in zip(gn, gc)):.3e} (largest gradient {max(float(a.abs().max()) for a in gn):.3e})")
+    say(f"native gradients equal from call to call, bit for bit: {all(torch.equal(a, b) for a, b in zip(gn, fwd_bwd(native_rows)))}; "
+        f"composed: {all(torch.equal(a, b) for a, b in zip(gc, fwd_bwd(composed_rows)))}")
+    say()
+    say("rows forward + backward (planes and volumes)")
+    ways = (("native", lambda: fwd_bwd(native_rows)), ("composed", lambda: fwd_bwd(composed_rows)))
+    for _ in range(3):
+        for _, f in ways:
+            f()
+    times = {name: [] for name, _ in ways}
+    for _ in range(args.reps):
+        for name, f in ways:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(); f(); e1.record(); e1.synchronize()
+            times[name].append(e0.elapsed_time(e1))
+    med = {}
+    for name, ts in times.items():
+        ts = sorted(ts)
+        med[name] = ts[len(ts) // 2]
+        say(f"  {name:9s} {ts[len(ts) // 2]:8.3f} ms median (min {ts[0]:.3f}, max {ts[-1]:.3f}; {len(ts)} calls, HIP events, alternated)")
+    say(f"  the bar (native pair not slower than the composed pair in this process): {'met' if med['native'] <= med['composed'] else 'MISSED'}")
+    for name, f in ways:
+        torch.cuda.synchronize()
+        with profile(activities=[ProfilerActivity.CUDA, ProfilerActivity.CPU]) as prof:
+            f()
+            torch.cuda.synchronize()
+        ev = [e for e in prof.events() if e.device_type == torch.autograd.DeviceType.CUDA]
+        kernels = [e for e in ev if "memcpy" not in e.name.lower() and "memset" not in e.name.lower()]
+        say(f"  {name:9s} {len(kernels)} kernel launches, {len(ev) - len(kernels)} copies / memsets")
+        if name == "native":
+            for e in sorted(kernels, key=lambda e: -e.device_time)[:6]:
+                say(f"            {e.device_time:8.1f} us  {e.name[:90]}")
+    out = args.out or os.path.join(ROOT, "profiles", "train_rows_pamir_timing.txt")
+    with open(out, "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=30)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "train_rows_timing.txt"))
+    ap.add_argument("--prior", default="icon", choices=("icon", "pamir"))
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.prior == "pamir":
+        return main_pamir(args)
+    args.out = args.out or os.path.join(ROOT, "profiles", "train_rows_timing.txt")
     import numpy as np
     import torch
     import torch.nn.functional as F
