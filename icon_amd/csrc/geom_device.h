@@ -251,9 +251,11 @@ typedef __attribute__((address_space(4))) const i2 ci2;
 // d^2 >= +0, so its bit pattern orders like the value; equal d^2 -> lower face id wins; NaN (bits above +inf) never wins; a
 // padding copy has the same key as its original.
 struct PairKeys { unsigned long long k0, k1; };
-__device__ __forceinline__ PairKeys leaf_pair_keys(const MeshDev &m, int leaf, int pr, f3 p)
+// a record at a 32-bit byte offset from its table's base: what a scalar load addresses with the base pair and ONE offset register
+__device__ __forceinline__ cfloat *rec_at(const void *base, uint32_t byte_off) { return as_const(reinterpret_cast<const char *>(base) + byte_off); }
+// q: the pair's 24 two-float fields (LeafRec::pair[pr])
+__device__ __forceinline__ PairKeys leaf_pair_keys_at(cf2 *q, f3 p)
 {
-    cf2 *q = reinterpret_cast<cf2 *>(as_const(&m.leaves[leaf].pair[pr]));
     const f2 d2 = tri_dist2_pair(p, q);
     const f2 fc = q[22];
     PairKeys k;
@@ -261,18 +263,28 @@ __device__ __forceinline__ PairKeys leaf_pair_keys(const MeshDev &m, int leaf, i
     k.k1 = ((unsigned long long)(unsigned)__float_as_int(d2.y) << 32) | (unsigned)__float_as_int(fc.y);
     return k;
 }
+__device__ __forceinline__ PairKeys leaf_pair_keys(const MeshDev &m, int leaf, int pr, f3 p)
+{
+    return leaf_pair_keys_at(reinterpret_cast<cf2 *>(as_const(&m.leaves[leaf].pair[pr])), p);
+}
 // AABB inner node: both children's box distances and the node's child references, integers from the record's own scalar load
 // (one 64-byte load): lo.x lo.y lo.z hi.x hi.y hi.z (children 0,1), ids, walk ids.  `walk`: the references that carry
 // kNodeBoxFlag (wave-uniform; nearest_packet with node boxes only).
 struct AabbVisit { f2 dd; i2 ids; };
-__device__ __forceinline__ AabbVisit aabb_visit(const MeshDev &m, int node, f3 p, bool walk = false)
+// WALK: which references are taken is known when the kernel is compiled (1: flagged, 0: plain) - no select per visit; -1: `walk` decides.
+template <int WALK = -1>
+__device__ __forceinline__ AabbVisit aabb_visit_at(cf2 *q /* the BvhNode */, f3 p, bool walk = false)
 {
     AabbVisit v;
-    v.dd = box_dist2_pair(reinterpret_cast<cf2 *>(as_const(m.nodes + node)), p);
-    ci2 *qi = reinterpret_cast<ci2 *>(as_const(m.nodes + node));
-    const i2 plain = qi[6], flagged = qi[7];
-    v.ids = walk ? flagged : plain;
+    v.dd = box_dist2_pair(q, p);
+    ci2 *qi = reinterpret_cast<ci2 *>(q);
+    if (WALK >= 0) v.ids = qi[6 + WALK];
+    else { const i2 plain = qi[6], flagged = qi[7]; v.ids = walk ? flagged : plain; }
     return v;
+}
+__device__ __forceinline__ AabbVisit aabb_visit(const MeshDev &m, int node, f3 p)
+{
+    return aabb_visit_at<0>(reinterpret_cast<cf2 *>(as_const(m.nodes + node)), p);
 }
 
 // BVH2 PACKET traversal: the 64 lanes of a wavefront descend the tree TOGETHER.  Control flow, the
@@ -290,9 +302,12 @@ __device__ __forceinline__ AabbVisit aabb_visit(const MeshDev &m, int node, f3 p
 // CLAMP ("box_clamp"): the oriented boxes - parents and leaf pairs - are evaluated in half units with the excess limited to
 // [0, 1] by the subtraction's clamp bit (mesh_rules.h: pair_box_bound_half) and voted against thr / 4: the same decisions, or
 // fewer culls where an excess passes 2.0 - bit-identical results either way.
-// The loop is written for its listing (profiles/walk_diet_isa.txt): child references are integers from the scalar load in both
-// kinds of inner visit, the key and the threshold are updated in place, both pair ballots become bits on the scalar unit, and
-// there is ONE pop, at the loop's tail.
+// BOXES: the caller has checked that the mesh holds pair boxes AND node boxes (k_nearest<lattice> under CLAMP): which child
+// references an AABB parent hands on and whether a leaf has boxes is then settled when the kernel is compiled, not asked per visit.
+// The loop is written for its listing, vector side (profiles/walk_diet_isa.txt) and scalar side (profiles/walk_scalar_isa.txt,
+// tools/walk_listing.py): child references are integers from the scalar load in both kinds of inner visit, the key and the threshold
+// are updated in place, ballots become bits on the scalar unit, every record is addressed by one shift of its reference, the descent
+// is two plain loops and a leaf visit, and there is ONE pop, at the loop's tail.
 // STATS (k_walk_stats): the visits are counted per packet into a WalkStats.
 struct WalkStats { int nodes, tris, offered, tested, leaves, obox; };
 // root: the BVH root - mesh_root(m), or the copy the caller already holds in a register.  center_lane: the lane whose box
@@ -304,7 +319,7 @@ struct WalkArgs {
     WalkStats *stats = nullptr;
     unsigned long long *runner_up = nullptr;
 };
-template <bool STATS = false, bool TIES = false, bool CLAMP = false>
+template <bool STATS = false, bool TIES = false, bool CLAMP = false, bool BOXES = false>
 __device__ __forceinline__ Nearest nearest_packet(const MeshDev &m, f3 p, bool live, int *wstack /* LDS, kStackDepth ints of this wave */,
                                                   const WalkArgs &a)
 {
@@ -325,20 +340,63 @@ __device__ __forceinline__ Nearest nearest_packet(const MeshDev &m, f3 p, bool l
     // worked out here, from its split point.  All of it wave-uniform.
     const PairBox *nbox = m.nbox_off ? reinterpret_cast<const PairBox *>(m.leaves) + m.nbox_off : nullptr;
     if (nbox) cur = node_ref_flagged(cur, 0, m.n_tris);
+    // Every record is read at a 32-bit BYTE offset from its table's base (rec_at): the scalar load takes the base pair and one
+    // offset register, and the offset is one shift of the reference - no 64-bit add chain, no multiply (profiles/walk_scalar_isa.txt).
+    const void *const leaves = m.leaves, *const nodes = m.nodes;
+    const bool walk = BOXES || nbox != nullptr;                  // the references an AABB parent hands on: flagged (word 7) or plain (word 6)
+    // The control flow is stated the way the compiler's structuriser leaves alone (it turns every if / ELSE, `continue` and inner
+    // `break` of a loop into 64-bit flag registers and extra branches, uniform or not): a descent runs through AABB parents, then
+    // oriented parents, then at most one leaf - a child of an oriented parent is never an AABB parent - so it is two plain
+    // `while` loops and an `if`, each with one test at its end, and a visit that enters no child leaves kWalkNone in `cur`, which
+    // fails all three tests and falls through to the pop.  Same visits in the same order as the one-switch-per-visit loop.
+    constexpr int kWalkNone = (int)0x80000000;                   // no reference (leaf ids are < 2^23: a leaf code ~(id << 2 | n) has bits 25 .. 31 set)
+    // The child choice on the two votes themselves: the child to enter if one is wanted, the push if both are, kWalkNone if none.
+    auto choose = [&](unsigned long long b0, unsigned long long b1, i2 ids, f2 dd) {
+        // (each vote becomes a bit by a scalar select of constants, as at the leaf, and stays one: left to itself the compiler turns
+        //  the bits back into two booleans joined by &&, which it keeps as two 64-bit masks - four more scalar instructions a visit)
+        int v0 = b0 != 0 ? 2 : 0, v1 = b1 != 0 ? 4 : 0;
+        asm("" : "+s"(v0), "+s"(v1));
+        const int votes = v0 | v1;
+        int next = b0 != 0 ? ids.x : ids.y;
+        if (votes == 6) {
+            // order by the block's centre lane; non-negative floats order like their bit patterns
+            const int e0 = __builtin_amdgcn_readlane(__float_as_int(dd.x), a.center_lane);
+            const int e1 = __builtin_amdgcn_readlane(__float_as_int(dd.y), a.center_lane);
+            const bool first0 = e0 <= e1;
+            wstack[sp++] = first0 ? ids.y : ids.x;
+            next = first0 ? ids.x : ids.y;
+        }
+        return votes ? next : kWalkNone;
+    };
     while (true) {
-        bool pop;                                                // wave-uniform: this visit entered no child
-        if (cur < 0) {
-            const int code = ~cur;
-            const int leaf = code >> 2, cnt = (code & 3) + 1;
-            if (STATS) { a.stats->tris += cnt; ++a.stats->leaves; }
-            const int npairs = __builtin_amdgcn_readfirstlane((cnt + 1) >> 1);      // 1 or 2, wave-uniform (scalar loop counter)
+        // both children's lower bounds in one packed evaluation: box distances of an AABB parent, the oriented-box bound of an
+        // oriented parent's record - either way <= the real d^2 of every triangle below the child, which is all the vote relies on;
+        // the child references are integers from the record's own scalar load, both ways
+        while ((uint32_t)cur < (uint32_t)kNodeBoxFlag) {         // AABB parents
+            if (STATS) ++a.stats->nodes;
+            const AabbVisit v = aabb_visit_at<BOXES ? 1 : -1>(reinterpret_cast<cf2 *>(rec_at(nodes, (uint32_t)cur << 6)), p, walk);
+            cur = choose(__builtin_amdgcn_ballot_w64(v.dd.x <= thr), __builtin_amdgcn_ballot_w64(v.dd.y <= thr), v.ids, v.dd);
+        }
+        while (cur >= kNodeBoxFlag) {                            // oriented parents (in half units under CLAMP: one visit, one unit)
+            if (STATS) { ++a.stats->nodes; ++a.stats->obox; }
+            cf2 *q = reinterpret_cast<cf2 *>(rec_at(nbox, (uint32_t)cur << 7));          // (the shift drops the flag, bit 30)
+            const f2 dd = CLAMP ? pair_box_bound_half(q, ph.x, ph.y, ph.z) : pair_box_bound(q, p.x, p.y, p.z);
+            const float lim = CLAMP ? thq : thr;
+            cur = choose(__builtin_amdgcn_ballot_w64(dd.x <= lim), __builtin_amdgcn_ballot_w64(dd.y <= lim), reinterpret_cast<ci2 *>(q)[15], dd);
+        }
+        if (cur != kWalkNone) {
+            // a leaf code: ~cur = leaf id << 2 | (triangles - 1).  Its pair-box record lies at leaf id * 128, its triangles at three times
+            // that; one pair (1 or 2 triangles) or two (3 or 4): bit 1 of the count field, inverted in cur.
+            const uint32_t pb_off = ((uint32_t)~cur << 5) & ~127u, leaf_off = pb_off * 3u;
+            const int npairs = (cur & 2) ? 1 : 2;
+            if (STATS) { a.stats->tris += (~cur & 3) + 1; ++a.stats->leaves; }
             // Most pairs of a visited leaf are out of every lane's reach (the leaf's AABB admits a slanted patch from far away:
             // DESIGN.md 4.1): both pairs' oriented boxes in one packed evaluation, then the distance test only for the pairs
             // SOME lane still needs.  box bound <= real d^2 of the pair's triangles, so a pair skipped here could neither beat
             // nor tie any lane's key - the same argument as for a child's box.  Parked lanes (thr = -inf) never vote.
-            int need = (2 << npairs) - 2;                        // bit pr + 1: pair pr is tested; scalar, like the loop over its bits
-            if (pbox) {
-                cf2 *q = reinterpret_cast<cf2 *>(as_const(pbox + leaf));
+            int need = (cur & 2) ? 2 : 6;                        // bit pr + 1: pair pr is tested; scalar, like the loop over its bits
+            if (BOXES || pbox) {
+                cf2 *q = reinterpret_cast<cf2 *>(rec_at(pbox, pb_off));
                 const f2 bb = CLAMP ? pair_box_bound_half(q, ph.x, ph.y, ph.z) : pair_box_bound(q, p.x, p.y, p.z);
                 const float lim = CLAMP ? thq : thr;
                 // (ballots are wave-uniform; each becomes a bit by a scalar select of constants - which is why the bits start at 1:
@@ -349,8 +407,7 @@ __device__ __forceinline__ Nearest nearest_packet(const MeshDev &m, f3 p, bool l
             if (STATS) { a.stats->offered += npairs; a.stats->tested += __builtin_popcount((unsigned)need); }
             if (need) {                                          // (nothing tested: key and bound are what they were)
                 do {
-                    const int pr = __builtin_ctz((unsigned)need) - 1;
-                    const PairKeys k = leaf_pair_keys(m, leaf, pr, p);
+                    const PairKeys k = leaf_pair_keys_at(reinterpret_cast<cf2 *>(rec_at(leaves, leaf_off + ((need & 2) ? 0u : 192u))), p);
                     const unsigned long long k0 = k.k0, k1 = k.k1;
                     // (the winner's slot is looked up from its face id at the end: nothing else to carry per test; a parked
                     //  lane computes on a clamped copy of a real point and may update its key freely - it never votes
@@ -367,45 +424,10 @@ __device__ __forceinline__ Nearest nearest_packet(const MeshDev &m, f3 p, bool l
                 thr = live ? prune_threshold(__int_as_float((int)(key >> 32))) : thr;   // one fma + select: cheaper than finding out whether the key moved
                 if (CLAMP) thq = thr * 0.25f;
             }
-            pop = true;
-        } else {
-            if (STATS) ++a.stats->nodes;
-            // both children's lower bounds in one packed evaluation: box distances of an AABB parent, the oriented-box bound of an
-            // oriented parent's record - either way <= the real d^2 of every triangle below the child, which is all the vote relies on
-            i2 ids;                                              // the child references: integers from the record's own scalar load, both ways
-            unsigned long long b0, b1;                           // the votes
-            f2 dd;                                               // (in half units at an oriented parent under CLAMP: one visit, one unit)
-            if (cur & kNodeBoxFlag) {
-                if (STATS) ++a.stats->obox;
-                const PairBox *rec = nbox + (cur & ~kNodeBoxFlag);
-                cf2 *q = reinterpret_cast<cf2 *>(as_const(rec));
-                dd = CLAMP ? pair_box_bound_half(q, ph.x, ph.y, ph.z) : pair_box_bound(q, p.x, p.y, p.z);
-                const float lim = CLAMP ? thq : thr;
-                ids = reinterpret_cast<ci2 *>(as_const(rec))[15];
-                b0 = __builtin_amdgcn_ballot_w64(dd.x <= lim); b1 = __builtin_amdgcn_ballot_w64(dd.y <= lim);
-            } else {
-                const AabbVisit v = aabb_visit(m, cur, p, nbox != nullptr);
-                dd = v.dd; ids = v.ids;
-                b0 = __builtin_amdgcn_ballot_w64(dd.x <= thr); b1 = __builtin_amdgcn_ballot_w64(dd.y <= thr);
-            }
-            const int c0 = ids.x, c1 = ids.y;
-            const bool v0 = b0 != 0, v1 = b1 != 0;
-            pop = false;
-            if (v0 && v1) {
-                // order by the block's centre lane; non-negative floats order like their bit patterns
-                const int e0 = __builtin_amdgcn_readlane(__float_as_int(dd.x), a.center_lane);
-                const int e1 = __builtin_amdgcn_readlane(__float_as_int(dd.y), a.center_lane);
-                const bool first0 = e0 <= e1;
-                wstack[sp++] = first0 ? c1 : c0;
-                cur = first0 ? c0 : c1;
-            } else if (v0) cur = c0;
-            else if (v1) cur = c1;
-            else pop = true;
         }
-        if (pop) {
-            if (sp == 0) break;
-            cur = __builtin_amdgcn_readfirstlane(wstack[--sp]);
-        }
+        // the one pop: a leaf, or an inner visit that entered no child
+        if (sp == 0) break;
+        cur = __builtin_amdgcn_readfirstlane(wstack[--sp]);
     }
     nr.d2 = __int_as_float((int)(key >> 32)); nr.face = (int)(key & 0xffffffffu);
     nr.slot = (nr.face != 0x7fffffff) ? m.face2slot[nr.face] : 0;

@@ -75,7 +75,10 @@ __global__ __launch_bounds__(kCoopWaves * 64) void k_sdf_query_coop(MeshDev m, c
 // `tie_ulps` float32 ulps of the minimum d^2 (nearest_packet_alt) - for measuring how much of the output hangs on
 // the unpinned tie behaviour of the kaolin leaf (lib/dataset/mesh_util.py:374-390).
 // CLAMP: the half-unit, clamped evaluation of the oriented boxes (nearest_packet; "box_clamp"), lattice launches only.
-// <true, false, false> is the same lattice launch on pair_box_bound, for meshes created with the option off (A/B, tests).
+// The host launches it only for a mesh that holds pair boxes AND node boxes (the default), so what the walk would otherwise ask the
+// mesh record at every visit is settled when the kernel is compiled (nearest_packet's BOXES).
+// <true, false, false> is the same lattice launch on pair_box_bound and on whatever tables the mesh has, for meshes created with
+// one of the three options off (A/B, tests): bit-identical results.
 template <bool LATTICE, bool ALT, bool CLAMP>
 __global__ __launch_bounds__(kBlock) void k_nearest(MeshDev m, Calib cal, LatticeMap L, const float *__restrict__ pts, int64_t N,
                                                     NearRef near, const int32_t *__restrict__ perm,
@@ -107,7 +110,7 @@ __global__ __launch_bounds__(kBlock) void k_nearest(MeshDev m, Calib cal, Lattic
         p = project(resolve_calib(cal), mk3(pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]));
         root = mesh_root(m);
     }
-    Nearest nr = nearest_packet<false, false, CLAMP>(m, p, live, lds + (threadIdx.x >> 6) * kStackDepth, {root, LATTICE ? packet_center_lane(L) : 21});
+    Nearest nr = nearest_packet<false, false, CLAMP, CLAMP>(m, p, live, lds + (threadIdx.x >> 6) * kStackDepth, {root, LATTICE ? packet_center_lane(L) : 21});
     if (ALT) nr = nearest_packet_alt(m, p, live, lds + (threadIdx.x >> 6) * kStackDepth, (uint32_t)__float_as_int(nr.d2), (uint32_t)tie_ulps);
     // (staging the 16 x 4 x 4 block through LDS so that 16 threads store one 64-byte run removes the partial-line
     //  writes but the block-wide barrier costs 0.14 ms; not kept)
@@ -380,7 +383,7 @@ int launch_nearest(const icon_mesh_t *mesh, const Calib &cal, const LatticeMap &
         if (nw == 16) hipLaunchKernelGGL(k_nearest_shared<16>, dim3((unsigned)nb * 4), dim3(16 * 64), 0, st, mesh->dev, L, near, sdf_clip, dbg);
         else if (nw == 8) hipLaunchKernelGGL(k_nearest_shared<8>, dim3((unsigned)nb * 4), dim3(8 * 64), 0, st, mesh->dev, L, near, sdf_clip, dbg);
         else if (alt) hipLaunchKernelGGL((k_nearest<LATTICE, true, false>), dim3((unsigned)nb), dim3(kBlock), 0, st, mesh->dev, cal, L, d_points, N, near, perm, sdf_clip, work->tie_ulps, lf);
-        else if (LATTICE && !mesh->dev.box_clamp) hipLaunchKernelGGL((k_nearest<true, false, false>), dim3((unsigned)nb), dim3(kBlock), 0, st, mesh->dev, cal, L, d_points, N, near, perm, sdf_clip, 0, lf);
+        else if (LATTICE && !(mesh->dev.box_clamp && mesh->dev.pbox_off && mesh->dev.nbox_off)) hipLaunchKernelGGL((k_nearest<true, false, false>), dim3((unsigned)nb), dim3(kBlock), 0, st, mesh->dev, cal, L, d_points, N, near, perm, sdf_clip, 0, lf);
         else hipLaunchKernelGGL((k_nearest<LATTICE, false, LATTICE>), dim3((unsigned)nb), dim3(kBlock), 0, st, mesh->dev, cal, L, d_points, N, near, perm, sdf_clip, 0, lf);
         if (work->prof) { (void)hipEventRecord(work->ev[5], st); work->ev_search = true; }
     }
