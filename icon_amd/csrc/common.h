@@ -474,7 +474,7 @@ extern int g_rn_lanes;                // render_normal.hip: lanes per face of th
 extern int g_tt_chunk;                // turntable.hip: views per chunk of the turntable call ("tt_chunk"; 0 = default)
 extern int g_ev_lanes;                // evaluator.hip: lanes per face of the evaluator's rasteriser ("ev_lanes"; 0 = default)
 // the process-wide test / A-B switches (work.hip: the table with their keys, environment variables and defaults)
-enum Opt { kOptPairBox, kOptNodeBox, kOptBoxClamp, kOptLatticeFast, kOptUnfused, kOptShellSkip, kOptShareWaves, kOptShareRing, kOptShareLose,
+enum Opt { kOptPairBox, kOptNodeBox, kOptBoxClamp, kOptLatticeFast, kOptUnfused, kOptShellSkip, kOptMcClassify1, kOptShareWaves, kOptShareRing, kOptShareLose,
            kOptShareSpinLog2, kOptCount };
 int option(Opt o);
 }  // namespace icon

@@ -376,8 +376,7 @@ extern "C" int icon_mc_count_range(const float *d_occ, int res, float level, int
         ICON_HIP(hipMalloc((void **)&s->first_tri, (size_t)npts * sizeof(int32_t)));
         s->cap = npts;
     }
-    static const bool one_cell = getenv("ICON_AMD_MC_CLASSIFY1") != nullptr;         // A/B: the one-cell-per-thread form
-    if ((res - 1) % 4 == 0 && !one_cell)
+    if ((res - 1) % 4 == 0 && !option(kOptMcClassify1))                             // "mc_classify1": the one-cell-per-thread form (A/B, tests)
         hipLaunchKernelGGL(k_mc_classify4, dim3((unsigned)nblk), dim3(kMcBlock / 4), 0, st, d_occ, res, level, npts, s->flags, s->ntri, s->block_tot, zc0, zc1, halo);
     else
         hipLaunchKernelGGL(k_mc_classify, dim3((unsigned)nblk), dim3(kMcBlock), 0, st, d_occ, res, level, npts, s->flags, s->ntri, s->block_tot, zc0, zc1, halo);

@@ -17,7 +17,8 @@ static constexpr Option kOptions[kOptCount] = {
     {kOptLatticeFast, "lattice_fast", "ICON_AMD_LATTICE_FAST", 1},  // 0: every packet derives its own set-up (A/B runs)
     {kOptUnfused, nullptr, "ICON_AMD_UNFUSED", 0},                  // icon_debug_set_unfused: 1 forces the materialising path
     {kOptShellSkip, nullptr, "ICON_AMD_SHELL_SKIP", 1},             // icon_debug_set_shell_skip: 0 evaluates and masks the in_cube shell
-    {kOptShareWaves, "share_waves", "ICON_AMD_SHARE", -1,           // wavefronts per shared walk (4: the adaptive schedule's searches only)
+    {kOptMcClassify1, "mc_classify1", "ICON_AMD_MC_CLASSIFY1", 0},  // 1: marching cubes classifies one cell per thread at every size (A/B)
+    {kOptShareWaves, "share_waves", "ICON_AMD_SHARE", -1,          // wavefronts per shared walk (4: the adaptive schedule's searches only)
      [](int v) { return v == -1 || v == 1 || v == 4 || v == 8 || v == 16; }, "-1 (by launch size), 1, 4, 8 or 16"},
     {kOptShareRing, "share_ring", nullptr, 0,                       // forced ring size of the shared walks (0 = 64)
      [](int v) { return v == 0 || (v >= 2 && v <= 64 && (v & (v - 1)) == 0); }, "0 or a power of two in 2..64"},

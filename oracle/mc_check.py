@@ -190,11 +190,12 @@ def largest_component_by_faces(verts, faces):
             if ra != rb:
                 parent[max(ra, rb)] = min(ra, rb)
     lab = np.array([find(i) for i in range(len(f))])
-    best, best_n = -1, -1
-    for L in np.unique(lab):                     # ascending: the first of several largest is the one with the lowest face
-        n = len(np.unique(f[lab == L]))
-        if n > best_n:
-            best, best_n = L, n
+    # distinct vertices per component: the distinct (component, vertex) pairs, counted per component (a loop over the components
+    # with a mask each is quadratic on a noise surface, which has thousands of them)
+    labs, linv = np.unique(lab, return_inverse=True)
+    pairs = np.unique(np.repeat(linv.reshape(-1), 3) * (len(v) + 1) + f.reshape(-1))
+    n_verts = np.bincount(pairs // (len(v) + 1), minlength=len(labs))
+    best = labs[int(np.argmax(n_verts))] if len(labs) else -1      # ascending, first maximum: of several largest the one with the lowest face
     keep_f = lab == best
     keep_v = np.zeros(len(v), bool)
     keep_v[f[keep_f].reshape(-1)] = True
