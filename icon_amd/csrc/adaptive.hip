@@ -17,7 +17,7 @@
 // nearest-triangle search runs as 4x4x4 PACKETS over the blocks of the level lattice that hold at least one candidate
 // (k_ad_nearest, the traversal of k_nearest<lattice>) instead of one wavefront per scattered point; the per-point phases
 // (inside test, sign list, feature rows + MLP) are the point-mode kernels of the ordinary query with the point count left on
-// the device (icon_work::q_n_dev) and the search results found through the lattice index (NearRef::map).
+// the device (QueryCall::n_dev) and the search results found through the lattice index (QueryCall::map).
 // Masks live in [x][y][z] order (z fastest): the compaction's linear order IS the reference's point order.
 #pragma clang fp contract(off)
 
@@ -446,6 +446,11 @@ static int adaptive_eval_impl(const icon_mesh_t *mesh, const icon_feat_t *feat, 
     static_assert(15 * 1290 + 32 <= (256 << kAdSupShift), "k_ad_mask: a tile's rows of one x must span at most two second-level counters");
     hipStream_t st = (hipStream_t)stream;
     int rc;
+    // what every queried level has in common: a point-mode call in the standard box
+    QueryCall base = query_call("icon_adaptive_eval", Src::Points, feat, prior_type, sdf_clip, cmap_mode, search);
+    base.mesh = mesh;
+    memcpy(base.cal.m, kIdentCalib, sizeof(kIdentCalib));
+    if ((rc = describe_call(base))) return rc;
 
     // ---- level buffers (allocated once per schedule) ----------------------------------------------------------------
     icon_adaptive *a = work->ad;
@@ -493,22 +498,19 @@ static int adaptive_eval_impl(const icon_mesh_t *mesh, const icon_feat_t *feat, 
     a->other_clean = false;
     int *const other_set = a->counters_base + 16 * (a->cur_set ^ 1);
     bool mirrored = false;
-    // whatever way this function is left, the workspace must not keep pointing at a level's compaction buffers: a later point
-    // query on it would read them as ITS map
-    struct QMapGuard { icon_work *w; ~QMapGuard() { w->q_map = nullptr; w->q_n_dev = nullptr; w->defer_range_flag = nullptr; } } q_guard{work};
+    // the schedule's sticky range word, armed for this function only: however it is left, no later call on the workspace may raise it
+    struct Disarm { icon_work *w; ~Disarm() { w->defer_range_flag = nullptr; } } disarm{work};
     work->defer_range_flag = defer_rescue ? a->counters + 10 : nullptr;
 
     // ---- level 0: the coarsest lattice, dense, ONE call ---------------------------------------------------------------
     const int r0 = resolutions[0];
     float *occ0 = a->occ[0];
-    work->q_map = nullptr; work->q_n_dev = nullptr;
     if ((rc = icon_grid_eval_slab(mesh, feat, mlp, prior_type, sdf_clip, cmap_mode, r0, 0, r0, occ0, search, precision, work, stream))) return rc;
     if (n_levels == 1) {                                        // no upsample launch to carry the any-positive test
         const int64_t n0 = (int64_t)r0 * r0 * r0;
         hipLaunchKernelGGL(k_ad_pbits, dim3((unsigned)((n0 + 255) / 256)), dim3(256), 0, st, occ0, r0, balance, (uint8_t *)nullptr, a->counters + 9);
     }
 
-    const float ident[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
     for (int l = 1; l < n_levels; ++l) {
         const int r = resolutions[l], rp = resolutions[l - 1];
         const int64_t n = (int64_t)r * r * r;
@@ -552,19 +554,12 @@ static int adaptive_eval_impl(const icon_mesh_t *mesh, const icon_feat_t *feat, 
         ICON_HIP(hipGetLastError());
         debug_sync("adaptive: upsample + boundary + dilate + compact", st);
         // ---- the level's query: ONE call over the compacted points (count on the device) ---------------------------------
-        if ((rc = ensure_work_points(work, std::max<int64_t>(n, 1)))) return rc;      // near arrays by lattice index, codes / signs by call index
-        work->q_map = a->map; work->q_n_dev = a->counters + l;
-        Calib cal;
-        memcpy(cal.m, ident, sizeof(ident)); cal.d = nullptr;
-        const bool icon = icon_prior;
-        const bool needs_list = icon && cmap_mode == ICON_CMAP_REFERENCE && (feat->dev.smpl_mask & kSmplCmap);
-        if (icon) {
-            if (mesh->F > kNearLoSlots && work->cap_points_hi < work->cap_points) {
-                (void)hipFree(work->d_near_hi); work->d_near_hi = nullptr; work->cap_points_hi = 0;
-                ICON_HIP(hipMalloc((void **)&work->d_near_hi, (size_t)work->cap_points));
-                work->cap_points_hi = work->cap_points;
-            }
-            NearRef raw = work_near(work, mesh);
+        QueryCall lv = base;
+        lv.points = a->pts; lv.N = n;                           // N bounds the call (near arrays by lattice index, codes / signs by call index) ...
+        lv.map = a->map; lv.n_dev = a->counters + l;            // ... its size and its points' lattice indices are the compaction's
+        if ((rc = begin_call(work, lv))) return rc;
+        if (icon_prior) {
+            NearRef raw = work_near(work, lv);
             raw.map = nullptr;                                   // the search writes by lattice index
             int n_cu = 0;
             if ((rc = device_cu_count(&n_cu))) return rc;
@@ -589,14 +584,9 @@ static int adaptive_eval_impl(const icon_mesh_t *mesh, const icon_feat_t *feat, 
 #undef ICON_AD_NEAREST
             ICON_HIP(hipGetLastError());
             debug_sync("adaptive: k_ad_nearest", st);
-            if ((rc = launch_sign(mesh, cal, r, 0, a->pts, n, sdf_clip, work, false, st))) return rc;
-            if (needs_list && (rc = outlier_list(work, n, a->counters + l, work->d_signs, true, st))) return rc;
+            if ((rc = sign_and_list(lv, nullptr, work, st))) return rc;
         }
-        const SignSrc fs = self_signs(work, needs_list);
-        LatticeMap L{};
-        rc = launch_fused_f16x3(mesh, feat, mlp, prior_type, cal, L, 0, 0, a->pts, n, sdf_clip, cmap_mode == ICON_CMAP_LOCAL ? 1 : 0, work, fs,
-                                a->occ[l], false, st);
-        work->q_map = nullptr; work->q_n_dev = nullptr;
+        rc = launch_fused_f16x3(lv, mlp, work, 0, 0, self_signs(work, lv.needs_patch), a->occ[l], st);
         if (rc) return rc;
         debug_sync("adaptive: sign + list + fused", st);
         // (the bookkeeping for the next level - D, P - rides on the next level's upsample launch: k_ad_up)

@@ -64,44 +64,34 @@ __global__ __launch_bounds__(kBlock) void k_nearest_batch(BatchDev bd, const flo
     if (live) store_near(near, i, nr, sdf_clip);
 }
 
-// the geometry half of a batched icon call over the B*N points: nearest triangle (cooperative or Morton packets), the sign pass
-// (code bytes + block counts) and, for the reference cmap rule, the batch-global outlier sign list.  Shared by
-// icon_query_points_batch and icon_train_rows_forward (train_rows.hip): the search runs once per call, whoever consumes it.
-int batch_geometry(const icon_mesh_batch *mb, const BatchDev &bd, const float *d_points, int64_t N, int B, float sdf_clip,
-                   bool needs_patch, icon_work *work, hipStream_t st)
+// the search of a batched icon call over its B*n points: cooperative, or Morton packets.  The sign pass and the batch-global outlier
+// list behind it are the common ones (call_geometry), for icon_query_points_batch and icon_train_rows_forward (train_rows.hip) alike.
+int launch_nearest_batch(const QueryCall &c, icon_work *work, hipStream_t st)
 {
-    const icon_mesh *mesh0 = mb->subj[0];
-    const float *d_calibs = bd.calibs;
-    const int64_t NB = N * (int64_t)B;
-    int rc;
-    if (mb->F > kNearLoSlots && work->cap_points_hi < work->cap_points) {      // big meshes: the byte of higher slot bits
-        (void)hipFree(work->d_near_hi); work->d_near_hi = nullptr; work->cap_points_hi = 0;
-        ICON_HIP(hipMalloc((void **)&work->d_near_hi, (size_t)work->cap_points));
-        work->cap_points_hi = work->cap_points;
-    }
-    const NearRef near = work_near(work, mesh0);
-    static const int mode = getenv("ICON_AMD_POINT_SEARCH") ? atoi(getenv("ICON_AMD_POINT_SEARCH")) : 0;   // 0 auto, 2 coop, 3 packets
-    if (mode != 3 && (NB < kPacketMinPoints || mode == 2)) {
-        const int cap = coop_cap(mb->depth_bound);
+    const BatchDev &bd = c.bd;
+    const int64_t NB = c.N;
+    const NearRef near = work_near(work, c);
+    if (coop_search(NB, work)) {
+        const int cap = coop_cap(c.mb->depth_bound);
         hipLaunchKernelGGL(k_nearest_coop<true>, dim3((unsigned)((NB + kCoopWaves - 1) / kCoopWaves)), dim3(kCoopWaves * 64),
-                           kCoopWaves * coop_wave_bytes(cap), st, MeshDev{}, Calib{}, d_points, NB, near, cap, sdf_clip, bd);
+                           kCoopWaves * coop_wave_bytes(cap), st, MeshDev{}, Calib{}, c.points, NB, near, cap, c.sdf_clip, bd);
     } else {
         const int32_t *perm = nullptr;
-        if ((rc = morton_order_batch(work, d_points, d_calibs, N, B, st, &perm))) return rc;
-        const int64_t npad = (N + 63) / 64 * 64;
-        const int64_t nb = (npad * B + kBlock - 1) / kBlock;
-        ICON_ARG(nb < (1ll << 31), "icon_query_points_batch: too many workgroups for one launch");
+        const int rc = morton_order_batch(work, c.points, bd.calibs, bd.n, bd.B, st, &perm);
+        if (rc) return rc;
+        const int64_t npad = (bd.n + 63) / 64 * 64;
+        const int64_t nb = (npad * bd.B + kBlock - 1) / kBlock;
+        ICON_ARG(nb < (1ll << 31), std::string(c.who) + ": too many workgroups for one launch");
         if (work->prof) (void)hipEventRecord(work->ev[4], st);
-        hipLaunchKernelGGL(k_nearest_batch, dim3((unsigned)nb), dim3(kBlock), 0, st, bd, d_points, npad, near, perm, sdf_clip);
+        hipLaunchKernelGGL(k_nearest_batch, dim3((unsigned)nb), dim3(kBlock), 0, st, bd, c.points, npad, near, perm, c.sdf_clip);
         if (work->prof) { (void)hipEventRecord(work->ev[5], st); work->ev_search = true; }
     }
     ICON_HIP(hipGetLastError());
     debug_sync("nearest (batch)", st);
-    if ((rc = launch_sign(mesh0, Calib{}, 0, 0, d_points, NB, sdf_clip, work, false, st, &bd))) return rc;
-    debug_sync("k_sign_wide<batch>", st);
-    if (needs_patch && (rc = outlier_list(work, NB, nullptr, work->d_signs, true, st))) return rc;
     return ICON_OK;
 }
+
+template int launch_features<Src::Batch>(const QueryCall &, icon_work *, hipStream_t);     // k_features<prior, Src::Batch> live in this unit
 
 }  // namespace icon
 
@@ -185,61 +175,17 @@ extern "C" int icon_query_points_batch(const icon_mesh_batch_t *mb, const icon_f
     ICON_ARG(N * (int64_t)B < (1ll << 31), "icon_query_points_batch: B * N must be below 2^31");
     if (search == ICON_SEARCH_BRUTE) return fail(ICON_ERR_UNSUPPORTED, "icon_query_points_batch: search 'brute' is evaluated at batch size 1 only");
     if (work->tie_rule != 0) return fail(ICON_ERR_UNSUPPORTED, "icon_query_points_batch: tie rules are evaluated at batch size 1 only");
-    ICON_ARG(prior_type == ICON_PRIOR_ICON || prior_type == ICON_PRIOR_PAMIR || prior_type == ICON_PRIOR_PIFU, "icon_query_points_batch: unknown prior_type");
-    ICON_ARG(feat->batch == B, "icon_query_points_batch: the feature handle holds another number of subjects");
-    const FeatDev &f = feat->dev;
-    int c0 = 0;
-    if (prior_type == ICON_PRIOR_ICON) {
-        ICON_ARG(mb != nullptr, "icon_query_points_batch: the icon prior needs a mesh batch");
-        ICON_ARG(mb->B == B, "icon_query_points_batch: the mesh batch holds another number of subjects");
-        c0 = f.csel + 1 + ((f.smpl_mask & kSmplCmap) ? 3 : 0) + ((f.smpl_mask & kSmplNorm) ? 3 : 0);
-    } else if (prior_type == ICON_PRIOR_PAMIR) {
-        // [index(im_feat, xy) | index(vol_feat, xyz)] per subject (lib/net/HGPIFuNet.py:346-353): no mesh, no search, no sign pass
-        ICON_ARG(f.n_select == 1, "icon_query_points_batch: pamir prior needs n_select = 1");
-        ICON_ARG(f.vol != nullptr, "icon_query_points_batch: the pamir prior needs a feature handle with a volume (icon_feat_batch_set_volume)");
-        c0 = f.csel + f.Cv;
-    } else {
-        ICON_ARG(f.n_select == 1, "icon_query_points_batch: pifu prior needs n_select = 1");
-        c0 = f.csel + 1;
-    }
-    if (c0 > kCodeSlot) return fail(ICON_ERR_UNSUPPORTED, "icon_query_points_batch: more than 15 MLP input channels");
-    ICON_ARG(c0 == mlp->c0, "icon_query_points_batch: MLP input width does not match the feature layout");
+    QueryCall c = query_call("icon_query_points_batch", Src::Batch, feat, prior_type, sdf_clip, cmap_mode, search);
+    c.mb = mb; c.points = d_points; c.N = N * (int64_t)B;
+    c.bd.calibs = d_calibs; c.bd.n = N; c.bd.B = B; c.bd.plane_stride = feat->plane_stride; c.bd.vol_stride = feat->vol_stride;
+    int rc = describe_call(c);
+    if (rc) return rc;
+    ICON_ARG(c.c0 == mlp->c0, "icon_query_points_batch: MLP input width does not match the feature layout");
     if (N == 0) return ICON_OK;
-    const int64_t NB = N * (int64_t)B;
     hipStream_t st = (hipStream_t)stream;
-    int rc;
-    if ((rc = ensure_work(work, NB, false))) return rc;
-    work->slab_ready = false;
-    work->q_rows_ready = false; work->slab_patched = false;
-    const icon_mesh *mesh0 = (prior_type == ICON_PRIOR_ICON) ? mb->subj[0] : nullptr;
-    BatchDev bd{};
-    bd.meshes = mesh0 ? mb->d_table : nullptr; bd.calibs = d_calibs; bd.n = N; bd.plane_stride = feat->plane_stride; bd.B = B;
-    bd.vol_stride = feat->vol_stride;
-    const bool needs_patch = prior_type == ICON_PRIOR_ICON && cmap_mode == ICON_CMAP_REFERENCE && (f.smpl_mask & kSmplCmap);
-    const int local = (cmap_mode == ICON_CMAP_LOCAL) ? 1 : 0;
+    if ((rc = begin_call(work, c))) return rc;
     mark(work, 0, st);
-    if (prior_type == ICON_PRIOR_ICON && (rc = batch_geometry(mb, bd, d_points, N, B, sdf_clip, needs_patch, work, st))) return rc;
+    if ((rc = call_geometry(c, nullptr, work, st))) return rc;
     mark(work, 1, st);
-    const SignSrc fs = self_signs(work, needs_patch);
-    if (want_fused(precision, search)) {
-        mark(work, 2, st);
-        rc = launch_fused_f16x3(mesh0, feat, mlp, prior_type, Calib{}, LatticeMap{}, 0, 0, d_points, NB, sdf_clip, local, work, fs, d_occ,
-                                false, st, &bd);
-        mark(work, 3, st);
-        return rc;
-    }
-    if ((rc = ensure_work(work, NB, true))) return rc;
-    const NearRef near = work_near(work, mesh0);
-    const unsigned nb = (unsigned)((NB + kBlock - 1) / kBlock);
-#define ICON_LAUNCH(P) hipLaunchKernelGGL((k_features<P, Src::Batch, false>), dim3(nb), dim3(kBlock), 0, st, MeshDev{}, f, Calib{}, LatticeMap{}, d_points, NB, sdf_clip, local, (const int32_t *)nullptr, (const int32_t *)nullptr, near, work->d_x, work->d_code8, 0, bd)
-    if (prior_type == ICON_PRIOR_ICON) ICON_LAUNCH(ICON_PRIOR_ICON);
-    else if (prior_type == ICON_PRIOR_PAMIR) ICON_LAUNCH(ICON_PRIOR_PAMIR);
-    else ICON_LAUNCH(ICON_PRIOR_PIFU);
-#undef ICON_LAUNCH
-    ICON_HIP(hipGetLastError());
-    if ((rc = outlier_patch(work, NB, f.csel + 1, fs, st))) return rc;
-    mark(work, 2, st);
-    rc = mlp_launch(mlp, work->d_x, NB, d_occ, precision, st);
-    mark(work, 3, st);
-    return rc;
+    return call_finish(c, mlp, self_signs(work, c.needs_patch), d_occ, precision, work, st);
 }

@@ -404,7 +404,6 @@ inline int lattice_packet()
     static const int pk_env = getenv("ICON_AMD_PACKET") ? atoi(getenv("ICON_AMD_PACKET")) : 0;
     return pk_env == 2 ? 2 : 4;
 }
-int ensure_work_points(icon_work *w, int64_t n_points);                               // work.hip
 // mc_device.hip
 struct McDevState;
 void mc_destroy(McDevState *s);
@@ -426,22 +425,9 @@ int mlp_launch_f16x3(const icon_mlp *mlp, const float *d_x, int64_t N, float *d_
 uint16_t f32_to_f16_rtn(float f);
 float f16_to_f32(uint16_t h);
 float pick_scale(const std::vector<float> &W);     // power of two that brings max|W| to ~8192
-// fused_f16x3.hip
-int launch_sign(const icon_mesh *mesh, const Calib &cal, int res, int z0, const float *d_points, int64_t N, float sdf_clip,
-                const icon_work *work, bool lattice, hipStream_t st, const BatchDev *bd = nullptr);
-// lattice: evaluates the planes [za, zb) of the slab L (global plane numbers; the whole slab = [L.z0, L.z0 + L.nz)),
-// d_occ is the SLAB's output buffer; points: the N points of the call
-// bd: a batched point-mode call (icon_query_points_batch) - mesh, planes and calibration per subject
-int launch_fused_f16x3(const icon_mesh *mesh, const icon_feat *feat, const icon_mlp *mlp, int prior, const Calib &cal,
-                       const LatticeMap &L, int za, int zb, const float *d_points, int64_t N, float sdf_clip, int cmap_local,
-                       const icon_work *work, const SignSrc &fs, float *d_occ, bool lattice, hipStream_t st,
-                       const BatchDev *bd = nullptr);
 // sort_points.hip: Morton order of a batched call's B*n points, subject first: subject b's points are the sorted positions
 // [b n, (b + 1) n) (the key carries the subject above the Morton bits)
 int morton_order_batch(icon_work *w, const float *d_points, const float *d_calibs, int64_t n, int B, hipStream_t st, const int32_t **perm);
-// batch_query.hip: search + sign pass + (needs_patch) batch-global outlier list of a batched icon call; ensure_work(N * B) came first
-int batch_geometry(const icon_mesh_batch *mb, const BatchDev &bd, const float *d_points, int64_t N, int B, float sdf_clip,
-                   bool needs_patch, icon_work *work, hipStream_t st);
 // work.hip: the workspace's scratch and profiling events
 int ensure_work(icon_work *w, int64_t n_points, bool need_x);                          // scratch for n_points (need_x: the 64-byte input rows too)
 void mark(icon_work *w, int k, hipStream_t st);                                       // profiling event k of the call
@@ -479,6 +465,67 @@ enum Opt { kOptPairBox, kOptNodeBox, kOptBoxClamp, kOptLatticeFast, kOptUnfused,
 int option(Opt o);
 }  // namespace icon
 
+namespace icon {
+constexpr float kIdentCalib[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+constexpr int kNearLoSlots = 32768;      // slots addressable by the 15 low bits of a NearRef entry
+
+// ONE query call, from its entry point to its last launch.  The entry point fills the first two groups, describe_call checks them
+// and derives the third, begin_call sizes the workspace for it, the geometry step (call_geometry) and the finish step (call_finish)
+// and every launcher read it.  It lives on the entry point's stack; only icon_grid_slab_features leaves its record behind
+// (icon_work::slab), for the icon_grid_slab_finish* calls that complete it.
+struct QueryCall {
+    const char *who = "";                 // the entry point, as the refusals name it
+    Src src = Src::Points;                // where the work items come from: a lattice slab (L), points, the B * n points of a batch (bd)
+    const icon_mesh *mesh = nullptr;      // Src::Batch: subject 0's (the slot width of the search results), set by describe_call
+    const icon_mesh_batch *mb = nullptr;  // Src::Batch, icon prior
+    BatchDev bd{};
+    const icon_feat *feat = nullptr;
+    int prior = 0, cmap_mode = 0, search = 0;
+    float sdf_clip = 0.f;
+    Calib cal{};
+    LatticeMap L{};
+    const float *points = nullptr;
+    int64_t N = 0;                        // work items (Src::Batch: B * n)
+    // a level of the adaptive schedule (adaptive.hip): the points are a SUBSET of a lattice the search ran on - the search results of
+    // point i are entry map[i], its occupancy goes to d_occ[map[i]] - and their number lives on the device (*n_dev <= N, no read-back)
+    const int32_t *map = nullptr;
+    const int *n_dev = nullptr;
+    // describe_call
+    int c0 = 0;                           // MLP input width of the feature layout
+    int cmap_slot = 0;                    // row slot of the cmap channels
+    bool needs_patch = false;             // reference cmap mode: the outlier rows' cmap comes from the call's sign list (HGPIFuNet.py:303-305)
+    // progress of the materialising finish (idempotent per call: a slab may be finished piece by piece)
+    bool rows_ready = false, patched = false;
+};
+// what every entry point is handed in the same words
+inline QueryCall query_call(const char *who, Src src, const icon_feat *feat, int prior, float sdf_clip, int cmap_mode, int search)
+{
+    QueryCall c;
+    c.who = who; c.src = src; c.feat = feat; c.prior = prior; c.sdf_clip = sdf_clip; c.cmap_mode = cmap_mode; c.search = search;
+    return c;
+}
+// query_kernels.hip.  describe_call: the derived facts; refuses a prior the handles do not serve (ICON_ERR_ARG) and a layout wider
+// than a row (ICON_ERR_UNSUPPORTED).  call_geometry: what can be done before the sign list of the whole call is known - icon prior:
+// the search (lattice / points here, launch_nearest_batch; brute force: the rows themselves) and sign_and_list; nothing otherwise.
+// sign_and_list: the sign pass and, if needs_patch, the call's own outlier list into `signs` (null: work->d_signs).
+// call_finish: the MLP input of every work item and the MLP - fused, or rows + patch + MLP kernels - given where the call's
+// outlier signs are; lattice calls evaluate the planes [za, zb) of the slab into the SLAB's buffer d_occ.
+int describe_call(QueryCall &c);
+int describe_call(QueryCall &c, const FeatDev &f);    // ... of a call whose rows have the layout f, no feature handle behind it
+bool coop_search(int64_t N, const icon_work *work);    // point mode: one wavefront per point (sparse calls) or Morton packets
+int call_geometry(QueryCall &c, int8_t *d_signs_out, icon_work *work, hipStream_t st);
+int sign_and_list(const QueryCall &c, int8_t *d_signs_out, icon_work *work, hipStream_t st);
+int call_finish(QueryCall &c, const icon_mlp *mlp, const SignSrc &fs, float *d_occ, int precision, icon_work *work, hipStream_t st, int za = 0, int zb = 0);
+// batch_query.hip: the search of a Src::Batch call (cooperative, or Morton packets padded per subject)
+int launch_nearest_batch(const QueryCall &c, icon_work *work, hipStream_t st);
+// fused_f16x3.hip
+int launch_sign(const QueryCall &c, const icon_work *work, hipStream_t st);
+int launch_fused_f16x3(const QueryCall &c, const icon_mlp *mlp, const icon_work *work, int za, int zb, const SignSrc &fs, float *d_occ, hipStream_t st);
+// work.hip: starts a call on a workspace - scratch for c.N work items (need_x: the 64-byte input rows too), the byte of higher slot
+// bits for a mesh beyond kNearLoSlots, and whatever icon_grid_slab_features prepared there is gone
+int begin_call(icon_work *w, const QueryCall &c, bool need_x = false);
+}  // namespace icon
+
 struct icon_work {
     float *d_x = nullptr;                 // [cap_x][16] MLP input rows (materialising paths only: f32 / brute force)
     int64_t cap_x = 0;
@@ -513,25 +560,12 @@ struct icon_work {
     void *d_sort_tmp = nullptr;
     size_t sort_tmp_bytes = 0;
     int64_t cap_sort = 0;
-    // state of the split slab protocol (icon_grid_slab_features -> icon_grid_slab_finish)
-    int slab_res = 0, slab_z0 = 0, slab_z1 = 0, slab_c0 = 0, slab_cmap_slot = 0;
-    bool slab_ready = false, slab_needs_patch = false, slab_patched = false;
+    // the split slab protocol: the call icon_grid_slab_features prepared, until icon_grid_slab_finish or any other query call on this
+    // workspace (icon_grid_slab_finish_gathered leaves it: a slab may be finished piece by piece).  Its handles must outlive the pair.
+    icon::QueryCall slab{};
+    bool slab_ready = false;
     // diagnostics: tie rule of the nearest-triangle choice (icon_work_set_tie_rule); 0 = the definition (S3)
     int tie_rule = 0, tie_ulps = 0;
-    // what phase 1 of a query recorded for phase 2 (the handles must outlive the pair of calls)
-    const icon_mesh *q_mesh = nullptr;
-    const icon_feat *q_feat = nullptr;
-    int q_prior = 0, q_cmap_mode = 0, q_search = 0;
-    float q_sdf_clip = 0.f;
-    icon::Calib q_cal{};
-    icon::LatticeMap q_L{};
-    const float *q_points = nullptr;
-    int64_t q_N = 0;
-    bool q_lattice = false, q_rows_ready = false;
-    // lattice-subset calls of the adaptive schedule (adaptive.hip): the number of points lives on the device (no read-back
-    // between the levels), the search results are indexed through q_map, the occupancies go to d_occ[q_map[i]]
-    const int32_t *q_map = nullptr;
-    const int *q_n_dev = nullptr;
     int reserve_cus = 0;                  // the persistent MLP kernel leaves this many CUs free (icon_work_set_reserve_cus)
     // icon_adaptive_eval with host counts (it synchronises at its end anyway): the fused kernels of the schedule raise THIS sticky
     // word instead of d_flag and no k_rescue_fused is launched behind them (three launches at the launch floor per schedule);
@@ -557,13 +591,12 @@ struct icon_work {
 };
 
 namespace icon {
-constexpr int kNearLoSlots = 32768;      // slots addressable by the 15 low bits
-inline NearRef work_near(const icon_work *w, const icon_mesh *mesh)
+inline NearRef work_near(const icon_work *w, const QueryCall &c)
 {
     NearRef r;
     r.lo = w->d_near16; r.d2 = w->d_near_d2;
-    r.hi = (mesh && mesh->F > kNearLoSlots) ? w->d_near_hi : nullptr;
-    r.map = w->q_map;
+    r.hi = (c.mesh && c.mesh->F > kNearLoSlots) ? w->d_near_hi : nullptr;
+    r.map = c.map;
     return r;
 }
 }  // namespace icon

@@ -592,24 +592,25 @@ __global__ __launch_bounds__(64) void k_rescue_fused(FusedGeom G, float *__restr
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-int launch_sign(const icon_mesh *mesh, const Calib &cal, int res, int z0, const float *d_points, int64_t N, float sdf_clip,
-                const icon_work *work, bool lattice, hipStream_t st, const BatchDev *bd)
+int launch_sign(const QueryCall &c, const icon_work *work, hipStream_t st)
 {
+    const int64_t N = c.N;
     const int64_t nb = (N + 255) / 256;
     ICON_ARG(nb > 0 && nb < (1ll << 31), "too many workgroups for one launch");
-    const float far_box2 = far_box_dist2(sdf_clip);
-    if (lattice) hipLaunchKernelGGL(k_sign<true>, dim3((unsigned)nb), dim3(256), 0, st, mesh->dev, cal, res, z0, d_points, N, sdf_clip,
-                                    work->d_row_count, work->d_row_slots, work_near(work, mesh), work->d_code8, work->d_block_counts,
-                                    (unsigned long long *)work->d_grp_mask, far_box2, (const int *)nullptr, work->d_flag);
-    else if (bd)                                  // a batched call: every point in its subject's mesh (`mesh`: subject 0, for the slot width)
-        hipLaunchKernelGGL(k_sign_wide<true>, dim3((unsigned)nb), dim3(1024), 0, st, MeshDev{}, Calib{}, d_points, N, sdf_clip, work_near(work, mesh), work->d_code8,
-                           work->d_block_counts, (unsigned long long *)work->d_grp_mask, far_box2, (const int *)nullptr, work->d_flag, *bd);
-    else if (work->q_n_dev || N <= 262144)        // few points (a level of the schedule: the size on the device is a few percent of N)
-        hipLaunchKernelGGL(k_sign_wide<false>, dim3((unsigned)nb), dim3(1024), 0, st, mesh->dev, cal, d_points, N, sdf_clip, work_near(work, mesh), work->d_code8,
-                           work->d_block_counts, (unsigned long long *)work->d_grp_mask, far_box2, work->q_n_dev, work->d_flag, BatchDev{});
-    else hipLaunchKernelGGL(k_sign<false>, dim3((unsigned)nb), dim3(256), 0, st, mesh->dev, cal, res, z0, d_points, N, sdf_clip,
-                            (const int32_t *)nullptr, (const int32_t *)nullptr, work_near(work, mesh), work->d_code8, work->d_block_counts,
-                            (unsigned long long *)work->d_grp_mask, far_box2, work->q_n_dev, work->d_flag);
+    const float far_box2 = far_box_dist2(c.sdf_clip);
+    const NearRef near = work_near(work, c);
+    if (c.src == Src::Lattice) hipLaunchKernelGGL(k_sign<true>, dim3((unsigned)nb), dim3(256), 0, st, c.mesh->dev, c.cal, c.L.res, c.L.z0, c.points, N, c.sdf_clip,
+                                                  work->d_row_count, work->d_row_slots, near, work->d_code8, work->d_block_counts,
+                                                  (unsigned long long *)work->d_grp_mask, far_box2, (const int *)nullptr, work->d_flag);
+    else if (c.src == Src::Batch)                 // every point in its subject's mesh
+        hipLaunchKernelGGL(k_sign_wide<true>, dim3((unsigned)nb), dim3(1024), 0, st, MeshDev{}, Calib{}, c.points, N, c.sdf_clip, near, work->d_code8,
+                           work->d_block_counts, (unsigned long long *)work->d_grp_mask, far_box2, (const int *)nullptr, work->d_flag, c.bd);
+    else if (c.n_dev || N <= 262144)              // few points (a level of the schedule: the size on the device is a few percent of N)
+        hipLaunchKernelGGL(k_sign_wide<false>, dim3((unsigned)nb), dim3(1024), 0, st, c.mesh->dev, c.cal, c.points, N, c.sdf_clip, near, work->d_code8,
+                           work->d_block_counts, (unsigned long long *)work->d_grp_mask, far_box2, c.n_dev, work->d_flag, BatchDev{});
+    else hipLaunchKernelGGL(k_sign<false>, dim3((unsigned)nb), dim3(256), 0, st, c.mesh->dev, c.cal, c.L.res, c.L.z0, c.points, N, c.sdf_clip,
+                            (const int32_t *)nullptr, (const int32_t *)nullptr, near, work->d_code8, work->d_block_counts,
+                            (unsigned long long *)work->d_grp_mask, far_box2, c.n_dev, work->d_flag);
     ICON_HIP(hipGetLastError());
     work->flag_clean = work->d_flag != nullptr;
     return ICON_OK;
@@ -657,13 +658,17 @@ int once_per_device(int kernel_id, const std::function<hipError_t()> &set)
     return ICON_OK;
 }
 
-int launch_fused_f16x3(const icon_mesh *mesh, const icon_feat *feat, const icon_mlp *mlp, int prior, const Calib &cal,
-                       const LatticeMap &L, int za, int zb, const float *d_points, int64_t N, float sdf_clip, int cmap_local,
-                       const icon_work *work, const SignSrc &fs, float *d_occ, bool lattice, hipStream_t st, const BatchDev *bd)
+// lattice: evaluates the planes [za, zb) of the slab c.L (global plane numbers; the whole slab = [L.z0, L.z0 + L.nz)), d_occ is the
+// SLAB's output buffer; points / batch: the c.N work items of the call
+int launch_fused_f16x3(const QueryCall &c, const icon_mlp *mlp, const icon_work *work, int za, int zb, const SignSrc &fs, float *d_occ, hipStream_t st)
 {
+    const bool lattice = c.src == Src::Lattice;
+    const LatticeMap &L = c.L;
+    const int prior = c.prior;
+    int64_t N = c.N;
     FusedGeom G{};
-    if (mesh) G.m = mesh->dev;
-    G.f = feat->dev; G.cal = cal; G.pts = d_points; G.sdf_clip = sdf_clip; G.cmap_local = cmap_local;
+    if (c.mesh) G.m = c.mesh->dev;
+    G.f = c.feat->dev; G.cal = c.cal; G.pts = c.points; G.sdf_clip = c.sdf_clip; G.cmap_local = c.cmap_mode == ICON_CMAP_LOCAL ? 1 : 0;
     if (lattice) {
         // planes [za, zb) of the slab, minus the z shell when it is skipped; x / y interior likewise
         const int zs = std::max(za, L.off), ze = std::min(zb, L.res - L.off);
@@ -680,8 +685,8 @@ int launch_fused_f16x3(const icon_mesh *mesh, const icon_feat *feat, const icon_
     if (N <= 0) { ICON_HIP(hipGetLastError()); return ICON_OK; }
     ICON_ARG(N < (1ll << 31), "fused: more than 2^31 points in one call");
     G.N = N;
-    G.near = work_near(work, mesh); G.code8 = work->d_code8;
-    if (!lattice) { G.n_dev = work->q_n_dev; G.out_map = work->q_map; }
+    G.near = work_near(work, c); G.code8 = work->d_code8;
+    if (!lattice) { G.n_dev = c.n_dev; G.out_map = c.map; }
     G.clock = work->prof ? work->d_clock : nullptr;
     G.steal = nullptr; G.steal_static = 0; G.steal_grp = 1; G.steal_ngrp = 0;
     G.block_offsets = work->d_block_offsets; G.grp_mask = (const unsigned long long *)work->d_grp_mask;
@@ -708,7 +713,7 @@ int launch_fused_f16x3(const icon_mesh *mesh, const icon_feat *feat, const icon_
     const int64_t n_resc = std::min<int64_t>((N + 63) / 64, 2048);
     // calls of few points: the kernel variant that may cut its tiles in half (k_fused_f16x3<..., SMALL>; icon prior only); its
     // grid is sized for 128-point tiles.  A schedule level's N is n_max here - its real size lives on the device
-    const bool small = prior == ICON_PRIOR_ICON && (work->q_n_dev != nullptr || N <= 262144);
+    const bool small = prior == ICON_PRIOR_ICON && (c.n_dev != nullptr || N <= 262144);
     const int64_t ntiles = small ? (N + kTilePts / 2 - 1) / (kTilePts / 2) : (N + kTilePts - 1) / kTilePts;
     // one persistent workgroup per CU (LDS-bound: 132 KiB, all registers).  Multi-GPU: a collective's kernels cannot co-reside
     // with it on a CU - icon_work_set_reserve_cus leaves some CUs to them
@@ -720,14 +725,14 @@ int launch_fused_f16x3(const icon_mesh *mesh, const icon_feat *feat, const icon_
         const int per = (int)(ntiles / grid);
         const int pool_len = (int)((int64_t)per * work->steal_permille / 1000);
         // (a schedule level's N is the bound r^3: its device-side count gets the static partition - see FusedGeom::steal)
-        if (!small && !work->q_n_dev && work->d_steal && pool_len > 0 && ntiles > (int64_t)grid) {
+        if (!small && !c.n_dev && work->d_steal && pool_len > 0 && ntiles > (int64_t)grid) {
             G.steal = work->d_steal; G.steal_grp = std::min(work->steal_grp, kMaxStealGroup);
             G.steal_static = per - pool_len;
             G.steal_ngrp = (pool_len + 1 + G.steal_grp - 1) / G.steal_grp;     // covers the spans that are one tile longer
         }
     }
     if (G.clock) work->clock_grid = (int)std::min<unsigned>(grid, (unsigned)kMaxProfGrid);
-    const BatchDev batch = bd ? *bd : BatchDev{};                // (read by the Src::Batch instantiations only)
+    const BatchDev &batch = c.bd;                                // (read by the Src::Batch instantiations only)
 #define ICON_FUSED(P, S, ID, ...)                                                                                          \
     do {                                                                                                                   \
         if ((rc = once_per_device(ID, [] { return hipFuncSetAttribute(reinterpret_cast<const void *>(k_fused_f16x3<P, Src::S, ##__VA_ARGS__>), \
@@ -739,8 +744,8 @@ int launch_fused_f16x3(const icon_mesh *mesh, const icon_feat *feat, const icon_
             debug_sync("k_rescue_fused", st);                                                                              \
         }                                                                                                                  \
     } while (0)
-    if (bd) {                                    // batched point mode (no lattice, no device-side size, no deferred flag)
-        if (lattice || defer || work->q_n_dev) return fail(ICON_ERR_UNSUPPORTED, "fused: batched call outside point mode");
+    if (c.src == Src::Batch) {                   // batched point mode (no lattice, no device-side size, no deferred flag)
+        if (defer || c.n_dev) return fail(ICON_ERR_UNSUPPORTED, "fused: batched call outside point mode");
         if (small) ICON_FUSED(ICON_PRIOR_ICON, Batch, 11, true);
         else if (prior == ICON_PRIOR_ICON) ICON_FUSED(ICON_PRIOR_ICON, Batch, 12);
         else if (prior == ICON_PRIOR_PAMIR) ICON_FUSED(ICON_PRIOR_PAMIR, Batch, 14);

@@ -133,5 +133,36 @@ __global__ __launch_bounds__(kBlock) void k_features(MeshDev m, FeatDev f, Calib
     if (live) { store_row(X, i, row); code8[i] = (uint8_t)code; }   // byte copy of the code word: the outlier passes stream 1 B/pt
 }
 
+// X rows + codes of the call's work items (the materialising path): k_features, reading the search results unless the search is
+// brute force.  A template of the source so that each unit instantiates the kernels of the sources it serves (query_kernels.hip:
+// lattice and points, batch_query.hip: batch).
+template <Src SRC>
+int launch_features(const QueryCall &c, icon_work *work, hipStream_t st)
+{
+    // every point of the slab gets a row: tile the whole slab, whatever region the geometry pre-pass covered
+    LatticeMap Lf = c.L;
+    if (SRC == Src::Lattice) {
+        Lf.sx0 = Lf.sy0 = Lf.sz0 = 0; Lf.sx1 = Lf.sy1 = c.L.res; Lf.sz1 = c.L.nz;
+        Lf.tx = (c.L.res + 15) / 16; Lf.ty = (c.L.res + 3) / 4; Lf.tz = (c.L.nz + 3) / 4; Lf.pk = 4; Lf.trim = 0;
+    }
+    const int64_t nb = SRC == Src::Lattice ? (int64_t)Lf.tx * Lf.ty * Lf.tz : (c.N + kBlock - 1) / kBlock;
+    ICON_ARG(nb > 0 && nb < (1ll << 31), "too many workgroups for one launch");
+    const dim3 grid((unsigned)nb), block(kBlock);
+    constexpr bool batch = SRC == Src::Batch;    // mesh and calibration per subject, through c.bd
+    const MeshDev md = (c.mesh && !batch) ? c.mesh->dev : MeshDev{};
+    const int32_t *row_count = batch ? nullptr : work->d_row_count, *row_slots = batch ? nullptr : work->d_row_slots;
+    const int local = (c.cmap_mode == ICON_CMAP_LOCAL) ? 1 : 0;
+#define ICON_LAUNCH(P, B) hipLaunchKernelGGL((k_features<P, SRC, B>), grid, block, 0, st, md, c.feat->dev, c.cal, Lf, c.points, c.N, c.sdf_clip, local, row_count, row_slots, work_near(work, c), work->d_x, work->d_code8, c.L.off, c.bd)
+    if constexpr (!batch) {                      // (a batched call refuses the brute-force search: no such instantiation)
+        if (c.prior == ICON_PRIOR_ICON && c.search == ICON_SEARCH_BRUTE) { ICON_LAUNCH(ICON_PRIOR_ICON, true); ICON_HIP(hipGetLastError()); return ICON_OK; }
+    }
+    if (c.prior == ICON_PRIOR_ICON) ICON_LAUNCH(ICON_PRIOR_ICON, false);
+    else if (c.prior == ICON_PRIOR_PAMIR) ICON_LAUNCH(ICON_PRIOR_PAMIR, false);
+    else ICON_LAUNCH(ICON_PRIOR_PIFU, false);
+#undef ICON_LAUNCH
+    ICON_HIP(hipGetLastError());
+    return ICON_OK;
+}
+extern template int launch_features<Src::Batch>(const QueryCall &, icon_work *, hipStream_t);     // batch_query.hip
 
 }  // namespace icon

@@ -287,9 +287,8 @@ extern "C" int icon_sdf_query(const icon_mesh_t *mesh, const float *d_points, in
                            mesh->dev, d_points, N, d_sdf, d_norm, d_cmap, d_vis, d_face, d_inside, cap);
     } else {                              // large batches: packets over the Morton order (scratch freed after a stream sync)
         icon_work tmp;
-        static const float ident[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
         const int32_t *perm = nullptr;
-        int rc = morton_order(&tmp, d_points, ident, nullptr, N, st, &perm);
+        int rc = morton_order(&tmp, d_points, kIdentCalib, nullptr, N, st, &perm);
         if (!rc) {
             hipLaunchKernelGGL(k_sdf_query<false>, dim3((unsigned)nb), dim3(kBlock), 0, st, mesh->dev, d_points, N, d_sdf, d_norm,
                                d_cmap, d_vis, d_face, d_inside, perm);
@@ -302,34 +301,61 @@ extern "C" int icon_sdf_query(const icon_mesh_t *mesh, const float *d_points, in
     return ICON_OK;
 }
 
-namespace {
+namespace icon {
 
-int check_prior(const icon_mesh_t *mesh, const icon_feat_t *feat, int prior, int *c0)
+int describe_call(QueryCall &c)
 {
-    ICON_ARG(feat != nullptr, "feature handle is null");
-    const FeatDev &f = feat->dev;
-    if (prior == ICON_PRIOR_ICON) {
-        ICON_ARG(mesh != nullptr, "icon prior needs a mesh handle");
+    ICON_ARG(c.feat != nullptr, std::string(c.who) + ": feature handle is null");
+    if (c.src == Src::Batch) ICON_ARG(c.feat->batch == c.bd.B, std::string(c.who) + ": the feature handle holds another number of subjects");
+    return describe_call(c, c.feat->dev);
+}
+
+// the same for a call whose rows have the layout f without a feature handle behind it (the training rows: train_rows.hip)
+int describe_call(QueryCall &c, const FeatDev &f)
+{
+    const auto say = [&c](const char *what) { return std::string(c.who) + ": " + what; };      // (evaluated by a refusal only)
+    ICON_ARG(c.prior == ICON_PRIOR_ICON || c.prior == ICON_PRIOR_PAMIR || c.prior == ICON_PRIOR_PIFU, say("unknown prior_type"));
+    if (c.prior == ICON_PRIOR_ICON) {
+        if (c.src == Src::Batch) {
+            ICON_ARG(c.mb != nullptr, say("the icon prior needs a mesh batch"));
+            ICON_ARG(c.mb->B == c.bd.B, say("the mesh batch holds another number of subjects"));
+            c.mesh = c.mb->subj[0]; c.bd.meshes = c.mb->d_table;
+        }
+        ICON_ARG(c.mesh != nullptr, say("the icon prior needs a mesh handle"));
         // n_select = 2: smpl_vis picks the front or back half (HGPIFuNet.py:334-336); 1: smpl_feats without 'vis', every channel is an input (:345-346)
-        *c0 = f.csel + 1 + ((f.smpl_mask & kSmplCmap) ? 3 : 0) + ((f.smpl_mask & kSmplNorm) ? 3 : 0);
-    } else if (prior == ICON_PRIOR_PAMIR) {
-        ICON_ARG(f.n_select == 1 && f.vol != nullptr, "pamir prior needs n_select = 1 and a volume");
-        *c0 = f.csel + f.Cv;
-    } else if (prior == ICON_PRIOR_PIFU) {
-        ICON_ARG(f.n_select == 1, "pifu prior needs n_select = 1");
-        *c0 = f.csel + 1;
+        c.c0 = f.csel + 1 + ((f.smpl_mask & kSmplCmap) ? 3 : 0) + ((f.smpl_mask & kSmplNorm) ? 3 : 0);
+    } else if (c.prior == ICON_PRIOR_PAMIR) {
+        // [index(im_feat, xy) | index(vol_feat, xyz)] (lib/net/HGPIFuNet.py:346-353): no mesh, no search, no sign pass
+        ICON_ARG(f.n_select == 1, say("the pamir prior needs n_select = 1"));
+        ICON_ARG(f.vol != nullptr, say("the pamir prior needs a feature handle with a volume (icon_feat_batch_set_volume for a batch)"));
+        c.c0 = f.csel + f.Cv;
     } else {
-        return fail(ICON_ERR_ARG, "unknown prior_type");
+        ICON_ARG(f.n_select == 1, say("the pifu prior needs n_select = 1"));
+        c.c0 = f.csel + 1;
     }
-    if (*c0 > kCodeSlot) return fail(ICON_ERR_UNSUPPORTED, "more than 15 MLP input channels");
+    if (c.c0 > kCodeSlot) return fail(ICON_ERR_UNSUPPORTED, say("more than 15 MLP input channels"));
+    c.needs_patch = c.prior == ICON_PRIOR_ICON && c.cmap_mode == ICON_CMAP_REFERENCE && (f.smpl_mask & kSmplCmap);
+    c.cmap_slot = f.csel + 1;
     return ICON_OK;
 }
 
-// geometry pre-pass of the icon prior (BVH search): per-row crossing lists (lattice), nearest triangle -> near
-template <bool LATTICE>
-int launch_nearest(const icon_mesh_t *mesh, const Calib &cal, const LatticeMap &L, const float *d_points, int64_t N, float sdf_clip,
-                   icon_work *work, hipStream_t st)
+// point mode: sparse calls walk the tree one wavefront per point; a call dense enough for a wave's 64 Morton neighbours to be
+// close together goes through the packet kernels (the alternative tie rule - diagnostics - lives in the packet kernel only)
+bool coop_search(int64_t N, const icon_work *work)
 {
+    static const int mode = getenv("ICON_AMD_POINT_SEARCH") ? atoi(getenv("ICON_AMD_POINT_SEARCH")) : 0;   // 0 auto, 2 coop, 3 packets
+    return work->tie_rule == 0 && mode != 3 && (N < kPacketMinPoints || mode == 2);
+}
+
+namespace {
+
+// the search of a lattice / points call (icon prior, BVH): per-row crossing lists (lattice), nearest triangle -> work_near
+template <bool LATTICE>
+int launch_nearest(const QueryCall &c, icon_work *work, hipStream_t st)
+{
+    const icon_mesh *mesh = c.mesh;
+    const LatticeMap &L = c.L;
+    const int64_t N = c.N;
     LatticeFast *lf = nullptr;
     if (LATTICE) {
         const int64_t rows = (int64_t)L.nz * L.res;
@@ -355,24 +381,16 @@ int launch_nearest(const icon_mesh_t *mesh, const Calib &cal, const LatticeMap &
     int64_t nb;
     if (LATTICE) nb = (int64_t)L.tx * L.ty * L.tz; else nb = (N + kBlock - 1) / kBlock;
     ICON_ARG(nb >= 0 && nb < (1ll << 31), "too many workgroups for one launch");
-    if (mesh->F > kNearLoSlots && work->cap_points_hi < work->cap_points) {      // big meshes: the byte of higher slot bits
-        (void)hipFree(work->d_near_hi); work->d_near_hi = nullptr; work->cap_points_hi = 0;
-        ICON_HIP(hipMalloc((void **)&work->d_near_hi, (size_t)work->cap_points));
-        work->cap_points_hi = work->cap_points;
-    }
-    const NearRef near = work_near(work, mesh);
-    // point mode: sparse batches walk the tree one wavefront per point; a batch dense enough for a wave's 64
-    // Morton neighbours to be close together goes through the packet kernel
+    const NearRef near = work_near(work, c);
     const int32_t *perm = nullptr;
-    static const int mode = getenv("ICON_AMD_POINT_SEARCH") ? atoi(getenv("ICON_AMD_POINT_SEARCH")) : 0;   // 0 auto, 2 coop, 3 packets
-    const bool alt = work->tie_rule != 0;        // diagnostics: the alternative tie rule lives in the packet kernel only
-    if (!LATTICE && !alt && mode != 3 && (N < kPacketMinPoints || mode == 2)) {
+    const bool alt = work->tie_rule != 0;
+    if (!LATTICE && coop_search(N, work)) {
         const int cap = coop_cap(mesh->depth_bound);
         hipLaunchKernelGGL(k_nearest_coop<false>, dim3((unsigned)((N + kCoopWaves - 1) / kCoopWaves)), dim3(kCoopWaves * 64),
-                           kCoopWaves * coop_wave_bytes(cap), st, mesh->dev, cal, d_points, N, near, cap, sdf_clip, BatchDev{});
+                           kCoopWaves * coop_wave_bytes(cap), st, mesh->dev, c.cal, c.points, N, near, cap, c.sdf_clip, BatchDev{});
     } else if (nb > 0) {                         // nb == 0: a slab that is all shell (nothing to search)
         if (!LATTICE) {
-            const int rc = morton_order(work, d_points, cal.m, cal.d, N, st, &perm);
+            const int rc = morton_order(work, c.points, c.cal.m, c.cal.d, N, st, &perm);
             if (rc) return rc;
         }
         const int share_env = option(kOptShareWaves);            // diagnostics: 1 = never, 8 / 16
@@ -380,134 +398,100 @@ int launch_nearest(const icon_mesh_t *mesh, const Calib &cal, const LatticeMap &
         ShareDbg dbg{};
         if (nw > 1) { const int rc = work_share_dbg(work, &dbg); if (rc) return rc; }
         if (work->prof) (void)hipEventRecord(work->ev[4], st);
-        if (nw == 16) hipLaunchKernelGGL(k_nearest_shared<16>, dim3((unsigned)nb * 4), dim3(16 * 64), 0, st, mesh->dev, L, near, sdf_clip, dbg);
-        else if (nw == 8) hipLaunchKernelGGL(k_nearest_shared<8>, dim3((unsigned)nb * 4), dim3(8 * 64), 0, st, mesh->dev, L, near, sdf_clip, dbg);
-        else if (alt) hipLaunchKernelGGL((k_nearest<LATTICE, true, false>), dim3((unsigned)nb), dim3(kBlock), 0, st, mesh->dev, cal, L, d_points, N, near, perm, sdf_clip, work->tie_ulps, lf);
-        else if (LATTICE && !(mesh->dev.box_clamp && mesh->dev.pbox_off && mesh->dev.nbox_off)) hipLaunchKernelGGL((k_nearest<true, false, false>), dim3((unsigned)nb), dim3(kBlock), 0, st, mesh->dev, cal, L, d_points, N, near, perm, sdf_clip, 0, lf);
-        else hipLaunchKernelGGL((k_nearest<LATTICE, false, LATTICE>), dim3((unsigned)nb), dim3(kBlock), 0, st, mesh->dev, cal, L, d_points, N, near, perm, sdf_clip, 0, lf);
+        if (nw == 16) hipLaunchKernelGGL(k_nearest_shared<16>, dim3((unsigned)nb * 4), dim3(16 * 64), 0, st, mesh->dev, L, near, c.sdf_clip, dbg);
+        else if (nw == 8) hipLaunchKernelGGL(k_nearest_shared<8>, dim3((unsigned)nb * 4), dim3(8 * 64), 0, st, mesh->dev, L, near, c.sdf_clip, dbg);
+        else if (alt) hipLaunchKernelGGL((k_nearest<LATTICE, true, false>), dim3((unsigned)nb), dim3(kBlock), 0, st, mesh->dev, c.cal, L, c.points, N, near, perm, c.sdf_clip, work->tie_ulps, lf);
+        else if (LATTICE && !(mesh->dev.box_clamp && mesh->dev.pbox_off && mesh->dev.nbox_off)) hipLaunchKernelGGL((k_nearest<true, false, false>), dim3((unsigned)nb), dim3(kBlock), 0, st, mesh->dev, c.cal, L, c.points, N, near, perm, c.sdf_clip, 0, lf);
+        else hipLaunchKernelGGL((k_nearest<LATTICE, false, LATTICE>), dim3((unsigned)nb), dim3(kBlock), 0, st, mesh->dev, c.cal, L, c.points, N, near, perm, c.sdf_clip, 0, lf);
         if (work->prof) { (void)hipEventRecord(work->ev[5], st); work->ev_search = true; }
     }
     ICON_HIP(hipGetLastError());
     debug_sync(LATTICE ? "k_row_crossings + k_nearest<lattice>" : "nearest (points)", st);
-    const int rc_sign = launch_sign(mesh, cal, L.res, L.z0, d_points, N, sdf_clip, work, LATTICE, st);
-    debug_sync("k_sign", st);
-    return rc_sign;
-}
-
-// X rows + codes (the materialising path): k_features, reading `near` unless the search is brute force
-template <bool LATTICE>
-int launch_features(const icon_mesh_t *mesh, const icon_feat_t *feat, int prior, float sdf_clip, int cmap_mode,
-                    const Calib &cal, const LatticeMap &L, const float *d_points, int64_t N, int search,
-                    icon_work *work, hipStream_t st)
-{
-    // every point of the slab gets a row: tile the whole slab, whatever region the geometry pre-pass covered
-    LatticeMap Lf = L;
-    const int skip_shell = L.off;
-    if (LATTICE) {
-        Lf.sx0 = Lf.sy0 = Lf.sz0 = 0; Lf.sx1 = Lf.sy1 = L.res; Lf.sz1 = L.nz;
-        Lf.tx = (L.res + 15) / 16; Lf.ty = (L.res + 3) / 4; Lf.tz = (L.nz + 3) / 4; Lf.pk = 4; Lf.trim = 0;
-    }
-    int64_t nb;
-    if (LATTICE) nb = (int64_t)Lf.tx * Lf.ty * Lf.tz; else nb = (N + kBlock - 1) / kBlock;
-    ICON_ARG(nb > 0 && nb < (1ll << 31), "too many workgroups for one launch");
-    const dim3 grid((unsigned)nb), block(kBlock);
-    const MeshDev md = mesh ? mesh->dev : MeshDev{};
-    const int local = (cmap_mode == ICON_CMAP_LOCAL) ? 1 : 0;
-    const bool brute = (search == ICON_SEARCH_BRUTE);
-#define ICON_LAUNCH(P, B) hipLaunchKernelGGL((k_features<P, LATTICE ? Src::Lattice : Src::Points, B>), grid, block, 0, st, md, feat->dev, cal, Lf, d_points, N, sdf_clip, local, work->d_row_count, work->d_row_slots, work_near(work, mesh), work->d_x, work->d_code8, skip_shell, BatchDev{})
-    if (prior == ICON_PRIOR_ICON) { if (brute) ICON_LAUNCH(ICON_PRIOR_ICON, true); else ICON_LAUNCH(ICON_PRIOR_ICON, false); }
-    else if (prior == ICON_PRIOR_PAMIR) ICON_LAUNCH(ICON_PRIOR_PAMIR, false);
-    else ICON_LAUNCH(ICON_PRIOR_PIFU, false);
-#undef ICON_LAUNCH
-    ICON_HIP(hipGetLastError());
     return ICON_OK;
 }
 
-// Phase 1 of every query: what can be done before the outlier sign list of the whole call is known.
-//   icon prior, BVH: nearest search + k_sign (+ the call's own sign list in reference cmap mode); no rows yet
-//   icon prior, brute force: k_features (rows + codes) + sign list
-//   pamir / pifu: nothing
-// Records in `work` everything phase 2 needs (the handles must stay alive until then).
-template <bool LATTICE>
-int phase1(const icon_mesh_t *mesh, const icon_feat_t *feat, int prior, float sdf_clip, int cmap_mode, const Calib &cal,
-           const LatticeMap &L, const float *d_points, int64_t N, int search, int8_t *d_signs_out, icon_work *work, hipStream_t st)
+// The MLP input rows of the call in work->d_x ([N, kXRow], reference channel order, slot kCodeSlot = code word) ...
+int feature_rows(QueryCall &c, icon_work *work, hipStream_t st)
+{
+    if (c.rows_ready) return ICON_OK;
+    int rc;
+    if ((rc = ensure_work(work, c.N, true))) return rc;
+    rc = c.src == Src::Lattice ? launch_features<Src::Lattice>(c, work, st)
+       : c.src == Src::Points ? launch_features<Src::Points>(c, work, st) : launch_features<Src::Batch>(c, work, st);
+    c.rows_ready = rc == ICON_OK;
+    return rc;
+}
+
+// ... with the reference-mode outlier cmap patched in from wherever the call's sign list is.  Idempotent per call.
+int materialise_rows(QueryCall &c, icon_work *work, const SignSrc &fs, hipStream_t st)
 {
     int rc;
-    work->q_mesh = mesh; work->q_feat = feat; work->q_prior = prior; work->q_sdf_clip = sdf_clip; work->q_cmap_mode = cmap_mode;
-    work->q_cal = cal; work->q_L = L; work->q_points = d_points; work->q_N = N; work->q_search = search; work->q_lattice = LATTICE;
-    work->q_rows_ready = false; work->slab_patched = false;
-    work->slab_needs_patch = (prior == ICON_PRIOR_ICON && cmap_mode == ICON_CMAP_REFERENCE && (feat->dev.smpl_mask & kSmplCmap));
-    work->slab_cmap_slot = feat->dev.csel + 1;
-    if (prior != ICON_PRIOR_ICON) return ICON_OK;
-    if (search == ICON_SEARCH_BRUTE) {
-        if ((rc = ensure_work(work, N, true))) return rc;
-        if ((rc = launch_features<LATTICE>(mesh, feat, prior, sdf_clip, cmap_mode, cal, L, d_points, N, search, work, st))) return rc;
-        work->q_rows_ready = true;
-    } else {
-        if ((rc = launch_nearest<LATTICE>(mesh, cal, L, d_points, N, sdf_clip, work, st))) return rc;
-    }
-    if (work->slab_needs_patch) {
-        int8_t *signs = d_signs_out ? d_signs_out : work->d_signs;
-        if ((rc = outlier_list(work, N, nullptr, signs, search != ICON_SEARCH_BRUTE, st))) return rc;
+    if ((rc = feature_rows(c, work, st))) return rc;
+    if (c.needs_patch && !c.patched) {
+        if ((rc = outlier_patch(work, c.N, c.cmap_slot, fs, st))) return rc;
+        c.patched = true;
     }
     return ICON_OK;
 }
 
-// The MLP input rows of the prepared call in work->d_x ([N, kXRow], reference channel order, slot kCodeSlot = code word),
-// the reference-mode outlier cmap patched in from wherever the call's sign list is.  Idempotent per prepared call.
-int materialise_rows(icon_work *work, const SignSrc &fs, hipStream_t st)
+}  // namespace
+
+int sign_and_list(const QueryCall &c, int8_t *d_signs_out, icon_work *work, hipStream_t st)
 {
     int rc;
-    const int prior = work->q_prior;
-    const int64_t N = work->q_N;
-    if (!work->q_rows_ready) {
-        if ((rc = ensure_work(work, N, true))) return rc;
-        rc = work->q_lattice ? launch_features<true>(work->q_mesh, work->q_feat, prior, work->q_sdf_clip, work->q_cmap_mode, work->q_cal, work->q_L,
-                                                     work->q_points, N, work->q_search, work, st)
-                             : launch_features<false>(work->q_mesh, work->q_feat, prior, work->q_sdf_clip, work->q_cmap_mode, work->q_cal, work->q_L,
-                                                      work->q_points, N, work->q_search, work, st);
-        if (rc) return rc;
-        work->q_rows_ready = true;
-    }
-    if (work->slab_needs_patch && !work->slab_patched) {
-        if ((rc = outlier_patch(work, N, work->slab_cmap_slot, fs, st))) return rc;
-        work->slab_patched = true;
-    }
+    if ((rc = launch_sign(c, work, st))) return rc;
+    if (!c.n_dev) debug_sync(c.src == Src::Batch ? "k_sign_wide<batch>" : "k_sign", st);      // (a schedule level names its whole tail: adaptive.hip)
+    if (c.needs_patch && (rc = outlier_list(work, c.N, c.n_dev, d_signs_out ? d_signs_out : work->d_signs, true, st))) return rc;
     return ICON_OK;
 }
 
-// Phase 2: the MLP input of every point and the MLP itself, given where the call's outlier signs are.
-// Lattice calls evaluate the planes [za, zb) of the prepared slab into the SLAB's buffer d_occ (several calls may
-// cover a slab piece by piece: the multi-GPU driver gathers the first half while the second is computed).
-int phase2(const icon_mlp_t *mlp, const SignSrc &fs, float *d_occ, int precision, icon_work *work, hipStream_t st, int za = 0, int zb = 0)
+int call_geometry(QueryCall &c, int8_t *d_signs_out, icon_work *work, hipStream_t st)
 {
     int rc;
-    const int prior = work->q_prior;
-    const int64_t N = work->q_N;
-    const bool fused = want_fused(precision, work->q_search);
-    const int local = (work->q_cmap_mode == ICON_CMAP_LOCAL) ? 1 : 0;
-    const LatticeMap &L = work->q_L;
-    const bool first = !work->q_lattice || za == L.z0;
-    if (fused) {
+    if (c.prior != ICON_PRIOR_ICON) return ICON_OK;
+    if (c.search == ICON_SEARCH_BRUTE) {         // the rows themselves (k_features<.., BRUTE> searches and signs), then the list from their code bytes
+        if ((rc = feature_rows(c, work, st))) return rc;
+        return c.needs_patch ? outlier_list(work, c.N, nullptr, d_signs_out ? d_signs_out : work->d_signs, false, st) : ICON_OK;
+    }
+    rc = c.src == Src::Points ? launch_nearest<false>(c, work, st) : c.src == Src::Lattice ? launch_nearest<true>(c, work, st) : launch_nearest_batch(c, work, st);
+    if (rc) return rc;
+    return sign_and_list(c, d_signs_out, work, st);
+}
+
+int call_finish(QueryCall &c, const icon_mlp *mlp, const SignSrc &fs, float *d_occ, int precision, icon_work *work, hipStream_t st, int za, int zb)
+{
+    int rc;
+    const LatticeMap &L = c.L;
+    const bool lattice = c.src == Src::Lattice;
+    const bool first = !lattice || za == L.z0;
+    if (want_fused(precision, c.search)) {
         if (first) mark(work, 2, st);
-        rc = launch_fused_f16x3(work->q_mesh, work->q_feat, mlp, prior, work->q_cal, L, za, zb, work->q_points, N,
-                                work->q_sdf_clip, local, work, fs, d_occ, work->q_lattice, st);
+        rc = launch_fused_f16x3(c, mlp, work, za, zb, fs, d_occ, st);
         mark(work, 3, st);
         return rc;
     }
-    if ((rc = materialise_rows(work, fs, st))) return rc;
+    if ((rc = materialise_rows(c, work, fs, st))) return rc;
     if (first) mark(work, 2, st);
-    if (work->q_lattice) {
+    if (lattice) {
         const int64_t o = (int64_t)(za - L.z0) * L.res * L.res, n = (int64_t)(zb - za) * L.res * L.res;
         rc = mlp_launch(mlp, work->d_x + o * kXRow, n, d_occ + o, precision, st);
     } else {
-        rc = mlp_launch(mlp, work->d_x, N, d_occ, precision, st);
+        rc = mlp_launch(mlp, work->d_x, c.N, d_occ, precision, st);
     }
     mark(work, 3, st);
     return rc;
 }
 
-}  // namespace
+}  // namespace icon
+
+// a point-mode call's calibration: h_calib (host, null = identity) or d_calib (device, read by the kernels themselves)
+static Calib points_calib(const float *h_calib, const float *d_calib)
+{
+    Calib cal;
+    memcpy(cal.m, h_calib ? h_calib : kIdentCalib, sizeof(cal.m));
+    cal.d = d_calib;
+    return cal;
+}
 
 static int query_points_impl(const icon_mesh_t *mesh, const icon_feat_t *feat, const icon_mlp_t *mlp,
                              int prior_type, float sdf_clip, int cmap_mode, const float *h_calib, const float *d_calib,
@@ -516,23 +500,18 @@ static int query_points_impl(const icon_mesh_t *mesh, const icon_feat_t *feat, c
 {
     ICON_ARG(mlp && work && d_points && d_occ, "icon_query_points: null argument");
     ICON_ARG(N >= 0, "icon_query_points: negative N");
-    int c0 = 0;
-    int rc = check_prior(mesh, feat, prior_type, &c0);
+    QueryCall c = query_call("icon_query_points", Src::Points, feat, prior_type, sdf_clip, cmap_mode, search);
+    c.mesh = mesh; c.cal = points_calib(h_calib, d_calib); c.points = d_points; c.N = N;
+    int rc = describe_call(c);
     if (rc) return rc;
-    ICON_ARG(c0 == mlp->c0, "icon_query_points: MLP input width does not match the feature layout");
+    ICON_ARG(c.c0 == mlp->c0, "icon_query_points: MLP input width does not match the feature layout");
     if (N == 0) return ICON_OK;
     hipStream_t st = (hipStream_t)stream;
-    if ((rc = ensure_work(work, N, false))) return rc;
-    Calib cal;
-    static const float ident[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
-    memcpy(cal.m, h_calib ? h_calib : ident, sizeof(cal.m));
-    cal.d = d_calib;
-    LatticeMap L{};
-    work->slab_ready = false;
+    if ((rc = begin_call(work, c))) return rc;
     mark(work, 0, st);
-    if ((rc = phase1<false>(mesh, feat, prior_type, sdf_clip, cmap_mode, cal, L, d_points, N, search, nullptr, work, st))) return rc;
+    if ((rc = call_geometry(c, nullptr, work, st))) return rc;
     mark(work, 1, st);
-    return phase2(mlp, self_signs(work, work->slab_needs_patch), d_occ, precision, work, st);
+    return call_finish(c, mlp, self_signs(work, c.needs_patch), d_occ, precision, work, st);
 }
 
 extern "C" int icon_query_points(const icon_mesh_t *mesh, const icon_feat_t *feat, const icon_mlp_t *mlp,
@@ -588,36 +567,33 @@ static int slab_features_impl(const icon_mesh_t *mesh, const icon_feat_t *feat, 
                               int search, icon_work_t *work, void *stream)
 {
     ICON_ARG(work != nullptr, "icon_grid_slab_features: work is null");
-    int c0 = 0;
-    int rc = check_prior(mesh, feat, prior_type, &c0);
+    QueryCall c = query_call("icon_grid_slab_features", Src::Lattice, feat, prior_type, sdf_clip, cmap_mode, search);
+    c.mesh = mesh;
+    int rc = describe_call(c);
     if (rc) return rc;
-    LatticeMap L;
     // the brute-force path computes rows for every point itself; everything else may skip the shell
-    if ((rc = lattice_map(res, z0, z1, prior_type == ICON_PRIOR_ICON ? mesh : nullptr, sdf_clip, search != ICON_SEARCH_BRUTE, &L))) return rc;
+    if ((rc = lattice_map(res, z0, z1, prior_type == ICON_PRIOR_ICON ? mesh : nullptr, sdf_clip, search != ICON_SEARCH_BRUTE, &c.L))) return rc;
     hipStream_t st = (hipStream_t)stream;
-    const int64_t N = (int64_t)L.nz * res * res;
+    const int64_t N = c.N = (int64_t)c.L.nz * res * res;
     ICON_ARG(N < (1ll << 31), "icon_grid_slab_features: more than 2^31 points in one slab");
-    if ((rc = ensure_work(work, N, false))) return rc;
-    Calib cal{};
-    work->slab_ready = false;
+    if ((rc = begin_call(work, c))) return rc;
     mark(work, 0, st);
-    if ((rc = phase1<true>(mesh, feat, prior_type, sdf_clip, cmap_mode, cal, L, nullptr, N, search, d_signs_local, work, st))) return rc;
-    work->slab_c0 = c0;
+    if ((rc = call_geometry(c, d_signs_local, work, st))) return rc;
     if (d_count_local) {
-        if (work->slab_needs_patch) ICON_HIP(hipMemcpyAsync(d_count_local, work->d_total, sizeof(int64_t), hipMemcpyDeviceToDevice, st));
+        if (c.needs_patch) ICON_HIP(hipMemcpyAsync(d_count_local, work->d_total, sizeof(int64_t), hipMemcpyDeviceToDevice, st));
         else ICON_HIP(hipMemsetAsync(d_count_local, 0, sizeof(int64_t), st));
     }
     if (d_msg) {
         const int64_t cap = msg_bytes - 8;                 // packed bytes available
         ICON_ARG(msg_bytes >= 8 && cap * 4 >= N, "icon_grid_slab_features_msg: message buffer too small (8 + ceil(points / 4) bytes)");
-        if (work->slab_needs_patch) {
+        if (c.needs_patch) {
             if ((rc = pack_sign_message(work, d_signs_local ? d_signs_local : work->d_signs, d_msg, cap, st))) return rc;
         } else {
             ICON_HIP(hipMemsetAsync(d_msg, 0, sizeof(int64_t), st));
         }
     }
     mark(work, 1, st);
-    work->slab_res = res; work->slab_z0 = z0; work->slab_z1 = z1; work->slab_ready = true;
+    work->slab = c; work->slab_ready = true;
     return ICON_OK;
 }
 
@@ -638,21 +614,28 @@ extern "C" int icon_grid_slab_features_msg(const icon_mesh_t *mesh, const icon_f
     return slab_features_impl(mesh, feat, prior_type, sdf_clip, cmap_mode, res, z0, z1, nullptr, nullptr, d_msg, msg_bytes, search, work, stream);
 }
 
+// the slab icon_grid_slab_features prepared on this workspace, if it is the one a finish call names
+static QueryCall *prepared_slab(icon_work *work, int res, int z0, int z1)
+{
+    const LatticeMap &L = work->slab.L;
+    return (work->slab_ready && L.res == res && L.z0 == z0 && L.z0 + L.nz == z1) ? &work->slab : nullptr;
+}
+
 extern "C" int icon_grid_slab_finish(const icon_mlp_t *mlp, int res, int z0, int z1,
                                      const int8_t *d_signs_global, int64_t k_total, int64_t rank_offset,
                                      float *d_occ, int precision, icon_work_t *work, void *stream)
 {
     ICON_ARG(mlp && work && d_occ, "icon_grid_slab_finish: null argument");
-    if (!work->slab_ready || work->slab_res != res || work->slab_z0 != z0 || work->slab_z1 != z1)
-        return fail(ICON_ERR_STATE, "icon_grid_slab_finish: no matching icon_grid_slab_features call on this workspace");
-    ICON_ARG(work->slab_c0 == mlp->c0, "icon_grid_slab_finish: MLP input width does not match the feature layout");
+    QueryCall *c = prepared_slab(work, res, z0, z1);
+    if (!c) return fail(ICON_ERR_STATE, "icon_grid_slab_finish: no matching icon_grid_slab_features call on this workspace");
+    ICON_ARG(c->c0 == mlp->c0, "icon_grid_slab_finish: MLP input width does not match the feature layout");
     SignSrc fs{};
-    if (work->slab_needs_patch) {
+    if (c->needs_patch) {
         ICON_ARG(k_total == 0 || d_signs_global != nullptr, "icon_grid_slab_finish: sign list is null");
         fs.mode = kSignGlobal; fs.list = d_signs_global; fs.k_host = k_total; fs.rank_offset = rank_offset;
     }
     work->slab_ready = false;
-    return phase2(mlp, fs, d_occ, precision, work, (hipStream_t)stream, z0, z1);
+    return call_finish(*c, mlp, fs, d_occ, precision, work, (hipStream_t)stream, z0, z1);
 }
 
 extern "C" int icon_grid_slab_finish_gathered(const icon_mlp_t *mlp, int res, int z0, int z1, int za, int zb,
@@ -660,30 +643,32 @@ extern "C" int icon_grid_slab_finish_gathered(const icon_mlp_t *mlp, int res, in
                                               float *d_occ, int precision, icon_work_t *work, void *stream)
 {
     ICON_ARG(mlp && work && d_occ, "icon_grid_slab_finish_gathered: null argument");
-    if (!work->slab_ready || work->slab_res != res || work->slab_z0 != z0 || work->slab_z1 != z1)
-        return fail(ICON_ERR_STATE, "icon_grid_slab_finish_gathered: no matching icon_grid_slab_features call on this workspace");
+    QueryCall *c = prepared_slab(work, res, z0, z1);
+    if (!c) return fail(ICON_ERR_STATE, "icon_grid_slab_finish_gathered: no matching icon_grid_slab_features call on this workspace");
     ICON_ARG(za >= z0 && zb > za && zb <= z1, "icon_grid_slab_finish_gathered: planes [za, zb) must lie inside the slab");
-    ICON_ARG(work->slab_c0 == mlp->c0, "icon_grid_slab_finish_gathered: MLP input width does not match the feature layout");
+    ICON_ARG(c->c0 == mlp->c0, "icon_grid_slab_finish_gathered: MLP input width does not match the feature layout");
     SignSrc fs{};
-    if (work->slab_needs_patch) {
+    if (c->needs_patch) {
         if (d_gathered) {
             ICON_ARG(world >= 1 && world <= kMaxWorld && rank >= 0 && rank < world, "icon_grid_slab_finish_gathered: bad world / rank");
             ICON_ARG(stride >= 8 && (stride & 7) == 0, "icon_grid_slab_finish_gathered: stride must be a multiple of 8 (int64 header)");
             fs.mode = kSignSeg; fs.gathered = (const int8_t *)d_gathered; fs.stride = stride; fs.world = world; fs.rank = rank;
         } else {
-            fs = self_signs(work, work->slab_needs_patch);              // no exchange: the slab's own list is the whole list
+            fs = self_signs(work, true);                                // no exchange: the slab's own list is the whole list
         }
     }
     // the slab stays prepared: its planes may be finished piece by piece (the next icon_grid_slab_features replaces it)
-    return phase2(mlp, fs, d_occ, precision, work, (hipStream_t)stream, za, zb);
+    return call_finish(*c, mlp, fs, d_occ, precision, work, (hipStream_t)stream, za, zb);
 }
 
 // ---- the MLP input rows of a call, handed out (regressors whose normalisation runs over the points of the call) ----
-static int copy_rows_out(icon_work *work, float *d_rows, hipStream_t st)
+static int rows_out(QueryCall &c, float *d_rows, icon_work *work, hipStream_t st)
 {
-    int rc = materialise_rows(work, self_signs(work, work->slab_needs_patch), st);
-    if (rc) return rc;
-    ICON_HIP(hipMemcpyAsync(d_rows, work->d_x, (size_t)work->q_N * kXRow * sizeof(float), hipMemcpyDeviceToDevice, st));
+    int rc;
+    if ((rc = begin_call(work, c))) return rc;
+    if ((rc = call_geometry(c, nullptr, work, st))) return rc;
+    if ((rc = materialise_rows(c, work, self_signs(work, c.needs_patch), st))) return rc;
+    ICON_HIP(hipMemcpyAsync(d_rows, work->d_x, (size_t)c.N * kXRow * sizeof(float), hipMemcpyDeviceToDevice, st));
     return ICON_OK;
 }
 
@@ -693,40 +678,27 @@ extern "C" int icon_query_rows(const icon_mesh_t *mesh, const icon_feat_t *feat,
 {
     ICON_ARG(work && d_points && d_rows, "icon_query_rows: null argument");
     ICON_ARG(N >= 0, "icon_query_rows: negative N");
-    int c0 = 0;
-    int rc = check_prior(mesh, feat, prior_type, &c0);
+    QueryCall c = query_call("icon_query_rows", Src::Points, feat, prior_type, sdf_clip, cmap_mode, search);
+    c.mesh = mesh; c.cal = points_calib(h_calib, d_calib); c.points = d_points; c.N = N;
+    const int rc = describe_call(c);
     if (rc) return rc;
     if (N == 0) return ICON_OK;
-    hipStream_t st = (hipStream_t)stream;
-    if ((rc = ensure_work(work, N, false))) return rc;
-    Calib cal;
-    static const float ident[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
-    memcpy(cal.m, h_calib ? h_calib : ident, sizeof(cal.m));
-    cal.d = d_calib;
-    LatticeMap L{};
-    work->slab_ready = false;
-    if ((rc = phase1<false>(mesh, feat, prior_type, sdf_clip, cmap_mode, cal, L, d_points, N, search, nullptr, work, st))) return rc;
-    return copy_rows_out(work, d_rows, st);
+    return rows_out(c, d_rows, work, (hipStream_t)stream);
 }
 
 extern "C" int icon_grid_rows(const icon_mesh_t *mesh, const icon_feat_t *feat, int prior_type, float sdf_clip, int cmap_mode,
                               int res, int z0, int z1, float *d_rows, int search, icon_work_t *work, void *stream)
 {
     ICON_ARG(work && d_rows, "icon_grid_rows: null argument");
-    int c0 = 0;
-    int rc = check_prior(mesh, feat, prior_type, &c0);
+    QueryCall c = query_call("icon_grid_rows", Src::Lattice, feat, prior_type, sdf_clip, cmap_mode, search);
+    c.mesh = mesh;
+    int rc = describe_call(c);
     if (rc) return rc;
-    LatticeMap L;
     // no shell skip: the rows of the shell are inputs of the call's statistics like any other (HGPIFuNet.py:361-363 masks afterwards)
-    if ((rc = lattice_map(res, z0, z1, nullptr, sdf_clip, false, &L))) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    const int64_t N = (int64_t)L.nz * res * res;
-    ICON_ARG(N < (1ll << 31), "icon_grid_rows: more than 2^31 points in one slab");
-    if ((rc = ensure_work(work, N, false))) return rc;
-    Calib cal{};
-    work->slab_ready = false;
-    if ((rc = phase1<true>(mesh, feat, prior_type, sdf_clip, cmap_mode, cal, L, nullptr, N, search, nullptr, work, st))) return rc;
-    return copy_rows_out(work, d_rows, st);
+    if ((rc = lattice_map(res, z0, z1, nullptr, sdf_clip, false, &c.L))) return rc;
+    c.N = (int64_t)c.L.nz * res * res;
+    ICON_ARG(c.N < (1ll << 31), "icon_grid_rows: more than 2^31 points in one slab");
+    return rows_out(c, d_rows, work, (hipStream_t)stream);
 }
 
 // k_walk_stats over the planes [z0, z1) of the res^3 lattice: clamp < 0 - the walk this mesh runs ("pair_box" / "node_box" /
@@ -786,10 +758,11 @@ extern "C" int icon_grid_eval_slab(const icon_mesh_t *mesh, const icon_feat_t *f
     ICON_ARG(mlp && work && d_occ, "icon_grid_eval_slab: null argument");
     int rc = icon_grid_slab_features(mesh, feat, prior_type, sdf_clip, cmap_mode, res, z0, z1, nullptr, nullptr, search, work, stream);
     if (rc) return rc;
-    ICON_ARG(work->slab_c0 == mlp->c0, "icon_grid_eval_slab: MLP input width does not match the feature layout");
+    QueryCall &c = work->slab;
+    ICON_ARG(c.c0 == mlp->c0, "icon_grid_eval_slab: MLP input width does not match the feature layout");
     // the slab's own sign list is the whole list (single call == whole lattice or caller's choice)
     work->slab_ready = false;
-    return phase2(mlp, self_signs(work, work->slab_needs_patch), d_occ, precision, work, (hipStream_t)stream, z0, z1);
+    return call_finish(c, mlp, self_signs(work, c.needs_patch), d_occ, precision, work, (hipStream_t)stream, z0, z1);
 }
 
 extern "C" int icon_sdf_query_ties(const icon_mesh_t *mesh, const float *d_points, int64_t N,
@@ -802,9 +775,8 @@ extern "C" int icon_sdf_query_ties(const icon_mesh_t *mesh, const float *d_point
     ICON_ARG(nb < (1ll << 31), "icon_sdf_query_ties: N too large for one launch");
     hipStream_t st = (hipStream_t)stream;
     icon_work tmp;
-    static const float ident[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
     const int32_t *perm = nullptr;
-    int rc = morton_order(&tmp, d_points, ident, nullptr, N, st, &perm);
+    int rc = morton_order(&tmp, d_points, kIdentCalib, nullptr, N, st, &perm);
     if (!rc) {
         hipLaunchKernelGGL(k_nearest_ties, dim3((unsigned)nb), dim3(kBlock), 0, st, mesh->dev, d_points, N, perm, d_face, d_face2, d_ulps);
         if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) rc = fail(ICON_ERR_HIP, "icon_sdf_query_ties: launch failed");

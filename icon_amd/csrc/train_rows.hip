@@ -3,7 +3,7 @@
 // 4.22, restated in numpy by tests/train_oracle.py.
 //
 // Forward (icon_train_rows_forward): the B*N points in subject-major order, as the batched query takes them.
-//   icon : batch_geometry (batch_query.hip: search, sign pass, batch-global outlier list - the launches of icon_query_points_batch),
+//   icon : call_geometry (the batched search, sign pass, batch-global outlier list - the launches of icon_query_points_batch),
 //          k_tr_point (SMPL channels of a point by sdf_attrs, its in_cube flag, its tap record), the existing cmap patch over those
 //          channels (outlier_patch), k_tr_rows (a lane per point and stack: the bilinear tap of S7 from the caller's [B,C,H,W] planes)
 //   pifu : k_tr_point (z, in_cube, tap record), k_tr_rows
@@ -409,28 +409,29 @@ extern "C" int icon_train_rows_forward(const icon_mesh_batch_t *mb, int prior_ty
     int rc;
     if ((rc = tr_shape(B, N, S, C, H, W, (icon_prior && has_vis) ? 2 : 1, what, &q))) return rc;
     q.smpl_mask = icon_prior ? ((has_cmap ? kSmplCmap : 0) | (has_norm ? kSmplNorm : 0)) : 0;
-    q.cin = q.csel + 1 + ((q.smpl_mask & kSmplCmap) ? 3 : 0) + ((q.smpl_mask & kSmplNorm) ? 3 : 0);
-    if (icon_prior) {
-        ICON_ARG(mb != nullptr, std::string(what) + ": the icon prior needs a mesh batch");
-        ICON_ARG(mb->B == B, std::string(what) + ": the mesh batch holds another number of subjects");
-    }
     ICON_ARG(((uintptr_t)d_taps & 15) == 0, std::string(what) + ": the tap records must be 16-byte aligned");
-    const int64_t NB = N * (int64_t)B;
+    // the call as the common steps see it: its rows in the workspace hold the SMPL channels alone ([sdf | cmap | norm] from slot 0 - a
+    // feature layout without image channels); the planes' channels are added per stack by k_tr_rows, so the width of a row of the
+    // result, q.cin, is not bounded by a workspace row
+    FeatDev smpl_rows{};
+    smpl_rows.n_select = 1; smpl_rows.csel = 0; smpl_rows.smpl_mask = q.smpl_mask;
+    QueryCall c = query_call(what, Src::Batch, nullptr, prior_type, sdf_clip, cmap_mode, search);
+    c.mb = mb; c.points = d_points; c.N = N * (int64_t)B;
+    c.bd.calibs = d_calibs; c.bd.n = N; c.bd.B = B;
+    if ((rc = describe_call(c, smpl_rows))) return rc;
+    q.cin = q.csel + c.c0;
+    const int64_t NB = c.N;
     hipStream_t st = (hipStream_t)stream;
-    if ((rc = ensure_work(work, NB, true))) return rc;
-    work->slab_ready = false;
-    work->q_rows_ready = false; work->slab_patched = false;
-    BatchDev bd{};
-    bd.meshes = icon_prior ? mb->d_table : nullptr; bd.calibs = d_calibs; bd.n = N; bd.B = B;
-    const bool needs_patch = icon_prior && cmap_mode == ICON_CMAP_REFERENCE && (q.smpl_mask & kSmplCmap);
+    if ((rc = begin_call(work, c, true))) return rc;
+    const BatchDev &bd = c.bd;
     const int local = (cmap_mode == ICON_CMAP_LOCAL) ? 1 : 0;
-    if (icon_prior && (rc = batch_geometry(mb, bd, d_points, N, B, sdf_clip, needs_patch, work, st))) return rc;
+    if ((rc = call_geometry(c, nullptr, work, st))) return rc;
     work->flag_clean = false;                                    // no fused kernel follows the sign pass here: the next one clears its own flag
     TrStacks stacks{};
     for (int s = 0; s < S; ++s) stacks.p[s] = d_stacks[s];
     TrTap *taps = static_cast<TrTap *>(d_taps);
     const unsigned nb = (unsigned)((NB + kBlock - 1) / kBlock);
-    const NearRef near = work_near(work, icon_prior ? mb->subj[0] : nullptr);
+    const NearRef near = work_near(work, c);
     if (icon_prior)
         hipLaunchKernelGGL(k_tr_point<ICON_PRIOR_ICON>, dim3(nb), dim3(kBlock), 0, st, q, bd, d_points, sdf_clip, local, near,
                            (const uint8_t *)work->d_code8, work->d_x, d_in_cube, taps);
@@ -438,7 +439,7 @@ extern "C" int icon_train_rows_forward(const icon_mesh_batch_t *mb, int prior_ty
         hipLaunchKernelGGL(k_tr_point<ICON_PRIOR_PIFU>, dim3(nb), dim3(kBlock), 0, st, q, bd, d_points, sdf_clip, local, near,
                            (const uint8_t *)work->d_code8, work->d_x, d_in_cube, taps);
     ICON_HIP(hipGetLastError());
-    if ((rc = outlier_patch(work, NB, 1, self_signs(work, needs_patch), st))) return rc;
+    if ((rc = outlier_patch(work, NB, c.cmap_slot, self_signs(work, c.needs_patch), st))) return rc;
     if (icon_prior)
         hipLaunchKernelGGL(k_tr_rows<ICON_PRIOR_ICON>, dim3(nb, (unsigned)S), dim3(kBlock), 0, st, q, stacks, TrStacks{}, (const TrTap *)taps, (const float *)work->d_x, d_rows);
     else

@@ -122,7 +122,19 @@ int ensure_work(icon_work *w, int64_t n_points, bool need_x)
     if (!w->d_seg) ICON_HIP(hipMalloc((void **)&w->d_seg, (kMaxWorld + 1) * sizeof(int64_t)));
     return ICON_OK;
 }
-int ensure_work_points(icon_work *w, int64_t n_points) { return ensure_work(w, n_points, false); }
+
+int begin_call(icon_work *w, const QueryCall &c, bool need_x)
+{
+    const int rc = ensure_work(w, c.N, need_x);
+    if (rc) return rc;
+    if (c.prior == ICON_PRIOR_ICON && c.mesh->F > kNearLoSlots && w->cap_points_hi < w->cap_points) {      // big meshes: the byte of higher slot bits
+        (void)hipFree(w->d_near_hi); w->d_near_hi = nullptr; w->cap_points_hi = 0;
+        ICON_HIP(hipMalloc((void **)&w->d_near_hi, (size_t)w->cap_points));
+        w->cap_points_hi = w->cap_points;
+    }
+    w->slab_ready = false;
+    return ICON_OK;
+}
 
 // the stride-(sx, sy, sz) sub-lattice of a [res]^3 volume: one thread per point, one store per wavefront that finds a value above
 // the level into a HOST-MAPPED word (visible to the host once the stream has drained: no copy, no second launch)
